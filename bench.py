@@ -20,6 +20,10 @@ film all-reduce when N > 1).  Default workload (`--config c3`): BASELINE config 
 
 For N > 1 the SAME image is sharded by 32x32 pixel tiles over the ranks (strong scaling) and the per-rank raw films are
 summed with one all-reduce before develop.  Prints ONE JSON line on rank 0 (contract: see the task statement).
+
+`--dump-outputs DIR` writes what the last timed step computed (image + raw film, or the PRB gradients) as DIR/<name>.npy once the
+clock has stopped.  Step k renders with seed k, so the same arguments give the same inputs on every run: two builds can be compared
+output for output (to float-atomic order in the film, see rmse_vs_oracle).
 """
 import argparse
 import json
@@ -84,7 +88,41 @@ def parse():
     p.add_argument("--main-only", action="store_true", help="only the timed steps of the named configuration: no host_visible / hg_phase / cpu_baseline legs (profiling: every dispatch of the render kernel then belongs to the workload)")
     p.add_argument("--backend", default="nccl", help="process-group backend; gloo allows a multi-rank rehearsal on a single GPU")
     p.add_argument("--cpu-spp", type=int, default=0, help="spp of the bounded CPU-baseline sample (0: calibrate to ~15 s)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
+
+
+DUMP_BYTES = 64 * 1000 * 1000
+DUMP_SEED = 20240229
+
+
+def dump_outputs(path, outputs, h, w):
+    """Writes `outputs` ({name: array}) as path/<name>.npy in float32 (float64 stays float64).  Arrays shaped (h, w, ...) are
+    per-pixel; when everything together exceeds DUMP_BYTES, each of them is cut to the same fixed, seeded sample of pixels
+    (flat indices y * w + x, ascending, in path/pixel_index.npy as float64), so that runs with the same arguments write the same
+    elements."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for name, v in outputs.items():
+        a = np.asarray(v)
+        arrs[name] = np.array(a, dtype=np.float64 if a.dtype == np.float64 else np.float32, order="C")
+    pixel = [k for k, a in arrs.items() if a.shape[:2] == (h, w)]
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_BYTES and pixel:
+        per_pixel = sum(arrs[k].nbytes for k in pixel) // (h * w) + 8          # + the float64 index
+        rest = total - sum(arrs[k].nbytes for k in pixel) + 128 * (len(arrs) + 1)      # + the .npy headers
+        n = max(1, min(h * w, (DUMP_BYTES - rest) // per_pixel))
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, size=n, replace=False))
+        for k in pixel:
+            arrs[k] = np.ascontiguousarray(arrs[k].reshape((h * w,) + arrs[k].shape[2:])[idx])
+        arrs["pixel_index"] = idx.astype(np.float64)
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {k: a.shape for k, a in arrs.items()}
 
 
 def kernel_source_id():
@@ -184,18 +222,21 @@ def main():
     grad = (np.ones((h, w, C - 1), np.float32) / (h * w * (C - 1))) if backward else None      # loss = mean(image)
 
     def step(seed):
+        """One timed step; returns what its caller receives: the developed image and the raw film (forward), the
+        parameter gradients (PRB)."""
         if backward:                                            # common.py:625-783: primal pass + adjoint replay
             g = scene.render_backward(grad, spp=spp, seed=seed, tile_rank=rank, tile_count=world, device=local_rank)
-            return reduce_gradients(g) if world > 1 else g
+            g = reduce_gradients(g) if world > 1 else g
+            return {"grad_" + k: v for k, v in g.items()}
         if world > 1:
             img, raw = render_distributed(scene, spp=spp, seed=seed)
-            return img
+            return {"image": img, "film": raw}
         dev = torch.device("cuda", local_rank)
         film = torch.zeros((h, w, C), dtype=torch.float32, device=dev)
         image = torch.empty((h, w, C - 1), dtype=torch.float32, device=dev)
         torch.cuda.synchronize()
         scene.render_to_device(film.data_ptr(), image.data_ptr(), spp=spp, seed=seed, device=local_rank)
-        return image
+        return {"image": image, "film": film}
 
     def fence():
         torch.cuda.synchronize()
@@ -209,9 +250,11 @@ def main():
     t0 = time.perf_counter()
     kern_ms = iters = shadows = launches = records = 0.0
     for i in range(a.steps):
-        step(i)
+        last = step(i)
         st = scene.stats()
         kern_ms += st["kernel_ms"]; iters += st["n_iter"]; shadows += st["n_shadow"]; launches += st["n_launches"]; records += st["n_records"]
+        if i + 1 < a.steps:
+            last = None                                         # only the last step's outputs outlive their step (--dump-outputs)
     fence()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -219,6 +262,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     value = n_samples * a.steps / dt / 1e6
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        host = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in last.items()}
+        dumped = dump_outputs(a.dump_outputs, host, h, w)
+    last = None
 
     # ---- roofline of the dominant kernel (k_render / k_render_prb: persistent, ONE launch per pass), this rank's launches.
     # Algorithmic bytes: every queued path record is written once and read once (RECORD_BYTES each way; fresh camera paths
@@ -273,6 +321,8 @@ def main():
                       "timed_region": "lrt_render / lrt_render_backward entry to the developed image (gradients) in device memory; scene resident in HBM",
                       "parallelism": "1 GPU" if world == 1 else f"32x32 pixel tiles over {world} GPUs + RCCL film all-reduce"},
            "roofline": roofline}
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": a.dump_outputs, "seed_of_step": a.steps - 1, "arrays": {k: list(s) for k, s in dumped.items()}}
     if cfg.get("published_msamples") and world == 1 and not (a.spp or a.width or a.height or a.scene or a.integrator):
         # BASELINE.md holds a published figure for exactly this scene, resolution and sample count (the reference's own time.txt;
         # hardware unstated there): the ratio is reported for this config only

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -66,3 +67,27 @@ def test_bench_f4_configs(config):
     j = last_json(r.stdout); ro = j["roofline"]
     assert ro["kernel"].startswith("lrt::k_render<101," if config == "het" else "lrt::k_render<5,") and ro["record_bytes"] == (104 if config == "het" else 168)
     assert j["value"] > 0 and ro["records_per_sample"] > 0 and j["data"].startswith("synthetic")
+
+
+@pytest.mark.parametrize("config,extra,names", [("c3", ["--spp", "16"], {"image", "film", "pixel_index"}),
+                                                ("c5", ["--spp", "4", "--width", "256", "--height", "256"], {"grad_sigma_t", "grad_albedo", "grad_g"})])
+def test_bench_dump_outputs(tmp_path, config, extra, names):
+    """--dump-outputs DIR: the last timed step's outputs as DIR/<name>.npy in float32 / float64, at most 64 MB in all; --steps sets the
+    number of timed steps"""
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--steps", "3", "--warmup", "1", "--main-only", "--dump-outputs", str(d)] + extra,
+                       capture_output=True, text=True, cwd=ROOT, env=ENV, timeout=600)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    j = last_json(r.stdout)
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["dumped_outputs"]["seed_of_step"] == 2
+    got = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert set(got) == names == set(j["dumped_outputs"]["arrays"])
+    assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 * 1000 * 1000
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+    if config == "c3":                                          # RGBA image + 5-channel film at 1920x1080: 75 MB, so a fixed pixel sample
+        h, w = j["config"]["height"], j["config"]["width"]; idx = got["pixel_index"]
+        assert h * w // 2 < len(idx) < h * w and np.all(np.diff(idx) > 0)
+        assert got["image"].shape == (len(idx), 4) and got["film"].shape == (len(idx), 5)
+        assert (got["film"][:, 4] > 0).all() and (got["image"][:, 3] == 1).all() and 0 < got["image"][:, :3].mean() < 10
+    else:
+        assert got["grad_sigma_t"].shape == (3,) and got["grad_albedo"].shape == (3,) and np.abs(got["grad_sigma_t"]).sum() > 0
