@@ -252,7 +252,8 @@ LRT_API void       lrt_scene_free(lrt_scene *scene);
  * Either may be NULL.  Both are overwritten: the film is cleared before the samples are accumulated (ImageBlock::clear, as
  * Film::prepare / SamplingIntegrator::render do before a render); with opts->output_on_device the two pointers are device
  * memory and the call returns after the library's stream has finished with them.  A tile shard (tile_count > 1) fills only
- * its own tiles' samples into the full-size film: shard films add up to the unsharded film.  */
+ * its own tiles' samples into the full-size film: shard films add up to the unsharded film.
+ * On a scene loaded with an `aov` integrator this renders the description's integrator (the first nested one): see lrt_render_aov.  */
 LRT_API lrt_status lrt_render(lrt_scene *scene, const lrt_render_opts *opts,
                               float *film_raw, float *image);
 LRT_API lrt_status lrt_render_stats_get(const lrt_scene *scene, lrt_render_stats *out);
@@ -322,6 +323,59 @@ LRT_API lrt_status lrt_image_write_exr(const char *path, int width, int height, 
  * blue-noise dithering of 8-bit conversions (src/core/struct.cpp:823-845) is not applied: values agree
  * with its PNGs to within one code value.                                                    */
 LRT_API lrt_status lrt_image_write_png(const char *path, int width, int height, int channels, const float *data);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * The `aov` integrator [v105] (src/integrators/aov.cpp): first-hit AOVs of the primary ray beside the images of nested
+ * integrators.  An XML `<integrator type="aov">` keeps the scene description an ordinary one: lrt_scene_desc.integrator holds
+ * the FIRST nested integrator (path defaults when there is none), so lrt_render on an aov scene renders that integrator alone.
+ * The AOV configuration lives beside the description:                                                                 */
+#define LRT_AOV_MAX_INTEGRATORS 4
+#define LRT_AOV_MAX_AOVS        16
+#define LRT_AOV_NAME_LEN        64
+/* AOV types (aov.cpp:142-196); duv_dx / duv_dy need ray differentials and are rejected (LRT_ERR_UNSUPPORTED) */
+enum { LRT_AOV_ALBEDO = 0,       /* .R .G .B  BSDF::eval_diffuse_reflectance                         */
+       LRT_AOV_DEPTH = 1,        /* .T        hit distance, 0 on a miss                              */
+       LRT_AOV_POSITION = 2,     /* .X .Y .Z                                                         */
+       LRT_AOV_UV = 3,           /* .U .V                                                            */
+       LRT_AOV_GEO_NORMAL = 4,   /* .X .Y .Z                                                         */
+       LRT_AOV_SH_NORMAL = 5,    /* .X .Y .Z  BSDF::sh_frame(si).n (bumpmap: in the local frame, as the reference returns it) */
+       LRT_AOV_DP_DU = 6,        /* .X .Y .Z                                                         */
+       LRT_AOV_DP_DV = 7,        /* .X .Y .Z                                                         */
+       LRT_AOV_PRIM_INDEX = 8,   /* .I        triangle index within its shape                        */
+       LRT_AOV_SHAPE_INDEX = 9   /* .I        1 + index into shapes[], 0 on a miss                   */ };
+
+typedef struct {
+    int32_t n_integrators;                                           /* nested integrators, in file order              */
+    lrt_integrator_desc integrators[LRT_AOV_MAX_INTEGRATORS];
+    char    integrator_names[LRT_AOV_MAX_INTEGRATORS][LRT_AOV_NAME_LEN];
+    int32_t n_aovs;
+    int32_t aov_types[LRT_AOV_MAX_AOVS];                             /* LRT_AOV_*                                      */
+    char    aov_names[LRT_AOV_MAX_AOVS][LRT_AOV_NAME_LEN];
+    int32_t n_aov_channels;   /* channels of the AOVs alone (the AOV film has n_aov_channels + 1: ..., W)                 */
+    int32_t n_channels;       /* developed output channels: the inner images' R,G,B[,A] each, then the AOV channels       */
+} lrt_aov_desc;
+
+/* LRT_ERR_INVALID when the scene has no aov integrator. */
+LRT_API lrt_status lrt_scene_aov_get(const lrt_scene *scene, lrt_aov_desc *out);
+/* Name of developed output channel c (0 <= c < n_channels): "<integrator name>.R" ... then "<aov name>.<suffix>"; NULL when
+ * the scene has no aov integrator or c is out of range.  The string lives as long as the scene. */
+LRT_API const char *lrt_aov_channel_name(const lrt_scene *scene, int c);
+/* AOVIntegrator::render (aov.cpp:369-395): every nested integrator renders as lrt_render would render it alone (same spp,
+ * seed), then one first-hit pass over all camera samples accumulates the AOVs through the reconstruction filter.
+ * image:        crop_h * crop_w * n_channels developed floats (merge_channels, aov.cpp:523-545); may be NULL.
+ * aov_film_raw: crop_h * crop_w * (n_aov_channels + 1) floats, the AOV pass's own film (AOV channels, then W); may be NULL.
+ * opts->integrator / max_depth / rr_depth / hide_emitters must be "use the scene's" (LRT_ERR_INVALID otherwise); spp, seed,
+ * device and output_on_device as in lrt_render.  tile_count > 1 is LRT_ERR_UNSUPPORTED, and so are lrt_render_multi,
+ * lrt_render_backward and lrt_render_backward_multi on an aov scene; so is a render in several passes of the independent
+ * sampler with two or more nested integrators.                                                                        */
+LRT_API lrt_status lrt_render_aov(lrt_scene *scene, const lrt_render_opts *opts, float *aov_film_raw, float *image);
+/* Test hook: the AOV values of lanes [lane_begin, lane_begin + n) of the AOV pass before film accumulation (its first pass
+ * only): out is n * n_aov_channels floats. */
+LRT_API lrt_status lrt_render_aov_samples(lrt_scene *scene, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out);
+/* Multi-channel float32 EXR with named channels (uncompressed; channel list sorted by name as OpenEXR requires, data
+ * permuted to match).  data: h * w * n_channels floats in the order of `names`. */
+LRT_API lrt_status lrt_image_write_exr_channels(const char *path, int width, int height, int n_channels,
+                                                const char *const *names, const float *data);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Learned subsurface model, network stage only: the shape-adaptive scatter network of

@@ -113,7 +113,7 @@ def cornell_box():
 
 # ------------------------------------------------------------- dict -> XML
 _TAGS = {
-    "scene": "scene", "path": "integrator", "volpath": "integrator", "prbvolpath": "integrator",
+    "scene": "scene", "path": "integrator", "volpath": "integrator", "prbvolpath": "integrator", "aov": "integrator",
     "biovolpath": "integrator", "biovolpath06": "integrator", "volpathmis": "integrator",
     "perspective": "sensor", "independent": "sampler", "ldsampler": "sampler", "hdrfilm": "film",
     "box": "rfilter", "gaussian": "rfilter", "tent": "rfilter",
@@ -135,7 +135,7 @@ def _fmt(v):
     return repr(float(v))
 
 
-def _dict_to_xml(name, d, out, indent, top_ids):
+def _dict_to_xml(name, d, out, indent, top_ids, parent=None):
     typ = d.get("type")
     if typ == "ref":
         out.append(f'{indent}<ref id="{_esc(d["id"])}"' + (f' name="{_esc(name)}"' if name and name not in ("bsdf",) else "") + "/>")
@@ -157,13 +157,15 @@ def _dict_to_xml(name, d, out, indent, top_ids):
         elif tag not in ("integrator", "sensor", "sampler", "film", "rfilter", "phase") and not (tag == "bsdf" and name == "bsdf") \
                 and not (tag == "emitter" and name == "emitter"):
             attrs += f' name="{_esc(name)}"'
+        elif tag == "integrator" and parent == "integrator":
+            attrs += f' name="{_esc(name)}"'            # a nested integrator of `aov`: the key names its image (aov.cpp:115-125)
     out.append(f"{indent}<{tag}{attrs}>")
     sub = indent + "    "
     for k, v in d.items():
         if k == "type":
             continue
         if isinstance(v, dict):
-            _dict_to_xml(k, v, out, sub, top_ids)
+            _dict_to_xml(k, v, out, sub, top_ids, tag)
         elif isinstance(v, ScalarTransform4f):
             m = " ".join(_fmt(x) for x in v.matrix.reshape(-1))
             out.append(f'{sub}<transform name="{_esc(k)}"><matrix value="{m}"/></transform>')
@@ -243,9 +245,50 @@ class Scene:
         d = self.desc
         return [d.media[i].id.decode() for i in range(d.n_media)]
 
+    # -- the aov integrator ------------------------------------------------
+    def aov_desc(self):
+        """lrt_aov_desc of a scene loaded with an `aov` integrator, None for any other scene."""
+        a = _lib.AovDesc()
+        return a if self._lib.lrt_scene_aov_get(self._h, C.byref(a)) == _lib.OK else None
+
+    def is_aov(self):
+        return self.aov_desc() is not None
+
+    def aov_channel_names(self):
+        """Names of the channels render() returns on an aov scene: each nested integrator's <name>.R/.G/.B[/.A], then the AOVs'
+        <name>.<suffix> (aov.cpp merge_channels)."""
+        a = self.aov_desc()
+        if a is None:
+            raise RuntimeError("aov_channel_names(): the scene has no aov integrator")
+        return [self._lib.lrt_aov_channel_name(self._h, c).decode() for c in range(a.n_channels)]
+
+    def render_aov_samples(self, lane_begin, n, **kw):
+        """lrt_render_aov_samples (test hook): the AOV values of lanes [lane_begin, lane_begin + n) of the AOV pass (its first
+        pass), before film accumulation: (n, n_aov_channels) float32."""
+        a = self.aov_desc()
+        if a is None:
+            raise RuntimeError("render_aov_samples(): the scene has no aov integrator")
+        out = np.empty((n, a.n_aov_channels), dtype=np.float32)
+        o = make_opts(None, None, None, None, kw.get("spp", 0), kw.get("seed", 0), 0, 1, kw.get("device", 0))
+        _lib.check(self._lib.lrt_render_aov_samples(self._h, C.byref(o), int(lane_begin), int(n), out.ctypes.data))
+        return out
+
+    def _render_aov(self, a, spp, seed, integrator, max_depth, rr_depth, hide_emitters, tile_rank, tile_count, device, return_raw):
+        f = self.desc.film
+        img = np.empty((f.crop_height, f.crop_width, a.n_channels), dtype=np.float32)
+        raw = np.empty((f.crop_height, f.crop_width, a.n_aov_channels + 1), dtype=np.float32) if return_raw else None
+        o = make_opts(integrator, max_depth, rr_depth, hide_emitters, spp, seed, tile_rank, tile_count, device)
+        _lib.check(self._lib.lrt_render_aov(self._h, C.byref(o), raw.ctypes.data if return_raw else None, img.ctypes.data))
+        return (img, raw) if return_raw else img
+
     # -- rendering ---------------------------------------------------------
     def render(self, spp=0, seed=0, integrator=None, max_depth=None, rr_depth=None, hide_emitters=None,
                tile_rank=0, tile_count=1, device=0, return_raw=False):
+        """Developed H x W x (3|4) image; on a scene with an `aov` integrator H x W x n_channels (aov_channel_names()), and with
+        return_raw the AOV pass's film (AOV channels, then W) as the second value."""
+        a = self.aov_desc()
+        if a is not None:
+            return self._render_aov(a, spp, seed, integrator, max_depth, rr_depth, hide_emitters, tile_rank, tile_count, device, return_raw)
         h, w, c = self.film_shape()
         img = np.empty((h, w, c), dtype=np.float32)
         raw = np.empty((h, w, self.raw_channels()), dtype=np.float32) if return_raw else None
@@ -431,7 +474,8 @@ def load_dict(d, base_dir="."):
 
 
 def render(scene, spp=0, seed=0, integrator=None, **kw):
-    """mi.render(scene, spp=..., seed=...): developed H x W x (3|4) float32 image."""
+    """mi.render(scene, spp=..., seed=...): developed H x W x (3|4) float32 image (an aov scene: H x W x n_channels, the inner
+    images then the AOVs, channel names from scene.aov_channel_names())."""
     return scene.render(spp=spp, seed=seed, integrator=integrator, **kw)
 
 
@@ -498,11 +542,20 @@ def write_png(path, image):
     _lib.check(_lib.lib().lrt_image_write_png(os.fspath(path).encode(), img.shape[1], img.shape[0], img.shape[2], img.ctypes.data))
 
 
-def write_exr(path, image):
+def write_exr(path, image, channel_names=None):
+    """Uncompressed float32 EXR.  Without `channel_names`: 1, 3 or 4 channels named Y / R,G,B / R,G,B,A.  With them (one name per
+    channel, e.g. scene.aov_channel_names()): any number of channels, written sorted by name as OpenEXR requires."""
     img = np.ascontiguousarray(image, dtype=np.float32)
     if img.ndim == 2:
         img = img[..., None]
-    _lib.check(_lib.lib().lrt_image_write_exr(os.fspath(path).encode(), img.shape[1], img.shape[0], img.shape[2], img.ctypes.data))
+    if channel_names is None:
+        _lib.check(_lib.lib().lrt_image_write_exr(os.fspath(path).encode(), img.shape[1], img.shape[0], img.shape[2], img.ctypes.data))
+        return
+    names = [str(n) for n in channel_names]
+    if len(names) != img.shape[2]:
+        raise ValueError(f"write_exr: {len(names)} channel names for an image of {img.shape[2]} channels")
+    arr = (C.c_char_p * len(names))(*[n.encode() for n in names])
+    _lib.check(_lib.lib().lrt_image_write_exr_channels(os.fspath(path).encode(), img.shape[1], img.shape[0], img.shape[2], arr, img.ctypes.data))
 
 
 # ---- the handful of image-side names the reference's drivers use (MitsubaRunner.py:166-167, LiverRenderer.py:383-385),

@@ -78,6 +78,19 @@ class SceneDesc(C.Structure):
                 ("sampler_type", C.c_uint32), ("samples_per_pass", C.c_uint32), ("use_spectral_mis", C.c_uint32), ("pad", C.c_uint32)]
 
 
+AOV_MAX_INTEGRATORS, AOV_MAX_AOVS, AOV_NAME_LEN = 4, 16, 64
+AOV_TYPES = {"albedo": 0, "depth": 1, "position": 2, "uv": 3, "geo_normal": 4, "sh_normal": 5, "dp_du": 6, "dp_dv": 7,
+             "prim_index": 8, "shape_index": 9}
+
+
+class AovDesc(C.Structure):
+    """lrt_aov_desc: the aov integrator's nested integrators and AOVs (include/liverrt.h)."""
+    _fields_ = [("n_integrators", C.c_int32), ("integrators", IntegratorDesc * AOV_MAX_INTEGRATORS),
+                ("integrator_names", (C.c_char * AOV_NAME_LEN) * AOV_MAX_INTEGRATORS),
+                ("n_aovs", C.c_int32), ("aov_types", C.c_int32 * AOV_MAX_AOVS), ("aov_names", (C.c_char * AOV_NAME_LEN) * AOV_MAX_AOVS),
+                ("n_aov_channels", C.c_int32), ("n_channels", C.c_int32)]
+
+
 class RenderOpts(C.Structure):
     _fields_ = [("integrator", C.c_int32), ("max_depth", C.c_int32), ("rr_depth", C.c_int32), ("hide_emitters", C.c_int32),
                 ("spp", C.c_uint32), ("seed", C.c_uint32), ("tile_rank", C.c_uint32), ("tile_count", C.c_uint32),
@@ -180,8 +193,15 @@ def lib():
     L.lrt_image_free.restype = None
     L.lrt_image_write_exr.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.lrt_image_write_png.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.lrt_image_write_exr_channels.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, P(C.c_char_p), C.c_void_p]
+    L.lrt_scene_aov_get.argtypes = [C.c_void_p, P(AovDesc)]
+    L.lrt_aov_channel_name.argtypes = [C.c_void_p, C.c_int]
+    L.lrt_aov_channel_name.restype = C.c_char_p
+    L.lrt_render_aov.argtypes = [C.c_void_p, P(RenderOpts), C.c_void_p, C.c_void_p]
+    L.lrt_render_aov_samples.argtypes = [C.c_void_p, P(RenderOpts), C.c_uint64, C.c_uint32, C.c_void_p]
     for name in ("lrt_image_read", "lrt_image_write_exr", "lrt_image_write_png", "lrt_scene_load_xml", "lrt_scene_load_xml_string", "lrt_scene_from_desc", "lrt_render", "lrt_render_multi", "lrt_render_backward_multi", "lrt_math_eval", "lrt_render_stats_get",
-                 "lrt_film_develop", "lrt_render_samples", "lrt_render_backward", "lrt_trace", "lrt_param_set", "lrt_param_get"):
+                 "lrt_film_develop", "lrt_render_samples", "lrt_render_backward", "lrt_trace", "lrt_param_set", "lrt_param_get",
+                 "lrt_image_write_exr_channels", "lrt_scene_aov_get", "lrt_render_aov", "lrt_render_aov_samples"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -191,7 +211,8 @@ EXPORTED_SYMBOLS = ["lrt_last_error", "lrt_version", "lrt_scene_load_xml", "lrt_
                     "lrt_scene_desc_get", "lrt_scene_free", "lrt_render", "lrt_render_multi", "lrt_render_backward_multi", "lrt_math_eval", "lrt_render_stats_get", "lrt_film_develop",
                     "lrt_render_samples", "lrt_render_backward", "lrt_trace", "lrt_param_set", "lrt_param_get",
                     "lrt_image_read", "lrt_image_free", "lrt_image_write_exr", "lrt_image_write_png",
-                    "lrt_vae_model_create", "lrt_vae_model_free", "lrt_vae_scatter"]
+                    "lrt_vae_model_create", "lrt_vae_model_free", "lrt_vae_scatter",
+                    "lrt_scene_aov_get", "lrt_aov_channel_name", "lrt_render_aov", "lrt_render_aov_samples", "lrt_image_write_exr_channels"]
 
 
 def check(status):

@@ -28,7 +28,7 @@ static lrt_status fail(lrt_status st, const std::string &msg) { g_error = msg; r
 extern "C" {
 
 const char *lrt_last_error(void) { return g_error.c_str(); }
-int lrt_version(void) { return 104; }    // 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
+int lrt_version(void) { return 105; }    // 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
 
 static std::vector<std::pair<std::string, std::string>> parse_defines(const char *const *defines, int n) {
     std::vector<std::pair<std::string, std::string>> r;
@@ -184,6 +184,7 @@ lrt_status lrt_render(lrt_scene *scene, const lrt_render_opts *opts, float *film
 lrt_status lrt_render_multi(lrt_scene *scene, const lrt_render_opts *opts, int n_devices, const int *device_ids, float *film_raw, float *image) {
     if (!scene) return fail(LRT_ERR_INVALID, "lrt_render_multi: null scene");
     LRT_TRY
+        if (scene->st.has_aov) return fail(LRT_ERR_UNSUPPORTED, "lrt_render_multi: an aov scene renders on one device (lrt_render_aov)");
         if (opts && (opts->tile_count > 1 || opts->tile_rank != 0)) throw std::invalid_argument("lrt_render_multi shards the image itself: tile_rank / tile_count must be 0 / 1 (or 0 / 0)");
         ensure_devices(scene, n_devices, device_ids);
         device_render_multi(scene->multi, scene->multi_ctx, scene->st.desc, opts, film_raw, image, scene->stats);
@@ -194,6 +195,7 @@ lrt_status lrt_render_multi(lrt_scene *scene, const lrt_render_opts *opts, int n
 lrt_status lrt_render_backward_multi(lrt_scene *scene, const lrt_render_opts *opts, int n_devices, const int *device_ids, const float *grad_image, lrt_param_grads *out) {
     if (!scene || !grad_image || !out) return fail(LRT_ERR_INVALID, "lrt_render_backward_multi: null argument");
     LRT_TRY
+        if (scene->st.has_aov) return fail(LRT_ERR_UNSUPPORTED, "lrt_render_backward_multi: the aov integrator has no adjoint here");
         if (opts && (opts->tile_count > 1 || opts->tile_rank != 0)) throw std::invalid_argument("lrt_render_backward_multi shards the image itself: tile_rank / tile_count must be 0 / 1 (or 0 / 0)");
         ensure_devices(scene, n_devices, device_ids);
         device_render_backward_multi(scene->multi, scene->multi_ctx, scene->st.desc, opts, grad_image, out, scene->stats);
@@ -234,9 +236,53 @@ lrt_status lrt_render_samples(lrt_scene *scene, const lrt_render_opts *opts, uin
 
 lrt_status lrt_render_backward(lrt_scene *scene, const lrt_render_opts *opts, const float *grad_image, lrt_param_grads *out) {
     if (!scene || !grad_image || !out) return fail(LRT_ERR_INVALID, "lrt_render_backward: null argument");
+    if (scene->st.has_aov) return fail(LRT_ERR_UNSUPPORTED, "lrt_render_backward: the aov integrator has no adjoint here");
     LRT_TRY
         ensure_device(scene, opts ? opts->device : 0);
         device_render_backward(scene->dev, scene->st.desc, opts, grad_image, out, scene->stats);
+        return LRT_OK;
+    LRT_CATCH
+}
+
+// ---- the aov integrator
+lrt_status lrt_scene_aov_get(const lrt_scene *scene, lrt_aov_desc *out) {
+    if (!scene || !out) return fail(LRT_ERR_INVALID, "lrt_scene_aov_get: null argument");
+    if (!scene->st.has_aov) return fail(LRT_ERR_INVALID, "lrt_scene_aov_get: the scene has no aov integrator");
+    *out = scene->st.aov; return LRT_OK;
+}
+
+const char *lrt_aov_channel_name(const lrt_scene *scene, int c) {
+    if (!scene || !scene->st.has_aov || c < 0 || c >= (int) scene->st.aov_channel_names.size()) return nullptr;
+    return scene->st.aov_channel_names[(size_t) c].c_str();
+}
+
+// the integrator comes from the scene: lrt_render_opts may not override what the nested integrators are
+static lrt_status check_aov_call(const lrt_scene *scene, const lrt_render_opts *opts, const char *fn) {
+    if (!scene->st.has_aov) return fail(LRT_ERR_INVALID, std::string(fn) + ": the scene has no aov integrator");
+    if (opts && (opts->integrator != -1 || opts->max_depth != -2 || opts->rr_depth != -1 || opts->hide_emitters != -1))
+        return fail(LRT_ERR_INVALID, std::string(fn) + ": integrator, max_depth, rr_depth and hide_emitters come from the scene's aov integrator (leave them at -1 / -2 / -1 / -1)");
+    if (opts && opts->tile_count > 1) return fail(LRT_ERR_UNSUPPORTED, std::string(fn) + ": tile sharding of an aov render is not supported");
+    return LRT_OK;
+}
+
+lrt_status lrt_render_aov(lrt_scene *scene, const lrt_render_opts *opts, float *aov_film_raw, float *image) {
+    if (!scene) return fail(LRT_ERR_INVALID, "lrt_render_aov: null scene");
+    lrt_status st = check_aov_call(scene, opts, "lrt_render_aov");
+    if (st != LRT_OK) return st;
+    LRT_TRY
+        ensure_device(scene, opts ? opts->device : 0);
+        device_render_aov(scene->dev, scene->st.desc, scene->st.aov, opts, aov_film_raw, image, scene->stats);
+        return LRT_OK;
+    LRT_CATCH
+}
+
+lrt_status lrt_render_aov_samples(lrt_scene *scene, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out) {
+    if (!scene || !out) return fail(LRT_ERR_INVALID, "lrt_render_aov_samples: null argument");
+    lrt_status st = check_aov_call(scene, opts, "lrt_render_aov_samples");
+    if (st != LRT_OK) return st;
+    LRT_TRY
+        ensure_device(scene, opts ? opts->device : 0);
+        device_render_aov_samples(scene->dev, scene->st.desc, scene->st.aov, opts, lane_begin, n, out, scene->stats);
         return LRT_OK;
     LRT_CATCH
 }
@@ -345,6 +391,16 @@ lrt_status lrt_image_write_exr(const char *path, int width, int height, int chan
     if (!path || !data) return fail(LRT_ERR_INVALID, "lrt_image_write_exr: null argument");
     LRT_TRY
         write_exr(path, width, height, channels, data);
+        return LRT_OK;
+    LRT_CATCH
+}
+
+lrt_status lrt_image_write_exr_channels(const char *path, int width, int height, int n_channels, const char *const *names, const float *data) {
+    if (!path || !names || !data) return fail(LRT_ERR_INVALID, "lrt_image_write_exr_channels: null argument");
+    LRT_TRY
+        std::vector<std::string> nm;
+        for (int c = 0; c < n_channels; ++c) { if (!names[c]) throw std::invalid_argument("lrt_image_write_exr_channels: null channel name"); nm.emplace_back(names[c]); }
+        write_exr_channels(path, width, height, nm, data);
         return LRT_OK;
     LRT_CATCH
 }

@@ -5,6 +5,8 @@
 #include "device_scene.h"
 #include "kernels_prb.h"
 #include "kernels_vae.h"
+#include "kernels_aov.h"
+#include <functional>
 #include "bvh.h"
 #include <cmath>
 #include <array>
@@ -65,6 +67,9 @@ struct DeviceScene {
     bool has_area_emitter = false;         // decides the record layout: only an area emitter's pdf reads the last scatter position (kernels.h, store_state)
     bool prb_null = false;                 // prbvolpath.py:84-91 `handle_null_scattering`: a heterogeneous medium is attached to a shape
     DLdsInfo lds{}; bool use_lds = false; int n_cus = 256; int bvh_leaf = 4;
+    // aov integrator: the AOV table (device copy), the AOV film and the inner images / merged image of the last aov render
+    DAovSpec *d_aov_spec = nullptr; uint32_t *d_first_face = nullptr;
+    float *aov_film = nullptr; size_t aov_film_floats = 0; float *aov_image = nullptr; size_t aov_image_floats = 0; float *aov_inner = nullptr; size_t aov_inner_floats = 0;
 
     template <typename T> T *track(T *p) { allocs.push_back((void *) p); return p; }
     void release(void *p) {                // free one tracked allocation now (a workspace that is being replaced by a larger one)
@@ -321,7 +326,7 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
 #ifndef LRT_DEV_BLOCK
 #define LRT_DEV_BLOCK 1024
 #endif
-            LRT_SMEM((k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD>)); LRT_SMEM((k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD, true>)); LRT_SMEM((k_trace_lds<true>)); LRT_SMEM((k_trace_lds<false>));
+            LRT_SMEM((k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD>)); LRT_SMEM((k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD, true>)); LRT_SMEM((k_trace_lds<true>)); LRT_SMEM((k_trace_lds<false>)); LRT_SMEM((k_aov<true, false>)); LRT_SMEM((k_aov<true, true>));
 #else
             LRT_SMEM((k_render<LRT_INTEGRATOR_PATH, 1024, true, false>)); LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH, 1024, true, false>));
             LRT_SMEM((k_render<LRT_INTEGRATOR_PATH, 1024, true, true>)); LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH, 1024, true, true>));
@@ -340,7 +345,7 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
             LRT_SMEM((k_render_prb<false, 1024, true, true>)); LRT_SMEM((k_render_prb<true, 1024, true, true>));
             LRT_SMEM((k_render_prb<false, 1024, true, false, true>)); LRT_SMEM((k_render_prb<true, 1024, true, false, true>));
             LRT_SMEM((k_render_prb<false, 1024, true, true, true>)); LRT_SMEM((k_render_prb<true, 1024, true, true, true>));
-            LRT_SMEM((k_trace_lds<true>)); LRT_SMEM((k_trace_lds<false>));
+            LRT_SMEM((k_trace_lds<true>)); LRT_SMEM((k_trace_lds<false>)); LRT_SMEM((k_aov<true, false>)); LRT_SMEM((k_aov<true, true>));
 #endif
             #undef LRT_SMEM
             D->use_lds = true;
@@ -797,7 +802,17 @@ static void run_wavefront(DeviceScene *D, const lrt_scene_desc &d, const Resolve
     finish_stats(D, log, e_begin, e_end, n_lanes, stats);
 }
 
+// after_pass (the aov integrator with one nested integrator): called after each pass's colour work, while D->cur_pass_in still
+// holds the sampler states at the start of that pass
+static void render_passes(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, float *film_raw, float *image, lrt_render_stats &stats,
+                          const std::function<void(const ResolvedOpts &)> &after_pass);
+
 void device_render(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, float *film_raw, float *image, lrt_render_stats &stats) {
+    render_passes(D, d, opts, film_raw, image, stats, nullptr);
+}
+
+static void render_passes(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, float *film_raw, float *image, lrt_render_stats &stats,
+                          const std::function<void(const ResolvedOpts &)> &after_pass) {
     HIP_CHECK(hipSetDevice(D->device));
     ResolvedOpts O = resolve(d, opts);
     const DFilm &F = D->sc.film;
@@ -827,6 +842,7 @@ void device_render(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opt
             run_wavefront(D, d, O, 0, n_lanes, pixel_list, film, nullptr, st1);
             total.n_samples += st1.n_samples; total.n_iter += st1.n_iter; total.n_shadow += st1.n_shadow; total.n_launches += st1.n_launches;
             total.n_records += st1.n_records; total.kernel_ms += st1.kernel_ms; total.total_ms += st1.total_ms;
+            if (after_pass) after_pass(O);
             continue;
         }
         // wide reconstruction filters: per-lane radiance first (16 B / lane, chunks of at most 2^28 lanes), then an in-order
@@ -844,6 +860,7 @@ void device_render(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opt
             total.n_samples += st1.n_samples; total.n_iter += st1.n_iter; total.n_shadow += st1.n_shadow; total.n_launches += st1.n_launches;
             total.n_records += st1.n_records; total.kernel_ms += st1.kernel_ms; total.total_ms += st1.total_ms;
         }
+        if (after_pass) after_pass(O);
     }
     D->cur_pass_in = nullptr; D->cur_pass_out = nullptr;
     total.lds_resident = D->use_lds ? 1 : 0;
@@ -889,6 +906,157 @@ void device_render_samples(DeviceScene *D, const lrt_scene_desc &d, const lrt_re
         HIP_CHECK(hipStreamSynchronize(D->stream));
     } catch (...) { (void) hipFree(d_out); throw; }
     HIP_CHECK(hipFree(d_out));
+}
+
+// ------------------------------------------------------------------ the aov integrator (kernels_aov.h)
+static float *aov_buffer(DeviceScene *D, float *&buf, size_t &have, size_t floats) {
+    if (have < floats) { D->release(buf); buf = nullptr; HIP_CHECK(hipMalloc((void **) &buf, std::max<size_t>(floats, 1) * 4)); D->track(buf); have = floats; }
+    return buf;
+}
+
+// The AOV table and the shapes' first faces, uploaded (stream-ordered) before each aov render.
+static void upload_aov_spec(DeviceScene *D, const lrt_scene_desc &d, const lrt_aov_desc &aov) {
+    if (!D->d_aov_spec) { HIP_CHECK(hipMalloc((void **) &D->d_aov_spec, sizeof(DAovSpec))); D->track(D->d_aov_spec); }
+    if (!D->d_first_face) {
+        std::vector<uint32_t> ff(std::max<uint32_t>(d.n_shapes, 1), 0u);
+        for (uint32_t i = 0; i < d.n_shapes; ++i) ff[i] = d.shapes[i].first_face;
+        D->d_first_face = D->track(dev_upload(ff.data(), ff.size(), D->stream));
+    }
+    static thread_local DAovSpec h;              // the source of an asynchronous copy: outlives the call
+    h = DAovSpec{}; h.n_aovs = aov.n_aovs; h.first_face = D->d_first_face;
+    int off = 0;
+    for (int k = 0; k < aov.n_aovs; ++k) {
+        h.type[k] = aov.aov_types[k]; h.offset[k] = off;
+        off += aov.aov_types[k] == LRT_AOV_DEPTH || aov.aov_types[k] >= LRT_AOV_PRIM_INDEX ? 1 : aov.aov_types[k] == LRT_AOV_UV ? 2 : 3;
+    }
+    h.n_ch = off;
+    if (off != aov.n_aov_channels) throw std::runtime_error("aov: channel count mismatch");
+    HIP_CHECK(hipMemcpyAsync(D->d_aov_spec, &h, sizeof(DAovSpec), hipMemcpyHostToDevice, D->stream));
+    HIP_CHECK(hipStreamSynchronize(D->stream));
+}
+
+// One launch of k_aov over lanes [lane_begin, lane_begin + n) of pass O.pass: into `film`, or per lane into `sample_out`.
+static void launch_aov(DeviceScene *D, const lrt_scene_desc &d, const ResolvedOpts &O, uint64_t lane_begin, uint64_t n, float *film, float *sample_out,
+                       const unsigned long long *pass_in, unsigned long long *pass_out) {
+    if (!n) return;
+    hipStream_t st = D->stream;
+    DRenderParams rp = make_params(d, O, n);
+    rp.pass_in = pass_in; rp.pass_out = pass_out;
+    DLaunch a{}; a.rp = rp; a.li = D->lds; a.lane_begin = lane_begin; a.n = n; a.film = film; a.sample_out = sample_out; a.sample_base = lane_begin;
+    const LaunchPtr lp = push_launch(D, a);
+    const AovSpecPtr spec = (AovSpecPtr) D->d_aov_spec;
+    if (D->use_lds) {
+        const uint32_t g = (uint32_t) std::min<uint64_t>((uint64_t) D->n_cus, (n + 1023) / 1024);       // one workgroup per CU: the LDS image is copied once
+        if (rp.ld_count) k_aov<true, true><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, lp, spec);
+        else k_aov<true, false><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, lp, spec);
+    } else {
+        const uint32_t g = (uint32_t) std::min<uint64_t>((uint64_t) D->n_cus * 8u, (n + LRT_BLOCK - 1) / LRT_BLOCK);
+        const size_t smem = (size_t) LRT_STACK * LRT_BLOCK * sizeof(int);
+        if (rp.ld_count) k_aov<false, true><<<g, LRT_BLOCK, smem, st>>>((ScenePtr) D->d_sc, lp, spec);
+        else k_aov<false, false><<<g, LRT_BLOCK, smem, st>>>((ScenePtr) D->d_sc, lp, spec);
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
+// The AOV pass renders like a (non-PRB) sampling integrator: its pass structure follows samples_per_pass and the 2^32 - 1 lane limit.
+static ResolvedOpts resolve_aov(const lrt_scene_desc &d, const lrt_render_opts *opts, lrt_scene_desc &da) {
+    da = d; da.integrator = lrt_integrator_desc{ LRT_INTEGRATOR_PATH, -1, 5, 0 };
+    return resolve(da, opts);
+}
+
+void device_render_aov(DeviceScene *D, const lrt_scene_desc &d, const lrt_aov_desc &aov, const lrt_render_opts *opts, float *aov_film_raw, float *image, lrt_render_stats &stats) {
+    HIP_CHECK(hipSetDevice(D->device));
+    lrt_scene_desc da; ResolvedOpts O = resolve_aov(d, opts, da);
+    if (O.tile_count > 1) throw std::runtime_error("lrt_render_aov: tile sharding is not supported");
+    const DFilm &F = D->sc.film;
+    const bool on_device = opts && opts->output_on_device;
+    const size_t np = (size_t) F.width * F.height;
+    const int C = aov.n_aov_channels + 1, T = aov.n_channels, IC = F.has_alpha ? 4 : 3, n_int = aov.n_integrators;
+    // the independent sampler runs on from pass to pass, and its state after pass p - 1 includes what the nested integrators drew
+    // (aov.cpp:348): one nested integrator -> that integrator's own pass states; none -> the AOV pass's; two or more -> no render here computes it
+    const bool carry = O.n_passes > 1 && d.sampler_type != LRT_SAMPLER_LD;
+    if (carry && n_int >= 2) throw std::runtime_error("lrt_render_aov: several passes of the independent sampler with two or more nested integrators are not supported");
+    if (carry && n_int == 1 && aov.integrators[0].type == LRT_INTEGRATOR_PRBVOLPATH)
+        throw std::runtime_error("lrt_render_aov: a nested prbvolpath renders in one pass; several AOV passes around it are not supported");
+    upload_aov_spec(D, d, aov);
+    hipStream_t st = D->stream;
+    float *film = (on_device && aov_film_raw) ? aov_film_raw : aov_buffer(D, D->aov_film, D->aov_film_floats, np * C);
+    HIP_CHECK(hipMemsetAsync(film, 0, np * C * 4, st));
+    float *img = nullptr;
+    if (image) img = on_device ? image : aov_buffer(D, D->aov_image, D->aov_image_floats, np * T);
+    const uint64_t n_lanes = np * O.spp;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t ev_next = 0;
+    auto aov_pass = [&](uint32_t pass, const unsigned long long *in, unsigned long long *out) {
+        ResolvedOpts Op = O; Op.pass = pass;
+        hipEvent_t a = get_event(D, ev_next++), b = get_event(D, ev_next++);
+        HIP_CHECK(hipEventRecord(a, st));
+        launch_aov(D, da, Op, 0, n_lanes, film, nullptr, in, out);
+        HIP_CHECK(hipEventRecord(b, st));
+        ev.emplace_back(a, b);
+    };
+    lrt_render_stats total{};
+    bool aov_done = false;
+    // 1. the nested integrators, each exactly as lrt_render renders it alone (aov.cpp:375-380)
+    for (int k = 0; k < n_int; ++k) {
+        const bool hook = carry && k == 0;
+        if (!image && !hook) continue;           // nothing of it is asked for
+        lrt_scene_desc dk = d; dk.integrator = aov.integrators[k];
+        lrt_render_opts ok{}; if (opts) ok = *opts; else { ok.integrator = -1; ok.max_depth = -2; ok.rr_depth = -1; ok.hide_emitters = -1; }
+        ok.output_on_device = 1; ok.tile_rank = 0; ok.tile_count = 1;
+        float *inner = image ? aov_buffer(D, D->aov_inner, D->aov_inner_floats, np * IC) : nullptr;
+        lrt_render_stats sk{};
+        std::function<void(const ResolvedOpts &)> after;
+        if (hook) after = [&](const ResolvedOpts &Oc) { aov_pass(Oc.pass, D->cur_pass_in, nullptr); };
+        render_passes(D, dk, &ok, nullptr, inner, sk, after);
+        if (hook) aov_done = true;
+        if (image) { k_aov_copy<<<(uint32_t) ((np + 255) / 256), 256, 0, st>>>(inner, IC, img, T, k * IC, (uint32_t) np); HIP_CHECK(hipGetLastError()); }
+        total.n_samples += sk.n_samples; total.n_iter += sk.n_iter; total.n_shadow += sk.n_shadow; total.n_launches += sk.n_launches;
+        total.n_records += sk.n_records; total.kernel_ms += sk.kernel_ms; total.total_ms += sk.total_ms;
+    }
+    // 2. the AOV pass (Base::render, aov.cpp:382-391)
+    if (!aov_done) {
+        if (carry && D->pass_state_lanes < n_lanes) {
+            HIP_CHECK(hipStreamSynchronize(st));
+            for (int k = 0; k < 2; ++k) { D->release(D->pass_state[k]); D->pass_state[k] = nullptr; HIP_CHECK(hipMalloc((void **) &D->pass_state[k], std::max<uint64_t>(n_lanes, 1) * 8)); D->track(D->pass_state[k]); }
+            D->pass_state_lanes = n_lanes;
+        }
+        for (uint32_t pass = 0; pass < O.n_passes; ++pass)
+            aov_pass(pass, carry ? D->pass_state[pass & 1] : nullptr, (carry && pass + 1 < O.n_passes) ? D->pass_state[(pass & 1) ^ 1] : nullptr);
+    }
+    // 3. merge (merge_channels, aov.cpp:523-545): the inner images are in place, the AOVs follow them
+    if (img) { k_aov_develop<<<(uint32_t) ((np + 255) / 256), 256, 0, st>>>(film, C, img, T, n_int * IC, (uint32_t) np); HIP_CHECK(hipGetLastError()); }
+    if (image && !on_device) HIP_CHECK(hipMemcpyAsync(image, img, np * T * 4, hipMemcpyDeviceToHost, st));
+    if (aov_film_raw && !on_device) HIP_CHECK(hipMemcpyAsync(aov_film_raw, film, np * C * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
+    double aov_ms = 0.0;
+    for (auto &e : ev) { float ms = 0.f; HIP_CHECK(hipEventElapsedTime(&ms, e.first, e.second)); aov_ms += ms; }
+    total.n_samples += n_lanes * O.n_passes; total.n_launches += ev.size(); total.kernel_ms += aov_ms; total.total_ms += aov_ms;
+    total.lds_resident = D->use_lds ? 1 : 0;
+    stats = total;
+}
+
+void device_render_aov_samples(DeviceScene *D, const lrt_scene_desc &d, const lrt_aov_desc &aov, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out, lrt_render_stats &stats) {
+    HIP_CHECK(hipSetDevice(D->device));
+    lrt_scene_desc da; ResolvedOpts O = resolve_aov(d, opts, da);
+    if (O.tile_count > 1) throw std::runtime_error("lrt_render_aov_samples: tile sharding is not supported");
+    const uint64_t n_lanes = (uint64_t) D->sc.film.width * D->sc.film.height * O.spp;
+    if (lane_begin + n > n_lanes) throw std::runtime_error("lrt_render_aov_samples: lane range exceeds the pass's " + std::to_string(n_lanes) + " lanes");
+    upload_aov_spec(D, d, aov);
+    const size_t floats = (size_t) n * aov.n_aov_channels;
+    if (!floats) { stats = lrt_render_stats{}; return; }
+    float *d_out = nullptr;
+    HIP_CHECK(hipMalloc((void **) &d_out, floats * 4));
+    try {
+        HIP_CHECK(hipMemsetAsync(d_out, 0, floats * 4, D->stream));
+        O.pass = 0;
+        launch_aov(D, da, O, lane_begin, n, nullptr, d_out, nullptr, nullptr);
+        HIP_CHECK(hipMemcpyAsync(out, d_out, floats * 4, hipMemcpyDeviceToHost, D->stream));
+        HIP_CHECK(hipStreamSynchronize(D->stream));
+        HIP_CHECK(hipGetLastError());
+    } catch (...) { (void) hipFree(d_out); throw; }
+    HIP_CHECK(hipFree(d_out));
+    stats = lrt_render_stats{}; stats.n_samples = n; stats.lds_resident = D->use_lds ? 1 : 0;
 }
 
 void device_trace(DeviceScene *D, const lrt_rays_soa *rays, const lrt_hits_soa *hits, uint32_t n, int any_hit) {

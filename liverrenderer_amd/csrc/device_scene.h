@@ -11,6 +11,9 @@ void device_scene_destroy(DeviceScene *d);
 void device_scene_update_params(DeviceScene *D, const lrt_scene_desc &d);
 void device_render(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, float *film_raw, float *image, lrt_render_stats &stats);
 void device_develop(DeviceScene *D, const float *film_raw, float *image, int on_device);
+// the aov integrator (kernels_aov.h): nested renders, then the first-hit AOV pass; merged image on the device
+void device_render_aov(DeviceScene *D, const lrt_scene_desc &d, const lrt_aov_desc &aov, const lrt_render_opts *opts, float *aov_film_raw, float *image, lrt_render_stats &stats);
+void device_render_aov_samples(DeviceScene *D, const lrt_scene_desc &d, const lrt_aov_desc &aov, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out, lrt_render_stats &stats);
 void device_render_samples(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out, lrt_render_stats &stats);
 void device_trace(DeviceScene *D, const lrt_rays_soa *rays, const lrt_hits_soa *hits, uint32_t n, int any_hit);
 // network stage of the learned subsurface model (kernels_vae.h): host arrays in, host arrays out

@@ -23,6 +23,10 @@ struct SceneStorage {
     std::vector<std::vector<float>> emdata;
     std::vector<std::vector<float>> meddata;   // heterogeneous media: grid values
     lrt_scene_desc desc{};
+    // `aov` integrator (loader.cpp): its configuration and the developed channel names, beside the ordinary description
+    bool has_aov = false;
+    lrt_aov_desc aov{};
+    std::vector<std::string> aov_channel_names;
     void fix_pointers();                 // re-point desc at the vectors above
     void copy_from(const lrt_scene_desc &d);
 };

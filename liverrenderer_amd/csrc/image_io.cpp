@@ -401,6 +401,48 @@ void write_exr(const std::string &path, int w, int h, int channels, const float 
     fclose(f);
 }
 
+void write_exr_channels(const std::string &path, int w, int h, const std::vector<std::string> &names, const float *data) {
+    const int channels = (int) names.size();
+    if (w <= 0 || h <= 0 || channels < 1) throw std::runtime_error("write_exr_channels: empty image");
+    bool long_names = false;
+    for (auto &n : names) {
+        if (n.empty() || n.size() > 255) throw std::runtime_error("write_exr_channels: channel names must have 1 to 255 characters");
+        long_names |= n.size() > 31;
+    }
+    std::vector<int> order(channels);                    // file channel k <- source channel order[k]
+    for (int c = 0; c < channels; ++c) order[c] = c;
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return names[a] < names[b]; });
+    for (int k = 1; k < channels; ++k) if (names[order[k]] == names[order[k - 1]]) throw std::runtime_error("write_exr_channels: duplicate channel name \"" + names[order[k]] + "\"");
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) throw std::runtime_error("cannot open \"" + path + "\" for writing");
+    auto put = [&](const void *p, size_t n) { fwrite(p, 1, n, f); };
+    auto attr = [&](const char *name, const char *type, const void *v, uint32_t n) { put(name, strlen(name) + 1); put(type, strlen(type) + 1); put(&n, 4); put(v, n); };
+    const uint8_t magic[8] = { 0x76, 0x2f, 0x31, 0x01, 2, (uint8_t) (long_names ? 0x04 : 0), 0, 0 }; put(magic, 8);   // version 2, bit 10: long names
+    std::vector<uint8_t> cl;
+    for (int k = 0; k < channels; ++k) {
+        const std::string &n = names[order[k]];
+        cl.insert(cl.end(), n.begin(), n.end()); cl.push_back(0);
+        int32_t v[4] = { 2, 0, 1, 1 }; const uint8_t *q = (const uint8_t *) v; cl.insert(cl.end(), q, q + 16);    // FLOAT, pLinear 0, sampling 1 x 1
+    }
+    cl.push_back(0);
+    attr("channels", "chlist", cl.data(), (uint32_t) cl.size());
+    uint8_t comp = 0; attr("compression", "compression", &comp, 1);
+    int32_t box[4] = { 0, 0, w - 1, h - 1 }; attr("dataWindow", "box2i", box, 16); attr("displayWindow", "box2i", box, 16);
+    uint8_t lo = 0; attr("lineOrder", "lineOrder", &lo, 1);
+    float one = 1.f, zero2[2] = { 0.f, 0.f }; attr("pixelAspectRatio", "float", &one, 4);
+    attr("screenWindowCenter", "v2f", zero2, 8); attr("screenWindowWidth", "float", &one, 4);
+    uint8_t z = 0; put(&z, 1);
+    size_t line = (size_t) w * channels * 4; uint64_t off = (uint64_t) ftell(f) + 8ull * h;
+    for (int y = 0; y < h; ++y) { put(&off, 8); off += 8 + line; }
+    std::vector<float> row((size_t) w * channels);
+    for (int y = 0; y < h; ++y) {
+        int32_t hdr[2] = { y, (int32_t) line }; put(hdr, 8);
+        for (int k = 0; k < channels; ++k) for (int x = 0; x < w; ++x) row[(size_t) k * w + x] = data[((size_t) y * w + x) * channels + order[k]];
+        put(row.data(), line);
+    }
+    if (fclose(f) != 0) throw std::runtime_error("write_exr_channels: could not write \"" + path + "\"");
+}
+
 // 8-bit PNG export of a linear float image, as LiverRenderer.py:383-385 does with
 // Bitmap.convert(RGBA, UInt8, srgb_gamma=True): colour channels through the sRGB OETF, alpha linear, clamp to [0,1],
 // round to nearest.  Filter type 0, one zlib stream, CRCs from zlib.

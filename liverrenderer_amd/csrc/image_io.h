@@ -21,6 +21,8 @@ Image read_png(const std::string &path);                  // throws std::runtime
 Image read_exr(const std::string &path);                  // channels in file (alphabetical) order
 Image read_image_rgb(const std::string &path);            // by extension; RGB(A)/Y -> channels as stored
 void  write_exr(const std::string &path, int w, int h, int channels, const float *data);  // RGB / RGBA float32, no compression
+// any number of named float32 channels, no compression; data in the order of `names`, written sorted by name (OpenEXR's channel order)
+void  write_exr_channels(const std::string &path, int w, int h, const std::vector<std::string> &names, const float *data);
 void  write_png(const std::string &path, int w, int h, int channels, const float *data);  // 8-bit, sRGB-encoded colour, linear alpha
 
 } // namespace lrt

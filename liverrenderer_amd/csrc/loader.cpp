@@ -2,7 +2,7 @@
 //
 // Replaces, for the plugins the liver scenes and mi.cornell_box() use, the
 // reference's src/core/parser.cpp + Properties + PluginManager instantiation.
-// Supported plugins: integrator {path, volpath, prbvolpath, biovolpath, biovolpath06}; sensor perspective;
+// Supported plugins: integrator {path, volpath, prbvolpath, biovolpath, biovolpath06, aov}; sensor perspective;
 // sampler {independent, ldsampler}; film hdrfilm; rfilter {box,
 // gaussian, tent}; bsdf {diffuse, dielectric, bumpmap, null}; texture {bitmap,
 // checkerboard}; medium {homogeneous, liver, parenchyma, glissonCapsule} (the
@@ -625,22 +625,103 @@ struct Loader {
         for (auto &c : o->children) if (c.second->tag == "medium") C.medium = make_medium(c.second);
     }
 
-    void make_integrator(const ObjP &o) {
-        lrt_integrator_desc &I = S.desc.integrator;
+    // one integrator plugin: its type and the properties a render reads (src/render/integrator.cpp:535-552)
+    lrt_integrator_desc parse_integrator(const ObjP &o, int *spass, bool *spectral_mis) {
+        lrt_integrator_desc I{};
         if (o->type == "path") I.type = LRT_INTEGRATOR_PATH;
         else if (o->type == "volpath") I.type = LRT_INTEGRATOR_VOLPATH;
         else if (o->type == "prbvolpath") I.type = LRT_INTEGRATOR_PRBVOLPATH;
         else if (o->type == "biovolpath") I.type = LRT_INTEGRATOR_BIOVOLPATH;
         else if (o->type == "biovolpath06") I.type = LRT_INTEGRATOR_BIOVOLPATH06;
         else if (o->type == "volpathmis") I.type = LRT_INTEGRATOR_VOLPATHMIS;
-        else fail("unsupported integrator \"" + o->type + "\" (supported: path, volpath, volpathmis, prbvolpath, biovolpath, biovolpath06)");
-        // src/render/integrator.cpp:535-552
+        else fail("unsupported integrator \"" + o->type + "\" (supported: path, volpath, volpathmis, prbvolpath, biovolpath, biovolpath06, aov)");
         I.max_depth = get_int(*o, "max_depth", -1); I.rr_depth = get_int(*o, "rr_depth", 5); I.hide_emitters = get_bool(*o, "hide_emitters", false);
         if (I.max_depth < 0 && I.max_depth != -1) fail("\"max_depth\" must be set to -1 (infinite) or a value >= 0");
         if (I.rr_depth <= 0) fail("\"rr_depth\" must be set to a value greater than zero!");
-        int spass = get_int(*o, "samples_per_pass", -1);                      // src/render/integrator.cpp:22-38 (SamplingIntegrator)
+        *spass = get_int(*o, "samples_per_pass", -1);                         // src/render/integrator.cpp:22-38 (SamplingIntegrator)
+        *spectral_mis = get_bool(*o, "use_spectral_mis", true);              // src/integrators/volpathmis.cpp:47
+        return I;
+    }
+
+    void make_integrator(const ObjP &o) {
+        if (o->type == "aov") { make_aov(o); return; }
+        int spass; bool spectral;
+        S.desc.integrator = parse_integrator(o, &spass, &spectral);
         S.desc.samples_per_pass = spass > 0 ? (uint32_t) spass : 0u;
-        S.desc.use_spectral_mis = get_bool(*o, "use_spectral_mis", true) ? 1u : 0u;     // src/integrators/volpathmis.cpp:47
+        S.desc.use_spectral_mis = spectral ? 1u : 0u;
+    }
+
+    // src/integrators/aov.cpp:109-197: nested integrators (children, file order) and the `aovs` list "name:type,...".
+    // The description's integrator becomes the first nested one (path defaults without one).
+    void make_aov(const ObjP &o) {
+        lrt_aov_desc &A = S.aov; A = lrt_aov_desc{};
+        std::vector<std::string> names;                  // m_aov_names: hdrfilm.cpp:269-272 rejects a duplicate
+        auto copy_name = [&](char *dst, const std::string &n, const char *what) {
+            if (n.size() >= LRT_AOV_NAME_LEN) fail(std::string("aov: ") + what + " name \"" + n + "\" is longer than " + std::to_string(LRT_AOV_NAME_LEN - 1) + " characters");
+            memcpy(dst, n.c_str(), n.size() + 1);
+        };
+        const int spass_aov = get_int(*o, "samples_per_pass", -1);
+        int mis_seen = -1;
+        for (auto &c : o->children) {
+            if (c.second->tag != "integrator") fail("aov: Child objects must be of type 'SamplingIntegrator'!");
+            if (c.second->type == "aov") fail("aov: an aov integrator nested in another one is not supported");
+            if (A.n_integrators == LRT_AOV_MAX_INTEGRATORS) fail("aov: more than " + std::to_string(LRT_AOV_MAX_INTEGRATORS) + " nested integrators");
+            int spass; bool spectral;
+            lrt_integrator_desc I = parse_integrator(c.second, &spass, &spectral);
+            if (spass > 0 && spass != spass_aov)
+                fail("aov: nested integrator \"" + c.first + "\" sets samples_per_pass = " + std::to_string(spass) + ", the aov integrator " +
+                     (spass_aov > 0 ? std::to_string(spass_aov) : std::string("none")) + " (a single scene description cannot express both)");
+            if (I.type == LRT_INTEGRATOR_VOLPATHMIS) {
+                if (mis_seen >= 0 && mis_seen != (int) spectral) fail("aov: two nested volpathmis integrators with different use_spectral_mis");
+                mis_seen = (int) spectral;
+            }
+            A.integrators[A.n_integrators] = I;
+            copy_name(A.integrator_names[A.n_integrators], c.first, "integrator");
+            for (const char *suf : { ".R", ".G", ".B", ".A" }) names.push_back(c.first + suf);
+            ++A.n_integrators;
+        }
+        // string::tokenize (src/core/string.cpp): delimiters ", " then ":", empty tokens dropped
+        auto tokenize = [](const std::string &str, const char *delim) {
+            std::vector<std::string> r; std::string cur;
+            for (char ch : str) { if (strchr(delim, ch)) { if (!cur.empty()) r.push_back(cur); cur.clear(); } else cur += ch; }
+            if (!cur.empty()) r.push_back(cur);
+            return r;
+        };
+        struct T { const char *name; int type; const char *suffixes; };
+        static const T table[] = { { "albedo", LRT_AOV_ALBEDO, "RGB" }, { "depth", LRT_AOV_DEPTH, "T" }, { "position", LRT_AOV_POSITION, "XYZ" },
+            { "uv", LRT_AOV_UV, "UV" }, { "geo_normal", LRT_AOV_GEO_NORMAL, "XYZ" }, { "sh_normal", LRT_AOV_SH_NORMAL, "XYZ" },
+            { "dp_du", LRT_AOV_DP_DU, "XYZ" }, { "dp_dv", LRT_AOV_DP_DV, "XYZ" }, { "prim_index", LRT_AOV_PRIM_INDEX, "I" }, { "shape_index", LRT_AOV_SHAPE_INDEX, "I" } };
+        std::vector<std::string> aov_ch;
+        for (const std::string &tok : tokenize(has(*o, "aovs") ? get_string(*o, "aovs", "") : std::string(), ", ")) {
+            std::vector<std::string> item = tokenize(tok, ":");
+            if (item.size() != 2) { fprintf(stderr, "[lrt] aov: Invalid AOV specification \"%s\": require <name>:<type> pair (skipped)\n", tok.c_str()); continue; }
+            if (item[1] == "duv_dx" || item[1] == "duv_dy")
+                fail("aov: unsupported AOV type \"" + item[1] + "\" (it needs ray differentials, which the primary-ray state does not carry)");
+            const T *t = nullptr;
+            for (const T &e : table) if (item[1] == e.name) t = &e;
+            if (!t) fail("Invalid AOV type \"" + item[1] + "\"!");
+            if (A.n_aovs == LRT_AOV_MAX_AOVS) fail("aov: more than " + std::to_string(LRT_AOV_MAX_AOVS) + " AOVs");
+            A.aov_types[A.n_aovs] = t->type;
+            copy_name(A.aov_names[A.n_aovs], item[0], "AOV");
+            ++A.n_aovs;
+            for (const char *q = t->suffixes; *q; ++q) { std::string n = item[0] + "." + *q; names.push_back(n); aov_ch.push_back(n); }
+        }
+        std::vector<std::string> sorted = names; std::sort(sorted.begin(), sorted.end());
+        for (size_t i = 1; i < sorted.size(); ++i)
+            if (sorted[i] == sorted[i - 1]) fail("aov: duplicate channel name \"" + sorted[i] + "\" (Film::prepare)");
+        // developed channels (merge_channels, aov.cpp:523-545): each inner image as it is, R,G,B[,A], then the AOV channels
+        S.aov_channel_names.clear();
+        for (int k = 0; k < A.n_integrators; ++k)
+            for (const char *suf : { ".R", ".G", ".B", ".A" }) {
+                if (suf[1] == 'A' && !S.desc.film.has_alpha) continue;
+                S.aov_channel_names.push_back(std::string(A.integrator_names[k]) + suf);
+            }
+        for (auto &n : aov_ch) S.aov_channel_names.push_back(n);
+        A.n_aov_channels = (int32_t) aov_ch.size(); A.n_channels = (int32_t) S.aov_channel_names.size();
+        S.has_aov = true;
+        S.desc.integrator = A.n_integrators ? A.integrators[0] : lrt_integrator_desc{ LRT_INTEGRATOR_PATH, -1, 5, 0 };
+        S.desc.samples_per_pass = spass_aov > 0 ? (uint32_t) spass_aov : 0u;
+        S.desc.use_spectral_mis = mis_seen >= 0 ? (uint32_t) mis_seen : 1u;
     }
 
     void run(const std::string &text) {
@@ -659,7 +740,7 @@ struct Loader {
             objs.push_back(o);
         }
         for (auto &o : objs) {
-            if (o->tag == "integrator") make_integrator(o);
+            if (o->tag == "integrator") { if (o->type != "aov") make_integrator(o); }   // aov: after the sensor (its channel list depends on the film)
             else if (o->tag == "sensor") { if (have_sensor) fail("only one sensor is supported"); make_sensor(o); have_sensor = true; }
             else if (o->tag == "shape") make_shape(o);
             else if (o->tag == "emitter") make_emitter(o);
@@ -669,6 +750,7 @@ struct Loader {
             else fail("unsupported top-level element <" + o->tag + ">");
         }
         if (!have_sensor) fail("the scene has no sensor");
+        for (auto &o : objs) if (o->tag == "integrator" && o->type == "aov") make_integrator(o);
         S.fix_pointers();
     }
 };
