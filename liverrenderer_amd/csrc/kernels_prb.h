@@ -170,18 +170,20 @@ DEV bool prb_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const TR &
     const int gm = rp.grad_medium;
     if (ADJOINT && in_medium_segment && (gm < 0 || medium == gm)) {     // prbvolpath.py:199-204
         const DMedium M = tab(sc.media, medium);
+        // a channel with sigma_t or albedo 0 has w = 0 at a real scatter and nothing left to collect (Lo = 0): its 1/sigma_t and 1/albedo
+        // terms are dropped instead of forming 0 * (0/0) (the reference differentiates the product and never divides)
         auto term = [&](float w, float l, float dl, float st, float al, float sn, float &gs, float &ga) {
             float Lo = l / fmax_(1e-8f, w);
             if (het) {                                // only the collision coefficient depends on `scale` (header comment)
                 const float dlog = act_medium_scatter ? 1.f / M.scale : (act_null_scatter ? het_null_dlog_dscale(M, mei.sigma_t.x, sn) : 0.f);
                 gs += dl * Lo * (w * dlog);
-                if (act_medium_scatter) ga += dl * Lo * (w / al);
+                if (act_medium_scatter && al > 0.f) ga += dl * Lo * (w / al);
                 return;
             }
-            float dws = w * (-seg_t) + (act_medium_scatter ? w / st : 0.f);
+            float dws = w * (-seg_t) + (act_medium_scatter && st > 0.f ? w / st : 0.f);
             if (!(seg_t < kInf)) dws = 0.f;
             gs += dl * Lo * dws * M.scale;
-            if (act_medium_scatter) ga += dl * Lo * (w / al);
+            if (act_medium_scatter && al > 0.f) ga += dl * Lo * (w / al);
         };
 #ifdef LRT_EXPERIMENT
         if (rp.pad1 && s.lane == rp.pad1 - 1u) printf("  [dev] medium term: depth %u seg_t %.9g w %.9g %.9g %.9g L %.9g %.9g %.9g dl %.9g scatter %d\n", depth, seg_t, weight.x, weight.y, weight.z, L.x, L.y, L.z, delta_L.x, (int) act_medium_scatter);

@@ -1080,15 +1080,17 @@ static void prb_sample(Ctx &C, Ray ray, bool adjoint, V3 delta_L, V3 L_in, V3 *L
                     /* weight_k = exp(-t majorant) / pdf [* sigma_s_k / scatter_prob | * sigma_n_k / (1 - scatter_prob)]: only the bracket depends on `scale` */
                     float dlog = act_medium_scatter ? 1.f / M.scale : (act_null_scatter ? het_null_dlog_dscale(M, mei.sigma_t.x, sn[k]) : 0.f);
                     G->sigma_t[k] += (double) (dl[k] * Lo * (w[k] * dlog));
-                    if (act_medium_scatter) G->albedo[k] += (double) (dl[k] * Lo * (w[k] / M.albedo[k]));
+                    if (act_medium_scatter && M.albedo[k] > 0.f) G->albedo[k] += (double) (dl[k] * Lo * (w[k] / M.albedo[k]));
                     continue;
                 }
-                /* weight_k = exp(-t sigma_k) / pdf [* sigma_k a_k]:  d/dsigma_k = w (-t [+ 1/sigma_k]),  d/da_k = w / a_k */
+                /* weight_k = exp(-t sigma_k) / pdf [* sigma_k a_k]:  d/dsigma_k = w (-t [+ 1/sigma_k]),  d/da_k = w / a_k.
+                   sigma_k = 0 or a_k = 0 makes w = 0 at a real scatter with nothing left to collect (Lo = 0): the 1/sigma_k and 1/a_k
+                   terms are dropped there instead of forming 0 * (0/0) (the reference differentiates the product, prbvolpath.py:199-204) */
                 float st = M.sigma_t[k] * M.scale;
-                float dws = w[k] * (-seg_t) + (act_medium_scatter ? w[k] / st : 0.f);
+                float dws = w[k] * (-seg_t) + (act_medium_scatter && st > 0.f ? w[k] / st : 0.f);
                 if (!(seg_t < kInf)) dws = 0.f;                                     /* exp(-inf) = 0: no dependence */
                 G->sigma_t[k] += (double) (dl[k] * Lo * dws * M.scale);
-                if (act_medium_scatter) G->albedo[k] += (double) (dl[k] * Lo * (w[k] / M.albedo[k]));
+                if (act_medium_scatter && M.albedo[k] > 0.f) G->albedo[k] += (double) (dl[k] * Lo * (w[k] / M.albedo[k]));
                 if (g_prb_debug) fprintf(stderr, "  [orc] trip %u k %d seg_t %.9g w %.9g L %.9g dl %.9g scatter %d term %.9g\n", depth, k, seg_t, w[k], l[k], dl[k], (int) act_medium_scatter, dl[k] * Lo * dws * M.scale);
             }
         }
