@@ -59,8 +59,12 @@ enum { LRT_MEDIUM_HOMOGENEOUS = 0, LRT_MEDIUM_LIVER = 1, LRT_MEDIUM_PARENCHYMA =
 enum { LRT_BSDF_DIFFUSE = 0, LRT_BSDF_DIELECTRIC = 1, LRT_BSDF_BUMPMAP = 2, LRT_BSDF_NULL = 3 };
 enum { LRT_TEX_RGB = 0, LRT_TEX_CHECKERBOARD = 1, LRT_TEX_BITMAP = 2 };
 enum { LRT_PHASE_ISOTROPIC = 0, LRT_PHASE_HG = 1 };
-enum { LRT_EMITTER_AREA = 0, LRT_EMITTER_ENVMAP = 1, LRT_EMITTER_CONSTANT = 2 };
-enum { LRT_SHAPE_MESH = 0, LRT_SHAPE_RECTANGLE = 1 };
+enum { LRT_EMITTER_AREA = 0, LRT_EMITTER_ENVMAP = 1, LRT_EMITTER_CONSTANT = 2,
+       LRT_EMITTER_POINT = 3          /* [v106] src/emitters/point.cpp: `intensity` in radiance[3], position = to_world * 0 */ };
+enum { LRT_SHAPE_MESH = 0, LRT_SHAPE_RECTANGLE = 1,
+       LRT_SHAPE_SPHERE = 2           /* [v106] src/shapes/sphere.cpp: n_faces = 0, analytic intersection (see lrt_shape_desc) */ };
+/* The CPU oracle under oracle/ knows neither LRT_SHAPE_SPHERE nor LRT_EMITTER_POINT: it must never be handed a scene
+   that contains them (it renders triangles and the three emitter kinds above only). */
 enum { LRT_RFILTER_BOX = 0, LRT_RFILTER_GAUSSIAN = 1, LRT_RFILTER_TENT = 2 };
 
 /* ------------------------------------------------- scene description (POD)
@@ -82,6 +86,11 @@ typedef struct {
     int32_t  flip_normals;
     float    to_world[16];    /* row-major; used by LRT_SHAPE_RECTANGLE sampling   */
 } lrt_shape_desc;
+/* LRT_SHAPE_SPHERE [v106]: first_face = n_faces = 0, has_normals = has_texcoords = 0; to_world holds
+   to_world * translate(center) * scale(radius) (sphere.cpp:128-136), so radius = |to_world * (1,0,0)| and
+   center = to_world * (0,0,0).  Shear and non-uniform scale only warn, as in the reference.  A ray hit on the k-th
+   sphere of shapes[] (counting spheres only) reports prim = n_faces + k, u = v = 0 (lrt_trace included).  Spheres
+   carry no area emitter (LRT_ERR_UNSUPPORTED), and prbvolpath rejects scenes with spheres or point emitters.     */
 
 typedef struct {
     int32_t type;             /* LRT_TEX_*                                         */
@@ -132,10 +141,10 @@ typedef struct {
 
 typedef struct {
     int32_t type;             /* LRT_EMITTER_*                                     */
-    float   radiance[3];      /* area / constant                                   */
+    float   radiance[3];      /* area / constant; point [v106]: intensity          */
     int32_t shape;            /* area: owning shape                                */
     float   scale;            /* envmap                                            */
-    float   to_world[16];     /* envmap, row-major                                 */
+    float   to_world[16];     /* envmap, row-major; point [v106]: position in column 3 */
     int32_t width, height;    /* envmap: ORIGINAL bitmap resolution (w, h)         */
     const float *data;        /* envmap: h * w * 3 linear RGB floats               */
 } lrt_emitter_desc;

@@ -28,7 +28,7 @@ static lrt_status fail(lrt_status st, const std::string &msg) { g_error = msg; r
 extern "C" {
 
 const char *lrt_last_error(void) { return g_error.c_str(); }
-int lrt_version(void) { return 105; }    // 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
+int lrt_version(void) { return 106; }    // 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
 
 static std::vector<std::pair<std::string, std::string>> parse_defines(const char *const *defines, int n) {
     std::vector<std::pair<std::string, std::string>> r;
@@ -99,17 +99,19 @@ static void validate_desc(const lrt_scene_desc &d) {
         if (s.emitter < -1 || s.emitter >= (int) d.n_emitters || s.interior_medium < -1 || s.interior_medium >= (int) d.n_media || s.exterior_medium < -1 || s.exterior_medium >= (int) d.n_media)
             bad("shape references an invalid emitter/medium");
         if ((uint64_t) s.first_face + s.n_faces > d.n_faces) bad("shape face range exceeds the face array");
+        if (s.kind < LRT_SHAPE_MESH || s.kind > LRT_SHAPE_SPHERE) bad("invalid shape kind");
+        if (s.kind == LRT_SHAPE_SPHERE && s.n_faces != 0) bad("a sphere shape has no faces");
         if (s.emitter >= 0 && (d.emitters[s.emitter].type != LRT_EMITTER_AREA || d.emitters[s.emitter].shape != (int) i)) bad("shape and area emitter do not reference each other");
     }
     uint32_t n_env = 0;
     for (uint32_t i = 0; i < d.n_emitters; ++i) {
         const lrt_emitter_desc &E = d.emitters[i];
-        if (E.type < LRT_EMITTER_AREA || E.type > LRT_EMITTER_CONSTANT) bad("invalid emitter type");
+        if (E.type < LRT_EMITTER_AREA || E.type > LRT_EMITTER_POINT) bad("invalid emitter type");
         if (E.type == LRT_EMITTER_AREA) {
             if (E.shape < 0 || (uint32_t) E.shape >= d.n_shapes) bad("area emitter references an invalid shape");
             const lrt_shape_desc &s = d.shapes[E.shape];
             if (s.kind != LRT_SHAPE_RECTANGLE || s.n_faces < 1) bad("area emitters are supported on rectangle shapes only");
-        } else ++n_env;
+        } else if (E.type != LRT_EMITTER_POINT) ++n_env;
         if (E.type == LRT_EMITTER_ENVMAP && (!E.data || E.width < 2 || E.height < 3)) bad("environment map without data or smaller than 2x3 pixels");
     }
     if (n_env > 1) bad("Only one environment emitter can be specified per scene.");

@@ -64,6 +64,7 @@ struct DeviceScene {
     std::vector<DMedium> h_media; DMedium *d_media = nullptr;
     std::vector<DBioMedium> h_bio; DBioMedium *d_bio = nullptr;
     std::vector<DHetMedium> h_het; DHetMedium *d_het = nullptr; std::vector<float *> het_data; bool has_het = false, has_non_bio = false, need_mis = false, mis_alloc = false;
+    bool ext = false;                      // spheres or point emitters: the EXT kernel instances (ExtTracer, point-emitter sampling), wide records
     bool has_area_emitter = false;         // decides the record layout: only an area emitter's pdf reads the last scatter position (kernels.h, store_state)
     bool prb_null = false;                 // prbvolpath.py:84-91 `handle_null_scattering`: a heterogeneous medium is attached to a shape
     DLdsInfo lds{}; bool use_lds = false; int n_cus = 256; int bvh_leaf = 4;
@@ -270,6 +271,32 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
     // leaves = fewer nodes: more triangle tests per leaf, but every fetch of the traversal stays in LDS; Liver-MultiMesh's two meshes
     // run 44 % faster with 8-triangle leaves in LDS than with 4-triangle leaves in global memory); 4 when nothing fits.
     // LRT_BVH_LEAF=n forces a size.
+    // ---- sphere shapes (src/shapes/sphere.cpp:146-165): centre, radius and the inverse transform, outside the triangle BVH
+    std::vector<DSphere> spheres;
+    for (uint32_t i = 0; i < d.n_shapes; ++i) {
+        const lrt_shape_desc &s = d.shapes[i];
+        if (s.kind != LRT_SHAPE_SPHERE) continue;
+        DSphere o; memset(&o, 0, sizeof(o));
+        const float *m = s.to_world;
+        for (int a = 0; a < 3; ++a) o.center[a] = m[4 * a + 3];                       // to_world * (0, 0, 0)
+        o.radius = sqrtf(fmaf(m[8], m[8], fmaf(m[4], m[4], m[0] * m[0])));           // |to_world * (1, 0, 0)|
+        for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) o.to_world[3 * a + b] = m[4 * a + b];
+        double md[16]; for (int k = 0; k < 16; ++k) md[k] = m[k];
+        const double c00 = md[5] * md[10] - md[6] * md[9], c01 = md[6] * md[8] - md[4] * md[10], c02 = md[4] * md[9] - md[5] * md[8];
+        const double id = 1.0 / (md[0] * c00 + md[1] * c01 + md[2] * c02);
+        double inv[12] = { c00 * id, (md[2] * md[9] - md[1] * md[10]) * id, (md[1] * md[6] - md[2] * md[5]) * id, 0,
+                           c01 * id, (md[0] * md[10] - md[2] * md[8]) * id, (md[2] * md[4] - md[0] * md[6]) * id, 0,
+                           c02 * id, (md[1] * md[8] - md[0] * md[9]) * id, (md[0] * md[5] - md[1] * md[4]) * id, 0 };
+        for (int a = 0; a < 3; ++a) inv[4 * a + 3] = -(inv[4 * a] * md[3] + inv[4 * a + 1] * md[7] + inv[4 * a + 2] * md[11]);
+        for (int k = 0; k < 12; ++k) o.to_object[k] = (float) inv[k];
+        o.shape = i; o.flip_normals = s.flip_normals;
+        if (!(o.radius > 0.f) || !std::isfinite(o.radius)) throw std::runtime_error("sphere with a zero or invalid radius");
+        spheres.push_back(o);
+    }
+    sc.n_spheres = (uint32_t) spheres.size();
+    sc.spheres = spheres.empty() ? nullptr : D->track(dev_upload(spheres.data(), spheres.size(), st));
+    for (uint32_t i = 0; i < d.n_emitters; ++i) if (d.emitters[i].type == LRT_EMITTER_POINT) D->ext = true;
+    if (!spheres.empty()) D->ext = true;
     HostBVH bvh;
     {
         const int forced = getenv("LRT_BVH_LEAF") ? std::max(1, atoi(getenv("LRT_BVH_LEAF"))) : 0;
@@ -346,6 +373,14 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
             LRT_SMEM((k_render_prb<false, 1024, true, false, true>)); LRT_SMEM((k_render_prb<true, 1024, true, false, true>));
             LRT_SMEM((k_render_prb<false, 1024, true, true, true>)); LRT_SMEM((k_render_prb<true, 1024, true, true, true>));
             LRT_SMEM((k_trace_lds<true>)); LRT_SMEM((k_trace_lds<false>)); LRT_SMEM((k_aov<true, false>)); LRT_SMEM((k_aov<true, true>));
+            if (D->ext) {                              // spheres / point emitters: the EXT instances (kernels.h)
+#define LRT_SMEM_EXT(I, BS) LRT_SMEM((k_render<I, BS, true, false, false, true>)); LRT_SMEM((k_render<I, BS, true, true, false, true>))
+                LRT_SMEM_EXT(LRT_INTEGRATOR_PATH, 1024); LRT_SMEM_EXT(LRT_INTEGRATOR_VOLPATH, 1024); LRT_SMEM_EXT(LRT_INTEGRATOR_BIOVOLPATH, 1024);
+                LRT_SMEM_EXT(LRT_INTEGRATOR_BIOVOLPATH06, 1024); LRT_SMEM_EXT(LRT_INTEGRATOR_VOLPATH_HET, LRT_WIDE_BLOCK);
+                LRT_SMEM_EXT(LRT_INTEGRATOR_VOLPATHMIS, LRT_WIDE_BLOCK); LRT_SMEM_EXT(LRT_INTEGRATOR_VOLPATHMIS_PLAIN, LRT_WIDE_BLOCK);
+#undef LRT_SMEM_EXT
+                LRT_SMEM((k_trace_lds<true, true>)); LRT_SMEM((k_trace_lds<false, true>)); LRT_SMEM((k_aov<true, false, true>)); LRT_SMEM((k_aov<true, true, true>));
+            }
 #endif
             #undef LRT_SMEM
             D->use_lds = true;
@@ -354,9 +389,12 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
     // ---- conservative distance field (scenes with participating media: short free-flight segments deep inside a
     // volume are proven surface-free with one lookup instead of a BVH traversal)
     sc.grid = DDistGrid{};
-    if (d.n_media > 0 && d.n_faces > 0 && d.n_faces <= (1u << 17) && !getenv("LRT_NO_DIST_GRID")) {
+    // Spheres are surfaces too: their exact distance | |p - c| - r | joins the field's minimum and their bounds the grid's
+    // (k_build_dist_grid), or every medium trip inside a sphere would prove its way through the sphere's surface.
+    if (d.n_media > 0 && (d.n_faces > 0 || !spheres.empty()) && d.n_faces <= (1u << 17) && !getenv("LRT_NO_DIST_GRID")) {
         float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
         for (uint32_t f = 0; f < 3 * d.n_faces; ++f) for (int a = 0; a < 3; ++a) { float v = d.positions[3 * (size_t) d.faces[f] + a]; lo[a] = std::min(lo[a], v); hi[a] = std::max(hi[a], v); }
+        for (const DSphere &o : spheres) for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], o.center[a] - o.radius); hi[a] = std::max(hi[a], o.center[a] + o.radius); }
         const float ext = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
         const int res = getenv("LRT_DIST_GRID_RES") ? std::max(8, std::min(256, atoi(getenv("LRT_DIST_GRID_RES")))) : (d.n_faces <= (1u << 14) ? 192 : 64);
         if (ext > 0.f && std::isfinite(ext)) {
@@ -368,7 +406,8 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
             float diag = std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
             float amax = 0.f; for (int a = 0; a < 3; ++a) amax = std::max(amax, std::max(std::fabs(lo[a]), std::fabs(hi[a])));
             const float abs_margin = 1e-4f * diag + 1e-5f * amax;          // >> f32 rounding of positions and of the field itself
-            k_build_dist_grid<<<(uint32_t) ((n_cells + LRT_BLOCK - 1) / LRT_BLOCK), LRT_BLOCK, 0, st>>>(sc.tris, (uint32_t) (bvh.tris.size() / 12), g, buf, abs_margin);
+            k_build_dist_grid<<<(uint32_t) ((n_cells + LRT_BLOCK - 1) / LRT_BLOCK), LRT_BLOCK, 0, st>>>(sc.tris, d.n_faces ? (uint32_t) (bvh.tris.size() / 12) : 0u, g, buf, abs_margin,
+                                                                                                 sc.spheres, sc.n_spheres);
             HIP_CHECK(hipGetLastError());
             g.d = buf; g.enabled = 1; sc.grid = g;
         }
@@ -426,8 +465,9 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
     {
         float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
         for (uint32_t i = 0; i < d.n_vertices; ++i) for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], d.positions[3 * i + a]); hi[a] = fmaxf(hi[a], d.positions[3 * i + a]); }
+        for (const DSphere &o : spheres) for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], o.center[a] - o.radius); hi[a] = fmaxf(hi[a], o.center[a] + o.radius); }   // Sphere::bbox
         const float ray_eps = 5.9604644775390625e-8f * 1500.f;
-        if (d.n_vertices) {
+        if (d.n_vertices || !spheres.empty()) {
             float c[3], dd[3]; for (int a = 0; a < 3; ++a) { c[a] = (hi[a] + lo[a]) * 0.5f; dd[a] = c[a] - hi[a]; E.bsphere_c[a] = c[a]; }
             float r = sqrtf(fmaf(dd[2], dd[2], fmaf(dd[1], dd[1], dd[0] * dd[0])));
             E.bsphere_r = fmaxf(ray_eps, r * (1.f + ray_eps));
@@ -458,6 +498,7 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
         if (S.type == LRT_EMITTER_AREA) {
             D->has_area_emitter = true;
             const lrt_shape_desc &sd = d.shapes[S.shape];
+            if (sd.kind == LRT_SHAPE_SPHERE) throw std::runtime_error("unsupported: an area emitter on a sphere (area emitters are supported on rectangle shapes only)");
             if (sd.kind != LRT_SHAPE_RECTANGLE) throw std::runtime_error("area emitters are supported on rectangle shapes only");
             memcpy(o.to_world, sd.to_world, sizeof(float) * 12);
             auto xv = [&](float x, float y, float z, float *r) { const float *m = sd.to_world; for (int a = 0; a < 3; ++a) r[a] = fmaf(m[4 * a + 2], z, fmaf(m[4 * a + 1], y, m[4 * a] * x)); };
@@ -466,6 +507,8 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
             o.inv_area = 1.f / sqrtf(fmaf(cz, cz, fmaf(cy, cy, cx * cx)));
             uint32_t v0 = d.faces[3 * sd.first_face];
             for (int a = 0; a < 3; ++a) o.n[a] = sd.flip_normals ? -d.normals[3 * v0 + a] : d.normals[3 * v0 + a];
+        } else if (S.type == LRT_EMITTER_POINT) {             // src/emitters/point.cpp: position and intensity (radiance[])
+            memcpy(o.to_world, S.to_world, sizeof(float) * 12);
         } else {
             E.type = S.type; E.emitter = (int) i; E.scale = S.scale; for (int k = 0; k < 3; ++k) E.radiance[k] = S.radiance[k];
             if (S.type == LRT_EMITTER_ENVMAP) {             // src/emitters/envmap.cpp:139-236
@@ -729,6 +772,8 @@ static void launch_prb(DeviceScene *D, const DRenderParams &rp, const PoolGeomet
 static void check_integrator_media(DeviceScene *D, int integrator) {
     if ((integrator == LRT_INTEGRATOR_BIOVOLPATH || integrator == LRT_INTEGRATOR_BIOVOLPATH06) && D->has_non_bio)
         throw std::runtime_error("NotImplementedError: sample_interaction (the bio integrators need liver / parenchyma / glissonCapsule media)");
+    if (integrator == LRT_INTEGRATOR_PRBVOLPATH && D->ext)
+        throw std::runtime_error("unsupported: prbvolpath on a scene with sphere shapes or point emitters (its adjoint is built for triangles and area / infinite emitters)");
     if (integrator == LRT_INTEGRATOR_VOLPATHMIS) D->need_mis = true;          // its wider path record is allocated on first use
 }
 
@@ -761,17 +806,20 @@ static void run_wavefront(DeviceScene *D, const lrt_scene_desc &d, const Resolve
         a.lane_begin = lane_begin; a.n = n_lanes; a.film = film; a.sample_out = sample_out; a.sample_base = lane_begin;
         // Compact records (kernels.h, store_state): only an area emitter's pdf reads the last scatter position, so a scene without one does not queue it.
         // Instances exist for the 1024-thread LDS kernels of path / volpath (homogeneous media) / biovolpath / biovolpath06.  LRT_WIDE_RECORDS: developer switch.
-        const bool compact = D->use_lds && !D->has_area_emitter && !getenv("LRT_WIDE_RECORDS") && O.integrator != LRT_INTEGRATOR_VOLPATHMIS && !(O.integrator == LRT_INTEGRATOR_VOLPATH && D->has_het);
+        const bool compact = D->use_lds && !D->has_area_emitter && !D->ext && !getenv("LRT_WIDE_RECORDS") && O.integrator != LRT_INTEGRATOR_VOLPATHMIS && !(O.integrator == LRT_INTEGRATOR_VOLPATH && D->has_het);
         a.rp.compact = compact ? 1u : 0u;
         const LaunchPtr lp = push_launch(D, a);
 #ifdef LRT_DEV_VOLPATH_ONLY
+        if (D->ext) throw std::runtime_error("developer build: no EXT instances (spheres / point emitters)");
         if (!(D->use_lds && (O.integrator == LRT_DEV_INTEGRATOR || (LRT_DEV_INTEGRATOR == LRT_INTEGRATOR_VOLPATH_HET && D->has_het)) && (rp.ld_count != 0) == LRT_DEV_LD)) throw std::runtime_error("developer build: one integrator / sampler / LDS BVH only");
         if (compact) k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD, true><<<g.n_wg, LRT_DEV_BLOCK, g.smem, st>>>((ScenePtr) D->d_sc, lp);
         else k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD><<<g.n_wg, LRT_DEV_BLOCK, g.smem, st>>>((ScenePtr) D->d_sc, lp);
         #define LRT_LAUNCH_I(BS, LDSB)
         #define LRT_LAUNCH(I, BS, LDSB)
 #else
-        #define LRT_LAUNCH(I, BS, LDSB) do { if (rp.ld_count) k_render<I, BS, LDSB, true><<<g.n_wg, BS, g.smem, st>>>((ScenePtr) D->d_sc, lp); \
+        #define LRT_LAUNCH(I, BS, LDSB) do { if (D->ext) { if (rp.ld_count) k_render<I, BS, LDSB, true, false, true><<<g.n_wg, BS, g.smem, st>>>((ScenePtr) D->d_sc, lp); \
+                                                               else k_render<I, BS, LDSB, false, false, true><<<g.n_wg, BS, g.smem, st>>>((ScenePtr) D->d_sc, lp); } \
+                                             else if (rp.ld_count) k_render<I, BS, LDSB, true><<<g.n_wg, BS, g.smem, st>>>((ScenePtr) D->d_sc, lp); \
                                              else k_render<I, BS, LDSB, false><<<g.n_wg, BS, g.smem, st>>>((ScenePtr) D->d_sc, lp); } while (0)
         #define LRT_LAUNCH_COMPACT(I) do { if (rp.ld_count) k_render<I, 1024, true, true, true><<<g.n_wg, 1024, g.smem, st>>>((ScenePtr) D->d_sc, lp); \
                                            else k_render<I, 1024, true, false, true><<<g.n_wg, 1024, g.smem, st>>>((ScenePtr) D->d_sc, lp); } while (0)
@@ -947,12 +995,16 @@ static void launch_aov(DeviceScene *D, const lrt_scene_desc &d, const ResolvedOp
     const AovSpecPtr spec = (AovSpecPtr) D->d_aov_spec;
     if (D->use_lds) {
         const uint32_t g = (uint32_t) std::min<uint64_t>((uint64_t) D->n_cus, (n + 1023) / 1024);       // one workgroup per CU: the LDS image is copied once
-        if (rp.ld_count) k_aov<true, true><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, lp, spec);
+        if (D->ext) { if (rp.ld_count) k_aov<true, true, true><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, lp, spec);
+                      else k_aov<true, false, true><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, lp, spec); }
+        else if (rp.ld_count) k_aov<true, true><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, lp, spec);
         else k_aov<true, false><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, lp, spec);
     } else {
         const uint32_t g = (uint32_t) std::min<uint64_t>((uint64_t) D->n_cus * 8u, (n + LRT_BLOCK - 1) / LRT_BLOCK);
         const size_t smem = (size_t) LRT_STACK * LRT_BLOCK * sizeof(int);
-        if (rp.ld_count) k_aov<false, true><<<g, LRT_BLOCK, smem, st>>>((ScenePtr) D->d_sc, lp, spec);
+        if (D->ext) { if (rp.ld_count) k_aov<false, true, true><<<g, LRT_BLOCK, smem, st>>>((ScenePtr) D->d_sc, lp, spec);
+                      else k_aov<false, false, true><<<g, LRT_BLOCK, smem, st>>>((ScenePtr) D->d_sc, lp, spec); }
+        else if (rp.ld_count) k_aov<false, true><<<g, LRT_BLOCK, smem, st>>>((ScenePtr) D->d_sc, lp, spec);
         else k_aov<false, false><<<g, LRT_BLOCK, smem, st>>>((ScenePtr) D->d_sc, lp, spec);
     }
     HIP_CHECK(hipGetLastError());
@@ -1072,9 +1124,13 @@ void device_trace(DeviceScene *D, const lrt_rays_soa *rays, const lrt_hits_soa *
         if (n) {
             if (D->use_lds) {                     // the render kernels' tracer: BVH image in LDS
                 const uint32_t g = std::min<uint32_t>((uint32_t) D->n_cus, (n + 1023) / 1024);
-                if (any_hit) k_trace_lds<true><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, D->lds, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n);
+                if (D->ext) { if (any_hit) k_trace_lds<true, true><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, D->lds, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n);
+                              else k_trace_lds<false, true><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, D->lds, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n); }
+                else if (any_hit) k_trace_lds<true><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, D->lds, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n);
                 else k_trace_lds<false><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, D->lds, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n);
-            } else if (any_hit) k_trace<true><<<grid, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n);
+            } else if (D->ext) { if (any_hit) k_trace<true, true><<<grid, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n);
+                                 else k_trace<false, true><<<grid, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n); }
+            else if (any_hit) k_trace<true><<<grid, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n);
             else k_trace<false><<<grid, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n);
         }
         HIP_CHECK(hipMemcpyAsync(hits->t, t, (size_t) n * 4, hipMemcpyDeviceToHost, st));

@@ -58,7 +58,16 @@ struct DHetMedium {
 struct DEmitter {
     int32_t type, shape; float radiance[3]; float scale;
     float n[3]; float inv_area;          // area: rectangle frame normal (flip applied), 1/area
-    float to_world[12];                  // area: rectangle to_world rows 0..2
+    float to_world[12];                  // area: rectangle to_world rows 0..2; point: position in to_world[3], [7], [11], intensity in radiance
+};
+
+// sphere shapes (src/shapes/sphere.cpp): read through scalar loads (a scene holds a few, every lane tests all of them)
+struct DSphere {
+    float center[3], radius;
+    float to_world[9];                   // linear part of the shape's to_world (dp_du / dp_dv)
+    float to_object[12];                 // inverse of to_world, rows 0..2 (uv)
+    uint32_t shape; int32_t flip_normals;
+    float pad[2];
 };
 
 #define LRT_MAX_HIER_LEVELS 16
@@ -125,6 +134,8 @@ struct DScene {
     uint32_t root_leaf_first, root_leaf_count;
     DCamera cam; DFilm film; DEnv env;
     DDistGrid grid;
+    const DSphere *spheres;          // sphere k is primitive n_faces + k
+    uint32_t n_spheres, pad_sph;
 };
 
 // The scene record lives in device memory and is read through the CONSTANT address space: every `sc.field` is a scalar

@@ -109,6 +109,7 @@ DEV Hit trace(SceneRef sc, const Ray &r, int *__restrict__ stack /* &lds[threadI
 
 // Ray-query back-ends the integrator loops are templated on.
 struct GlobalTracer {                      // BVH in global memory (any scene size), 32-bit stack entries in LDS
+    static constexpr bool kExt = false;    // (ExtTracer below: spheres and point emitters)
     SceneRef sc; int *stack;
     DEV Hit closest(const Ray &r) const { return trace<false>(sc, r, stack); }
     DEV Hit any(const Ray &r) const { return trace<true>(sc, r, stack); }
@@ -218,6 +219,7 @@ DEV Hit trace_lds(const LdsScene &L, const Ray &r, uint16_t *__restrict__ stack 
 
 template <int STRIDE>
 struct LdsTracer {
+    static constexpr bool kExt = false;
     const LdsScene &L; uint16_t *stack;
     DEV Hit closest(const Ray &r) const { return trace_lds<false, STRIDE>(L, r, stack); }
     DEV Hit any(const Ray &r) const { return trace_lds<true, STRIDE>(L, r, stack); }
@@ -363,6 +365,144 @@ DEV SI compute_si(SceneRef sc, const Ray &r, const Hit &h, const LdsScene *L = n
 
 DEV SI GlobalTracer::surface(SceneRef s, const Ray &r, const Hit &h) const { return compute_si(s, r, h); }
 template <int STRIDE> DEV SI LdsTracer<STRIDE>::surface(SceneRef s, const Ray &r, const Hit &h) const { return compute_si(s, r, h, &L); }
+
+// ------------------------------------------------------------------ spheres
+// Sphere shapes (src/shapes/sphere.cpp) in float32: llvm_ad_rgb takes the `is_diff_v` branch of ray_intersect_preliminary_impl
+// and compute_surface_interaction.  A scene holds a few spheres, kept out of the triangle BVH and read through scalar loads
+// (the loop index is wave-uniform); a hit on sphere k is primitive n_faces + k, u = v = 0.
+
+// include/mitsuba/core/math.h:360-400
+DEV bool solve_quadratic(float a, float b, float c, float &x0, float &x1) {
+    const bool linear_case = a == 0.f, valid_linear = linear_case && b != 0.f;
+    x0 = x1 = -c / b;
+    const float discrim = fma_(b, b, -(4.f * a * c));
+    const bool valid_quadratic = !linear_case && discrim >= 0.f;
+    const float sqrt_discrim = __builtin_sqrtf(discrim);
+    const float temp = -0.5f * (b + __builtin_copysignf(sqrt_discrim, b));
+    const float x0p = temp / a, x1p = c / temp;
+    const float x0m = fmin_(x0p, x1p), x1m = fmax_(x0p, x1p);
+    if (!linear_case) { x0 = x0m; x1 = x1m; }
+    return valid_linear || valid_quadratic;
+}
+// sphere.cpp:515-572 ray_intersect_preliminary_impl: t of the hit, +inf when there is none
+DEV float sphere_intersect(V3 center, float radius, const Ray &r) {
+    const V3 l = r.o - center, d = r.d;
+    const float plane_t = dot(-l, d) / norm(d);       // the plane through the centre perpendicular to the ray: a robust origin
+    const V3 o = fma3(d, plane_t, r.o) - center;
+    const float A = squared_norm(d), B = 2.f * dot(o, d), C = squared_norm(o) - sqr(radius);
+    float near_t, far_t;
+    const bool found = solve_quadratic(A, B, C, near_t, far_t);
+    near_t += plane_t; far_t += plane_t;
+    const bool out_bounds = !(near_t <= r.maxt && far_t >= 0.f);        // NaN-aware
+    const bool in_bounds = near_t < 0.f && far_t > r.maxt;
+    const float t = near_t < 0.f ? far_t : near_t;
+    return (found && !out_bounds && !in_bounds) ? t : kInf;
+}
+// sphere.cpp:574-618 ray_test_impl (no plane shift)
+DEV bool sphere_test(V3 center, float radius, const Ray &r) {
+    const V3 o = r.o - center, d = r.d;
+    const float A = squared_norm(d), B = 2.f * dot(o, d), C = squared_norm(o) - sqr(radius);
+    float near_t, far_t;
+    const bool found = solve_quadratic(A, B, C, near_t, far_t);
+    const bool out_bounds = !(near_t <= r.maxt && far_t >= 0.f);
+    const bool in_bounds = near_t < 0.f && far_t > r.maxt;
+    return found && !out_bounds && !in_bounds;
+}
+DEV const LRT_CONST DSphere &sphere_ref(SceneRef sc, uint32_t k) { return reinterpret_cast<const LRT_CONST DSphere *>((uintptr_t) sc.spheres)[k]; }
+// Closest sphere hit (ties: the lower index)
+DEV Hit spheres_closest(SceneRef sc, const Ray &r) {
+    Hit best; best.t = kInf; best.u = best.v = 0.f; best.prim = 0xffffffffu;
+    const uint32_t ns = sc.n_spheres;
+    for (uint32_t k = 0; k < ns; ++k) {
+        const LRT_CONST DSphere &S = sphere_ref(sc, k);
+        const float t = sphere_intersect(V3(S.center[0], S.center[1], S.center[2]), S.radius, r);
+        if (t < best.t) { best.t = t; best.prim = sc.n_faces + k; }
+    }
+    return best;
+}
+DEV bool spheres_any(SceneRef sc, const Ray &r) {
+    const uint32_t ns = sc.n_spheres;
+    bool hit = false;
+    for (uint32_t k = 0; k < ns; ++k) {
+        const LRT_CONST DSphere &S = sphere_ref(sc, k);
+        hit = hit || sphere_test(V3(S.center[0], S.center[1], S.center[2]), S.radius, r);
+    }
+    return hit;
+}
+// Closest hit over spheres and triangles: the spheres first, their t tightens maxt for the BVH walk (a triangle at the same t
+// wins, the lower primitive index).  Any hit: the spheres first, early return.
+template <bool ANY_HIT, class WALK> DEV Hit trace_ext(SceneRef sc, const Ray &r, const WALK &walk) {
+    if (ANY_HIT) {
+        if (spheres_any(sc, r)) { Hit h; h.t = 0.f; h.u = h.v = 0.f; h.prim = sc.n_faces; return h; }
+        return walk(r);
+    }
+    const Hit s = spheres_closest(sc, r);
+    Ray r2 = r; r2.maxt = fmin_(r.maxt, s.t);
+    const Hit h = walk(r2);
+    return h.prim != 0xffffffffu ? h : s;
+}
+
+// src/core/vector.h dir_to_sph -> unit_angle_z (Dr.Jit: 2 asin(|v - (0, 0, sign z)| / 2), mirrored for z < 0)
+DEV float unit_angle_z(V3 v) {
+    const float temp = 2.f * m_asin(.5f * norm(V3(v.x, v.y, v.z - signf_(v.z))));
+    return v.z >= 0.f ? temp : kPi - temp;
+}
+// sphere.cpp:626-740 compute_surface_interaction, the IsDiff / !follow_shape branch: p = ray(t) without re-projection
+DEV SI compute_si_sphere(SceneRef sc, const Ray &r, const Hit &h) {
+    const uint32_t k = h.prim - sc.n_faces;
+    const DSphere S = tab(reinterpret_cast<const DSphere *>(sc.spheres), k);
+    const V3 c(S.center[0], S.center[1], S.center[2]);
+    SI si;
+    si.valid = true; si.t = h.t;
+    si.p = fma3(r.d, h.t, r.o);
+    V3 n = normalize(si.p - c);
+    const V3 local = xform_point12(S.to_object, si.p);
+    const float theta = unit_angle_z(local);
+    float phi = m_atan2(local.y, local.x);
+    if (phi < 0.f) phi += 2.f * kPi;
+    si.uv = { phi * kInvTwoPi, theta * kInvPi };
+    V3 dp_du(-local.y, local.x, 0.f);
+    const float rd = __builtin_sqrtf(sqr(local.x) + sqr(local.y)), inv_rd = rcp(rd);
+    const float cos_phi = local.x * inv_rd, sin_phi = local.y * inv_rd;
+    V3 dp_dv(local.z * cos_phi, local.z * sin_phi, -rd);
+    if (rd == 0.f) dp_dv = V3(1.f, 0.f, 0.f);
+    si.dp_du = xform_vec9(S.to_world, dp_du) * (2.f * kPi);
+    si.dp_dv = xform_vec9(S.to_world, dp_dv) * kPi;
+    if (S.flip_normals) n = V3(-n.x, -n.y, -n.z);
+    si.n = n; si.sh.n = n;
+    // shading frame as for meshes (compute_si above)
+    V3 shs = normalize(fma3(n, -dot(n, si.dp_du), si.dp_du));
+    if (si.dp_du.x == 0.f && si.dp_du.y == 0.f && si.dp_du.z == 0.f) shs = coordinate_system(n).s;
+    si.sh.s = shs; si.sh.t = cross(n, shs);
+    const V3 md(-r.d.x, -r.d.y, -r.d.z);
+    si.wi = V3(dot(md, si.sh.s), dot(md, si.sh.t), dot(md, si.sh.n));
+    si.prim = h.prim; si.shape = S.shape;
+    return si;
+}
+
+// The tracer of the EXT kernel instances (scenes with spheres or point emitters): a triangle tracer plus the spheres.  The
+// other instances keep the plain tracers, so triangle-only scenes run the code they ran before.
+template <class BASE> struct ExtTracer {
+    static constexpr bool kExt = true;
+    const BASE &base; SceneRef sc;
+    DEV Hit closest(const Ray &r) const { return trace_ext<false>(sc, r, [&](const Ray &rr) { return base.closest(rr); }); }
+    DEV Hit any(const Ray &r) const { return trace_ext<true>(sc, r, [&](const Ray &rr) { return base.any(rr); }); }
+    DEV SI surface(SceneRef s, const Ray &r, const Hit &h) const {
+        if (h.prim != 0xffffffffu && h.prim >= s.n_faces) return compute_si_sphere(s, r, h);
+        return base.surface(s, r, h);
+    }
+};
+template <bool SECOND, class A, class B> DEV const auto &pick(const A &a, const B &b) { if constexpr (SECOND) return b; else return a; }
+// What the hide_emitters loops ask of a hit: its surface (without the LDS shortcut, as they always did) and whether it lies on an
+// area emitter.  Spheres carry none (the loader refuses an area light on a sphere).
+template <class TR> DEV SI surface_of(const TR &, SceneRef sc, const Ray &r, const Hit &h) { return compute_si(sc, r, h); }
+template <class B> DEV SI surface_of(const ExtTracer<B> &tr, SceneRef sc, const Ray &r, const Hit &h) { return tr.surface(sc, r, h); }
+template <class TR> DEV bool hit_on_emitter(const TR &, SceneRef sc, const Hit &h) {
+    return h.prim != 0xffffffffu && tab(sc.shapes, sc.face_shape[h.prim], sc.one_shape).emitter >= 0;
+}
+template <class B> DEV bool hit_on_emitter(const ExtTracer<B> &, SceneRef sc, const Hit &h) {
+    return h.prim != 0xffffffffu && h.prim < sc.n_faces && tab(sc.shapes, sc.face_shape[h.prim], sc.one_shape).emitter >= 0;
+}
 
 // include/mitsuba/render/interaction.h:140-168
 DEV V3 offset_p(V3 p, V3 n, V3 d) {
@@ -641,6 +781,8 @@ DEV V3 emitter_eval_env(SceneRef sc, V3 dir_world) {
 }
 
 // Scene::sample_emitter_direction without visibility test (src/render/scene.cpp:333-383)
+// POINT: the scene may hold point emitters (the EXT kernel instances only)
+template <bool POINT = false>
 DEV V3 sample_emitter_direction(SceneRef sc, V3 ref_p, float sx, float sy, DirSample *ds) {
     uint32_t ne = sc.n_emitters;
     ds->p = V3(0.f); ds->n = V3(0.f); ds->d = V3(0.f); ds->pdf = 0.f; ds->dist = 0.f; ds->delta = false; ds->emitter = -1;
@@ -668,6 +810,14 @@ DEV V3 sample_emitter_direction(SceneRef sc, V3 ref_p, float sx, float sy, DirSa
         bool active = dot(ds->d, ds->n) < 0.f && ds->pdf != 0.f;
         V3 rad(E.radiance[0], E.radiance[1], E.radiance[2]);
         spec = active ? rad / ds->pdf : V3(0.f);
+    } else if (POINT && E.type == LRT_EMITTER_POINT) {   // src/emitters/point.cpp:119-148: a delta position, pdf 1, no surface reaches it
+        ds->p = V3(E.to_world[3], E.to_world[7], E.to_world[11]);
+        ds->pdf = 1.f; ds->delta = true;
+        ds->d = ds->p - ref_p;
+        const float dist2 = squared_norm(ds->d), inv_dist = rsqrt_(dist2);
+        ds->dist = __builtin_sqrtf(dist2);
+        ds->d = ds->d * inv_dist;
+        spec = V3(E.radiance[0], E.radiance[1], E.radiance[2]) * sqr(inv_dist);
     } else if (E.type == LRT_EMITTER_ENVMAP) {          // src/emitters/envmap.cpp:415-459
         EnvRef EV = sc.env;
         float u, v, pdf; hier_sample(sc, sx, sy, &u, &v, &pdf);

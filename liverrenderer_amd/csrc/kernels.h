@@ -318,7 +318,7 @@ DEV V3 volpath_sample_emitter(SceneRef sc, SMP &rng, V3 ref_p, V3 ref_n, bool re
                               int medium, uint32_t channel, DirSample *ds_out, const TR &tr, uint32_t &n_shadow) {
     V3 transmittance(1.f);
     float sx, sy; rng.next2(sx, sy);
-    DirSample ds; V3 emitter_val = sample_emitter_direction(sc, ref_p, sx, sy, &ds);
+    DirSample ds; V3 emitter_val = sample_emitter_direction<TR::kExt>(sc, ref_p, sx, sy, &ds);
     *ds_out = ds;
     if (ds.pdf == 0.f) return V3(0.f);
     Ray ray = spawn_ray_to(ref_p, ref_n, ds.p);
@@ -448,7 +448,7 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
         if (PRE) mei = medium_interaction_at(M, ray, ff_t);          // the free-flight stage drew this distance (same sample, channel, medium)
         else { const float sample = rng.next(); mei = het ? het_sample_interaction(M, tab(sc.het, medium), ray, sample) : medium_sample_interaction(M, ray, sample, channel); }
         if (mei.valid() && !het) ray.maxt = mei.t;                              // medium->is_homogeneous() only (volpath.cpp:221)
-        if (!needs_intersection) si = compute_si(sc, ray, hkeep);                // the interaction a null collision kept
+        if (!needs_intersection) si = surface_of(tr, sc, ray, hkeep);                // the interaction a null collision kept
         else if (!proven_empty) { hkeep = tr.closest(ray); si = tr.surface(sc, ray, hkeep); }   // else: no surface within mei.t (look-ahead of the previous trip)
         if (si.t < mei.t) mei.t = kInf;
         if (M.has_spectral_extinction) {
@@ -541,10 +541,10 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
                 bool a = true; Hit h; h.prim = 0xffffffffu; h.t = kInf; h.u = h.v = 0.f;
                 while (a) {
                     h = tr.closest(r2);
-                    a = h.prim != 0xffffffffu && tab(sc.shapes, sc.face_shape[h.prim], sc.one_shape).emitter >= 0;
-                    if (a) { SI s2 = compute_si(sc, r2, h); r2 = spawn_ray(s2.p, s2.n, r2.d); }
+                    a = hit_on_emitter(tr, sc, h);
+                    if (a) { SI s2 = surface_of(tr, sc, r2, h); r2 = spawn_ray(s2.p, s2.n, r2.d); }
                 }
-                si = compute_si(sc, r2, h);
+                si = surface_of(tr, sc, r2, h);
             }
         }
         bool count_direct = (depth == 0) || specular_chain;
@@ -635,20 +635,20 @@ DEV bool path_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const TR 
     if (max_depth == 0) { commit(); return false; }
     Hit pi = tr.closest(ray);
     if (rp.hide_emitters && depth == 0) {                          // path.cpp:178-192
-        bool skip = pi.prim != 0xffffffffu && tab(sc.shapes, sc.face_shape[pi.prim], sc.one_shape).emitter >= 0;
+        bool skip = hit_on_emitter(tr, sc, pi);
         if (skip) {
-            SI s0 = compute_si(sc, ray, pi);
+            SI s0 = surface_of(tr, sc, ray, pi);
             Ray r2 = spawn_ray(s0.p, s0.n, ray.d);
             bool a = true; Hit h; h.prim = 0xffffffffu; h.t = kInf; h.u = h.v = 0.f;
             while (a) {
                 h = tr.closest(r2);
-                a = h.prim != 0xffffffffu && tab(sc.shapes, sc.face_shape[h.prim], sc.one_shape).emitter >= 0;
-                if (a) { SI s2 = compute_si(sc, r2, h); r2 = spawn_ray(s2.p, s2.n, r2.d); }
+                a = hit_on_emitter(tr, sc, h);
+                if (a) { SI s2 = surface_of(tr, sc, r2, h); r2 = spawn_ray(s2.p, s2.n, r2.d); }
             }
             pi = h; ray = r2;
         }
     }
-    SI si = compute_si(sc, ray, pi);
+    SI si = surface_of(tr, sc, ray, pi);
     int emitter = si_emitter(sc, si);
     if (emitter >= 0) {
         float em_pdf = 0.f;
@@ -675,7 +675,7 @@ DEV bool path_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const TR 
     // symbolic loop always traces: every lane in the loop consumes the two numbers, smooth BSDF or not
     float sx, sy; rng.next2(sx, sy);
     if (active_em) {
-        em_weight = sample_emitter_direction(sc, si.p, sx, sy, &ds);
+        em_weight = sample_emitter_direction<TR::kExt>(sc, si.p, sx, sy, &ds);
         if (ds.pdf != 0.f) {                                       // scene.cpp:361-365 test_visibility
             Ray sr = spawn_ray_to(si.p, si.n, ds.p);
             n_shadow++;
@@ -776,7 +776,8 @@ DEV void retire_and_compact_wave(SceneRef sc, RpRef rp, bool had_path, bool aliv
 // 4 waves per SIMD (128 VGPRs): one 1024-thread workgroup per CU, or four 256-thread ones.  BLOCK = 512 (one workgroup per CU, 2 waves per
 // SIMD, 256 VGPRs): the wide-record integrators (volpathmis: 18 weights per path), which at 128 registers spill 430 B per lane
 // COMPACT: 80-byte records (store_state): the host launches these instances for scenes without area emitters (DRenderParams::compact)
-template <int INTEGRATOR, int BLOCK, bool LDS_BVH, bool LD, bool COMPACT = false>
+// EXT: the scene holds spheres or point emitters (ExtTracer, point-emitter sampling); the triangle-only instances are unchanged
+template <int INTEGRATOR, int BLOCK, bool LDS_BVH, bool LD, bool COMPACT = false, bool EXT = false>
 __global__ void __launch_bounds__(BLOCK, BLOCK == 512 ? 2 : (BLOCK == 768 ? 3 : 4))
 k_render(ScenePtr scp, LaunchPtr lp) {
     SceneRef sc = *scp;
@@ -806,8 +807,12 @@ k_render(ScenePtr scp, LaunchPtr lp) {
         L.tris = reinterpret_cast<const uint2 *>(smem + li.tris_off);
         L.n_faces = sc.n_faces; L.root_is_leaf = (uint32_t) sc.root_is_leaf; L.root_first = sc.root_leaf_first; L.root_count = sc.root_leaf_count;
     }
-    const LdsTracer<BLOCK> tr_lds{ L, reinterpret_cast<uint16_t *>(smem + li.stack_off) + tid };
-    const GlobalTracer tr_glb{ sc, reinterpret_cast<int *>(smem) + tid };
+    const LdsTracer<BLOCK> tr_lds_tri{ L, reinterpret_cast<uint16_t *>(smem + li.stack_off) + tid };
+    const GlobalTracer tr_glb_tri{ sc, reinterpret_cast<int *>(smem) + tid };
+    const ExtTracer<LdsTracer<BLOCK>> tr_lds_ext{ tr_lds_tri, sc };
+    const ExtTracer<GlobalTracer> tr_glb_ext{ tr_glb_tri, sc };
+    const auto &tr_lds = pick<EXT>(tr_lds_tri, tr_lds_ext);
+    const auto &tr_glb = pick<EXT>(tr_glb_tri, tr_glb_ext);
     const size_t pool = (size_t) blockIdx.x * 2u * P;
     uint32_t parity = 0;                                      // queue the round reads: parity ? A.q1 : A.q0 (the stream pointers are scalar loads at the point of use)
     if (tid == 0) { s_in[0] = s_in[1] = s_in[2] = 0; if (LONGQ) s_in[3] = 0; }
@@ -947,7 +952,8 @@ DEV float point_triangle_dist2(V3 p, V3 a, V3 ab, V3 ac) {
 }
 
 __global__ void __launch_bounds__(LRT_BLOCK)
-k_build_dist_grid(const float4 *__restrict__ tris, uint32_t n_slots, DDistGrid g, uint16_t *__restrict__ out, float abs_margin) {
+k_build_dist_grid(const float4 *__restrict__ tris, uint32_t n_slots, DDistGrid g, uint16_t *__restrict__ out, float abs_margin,
+                  const DSphere *__restrict__ spheres, uint32_t n_spheres) {
     const size_t n_cells = (size_t) g.n[0] * g.n[1] * g.n[2];
     const size_t c = (size_t) blockIdx.x * LRT_BLOCK + threadIdx.x;
     if (c >= n_cells) return;
@@ -959,6 +965,11 @@ k_build_dist_grid(const float4 *__restrict__ tris, uint32_t n_slots, DDistGrid g
         float d2 = point_triangle_dist2(p, V3(a.x, a.y, a.z), V3(b.x, b.y, b.z), V3(cc.x, cc.y, cc.z));
         if (!(d2 >= 0.f)) d2 = 0.f;                 // degenerate triangle (NaN): be conservative
         best = fmin_(best, d2);
+    }
+    for (uint32_t k = 0; k < n_spheres; ++k) {          // spheres: the exact distance | |p - c| - r |, under the same margins
+        const DSphere &S = spheres[k];
+        const float ds = __builtin_fabsf(norm(p - V3(S.center[0], S.center[1], S.center[2])) - S.radius);
+        best = fmin_(best, ds * ds);
     }
     float d = __builtin_sqrtf(best) * .999f - abs_margin;
     d = d > 0.f ? fmin_(d, 60000.f) : 0.f;
@@ -1053,7 +1064,7 @@ __global__ void k_develop(DFilm F, const float *__restrict__ film, float *__rest
     for (int c = 0; c < T; ++c) image[(size_t) i * T + c] = film[(size_t) i * C + c] / w;
 }
 
-template <bool ANY_HIT>
+template <bool ANY_HIT, bool EXT = false>
 __global__ void __launch_bounds__(LRT_BLOCK)
 k_trace(ScenePtr scp, const float *ox, const float *oy, const float *oz, const float *dx, const float *dy, const float *dz, const float *tmax,
         float *t, float *u, float *v, uint32_t *prim, uint32_t n) {
@@ -1062,13 +1073,14 @@ k_trace(ScenePtr scp, const float *ox, const float *oy, const float *oz, const f
     uint32_t i = blockIdx.x * LRT_BLOCK + threadIdx.x;
     if (i >= n) return;
     Ray r; r.o = V3(ox[i], oy[i], oz[i]); r.d = V3(dx[i], dy[i], dz[i]); r.maxt = tmax[i];
-    Hit h = trace<ANY_HIT>(sc, r, s_stack + threadIdx.x);
+    const GlobalTracer tg{ sc, s_stack + threadIdx.x };
+    Hit h = EXT ? (ANY_HIT ? ExtTracer<GlobalTracer>{ tg, sc }.any(r) : ExtTracer<GlobalTracer>{ tg, sc }.closest(r)) : trace<ANY_HIT>(sc, r, s_stack + threadIdx.x);
     if (ANY_HIT) { t[i] = h.prim != 0xffffffffu ? 0.f : kInf; return; }
     t[i] = h.t; if (u) u[i] = h.u; if (v) v[i] = h.v; if (prim) prim[i] = h.prim;
 }
 
 // The same queries through the LDS-resident BVH image (1024 threads per workgroup, as in k_render)
-template <bool ANY_HIT>
+template <bool ANY_HIT, bool EXT = false>
 __global__ void __launch_bounds__(1024)
 k_trace_lds(ScenePtr scp, DLdsInfo li, const float *ox, const float *oy, const float *oz, const float *dx, const float *dy, const float *dz, const float *tmax,
             float *t, float *u, float *v, uint32_t *prim, uint32_t n) {
@@ -1086,7 +1098,8 @@ k_trace_lds(ScenePtr scp, DLdsInfo li, const float *ox, const float *oy, const f
     __syncthreads();
     for (uint32_t i = blockIdx.x * 1024u + tid; i < n; i += gridDim.x * 1024u) {
         Ray r; r.o = V3(ox[i], oy[i], oz[i]); r.d = V3(dx[i], dy[i], dz[i]); r.maxt = tmax[i];
-        Hit h = trace_lds<ANY_HIT, 1024>(L, r, reinterpret_cast<uint16_t *>(smem + li.stack_off) + tid);
+        const LdsTracer<1024> tl{ L, reinterpret_cast<uint16_t *>(smem + li.stack_off) + tid };
+        Hit h = EXT ? (ANY_HIT ? ExtTracer<LdsTracer<1024>>{ tl, sc }.any(r) : ExtTracer<LdsTracer<1024>>{ tl, sc }.closest(r)) : trace_lds<ANY_HIT, 1024>(L, r, reinterpret_cast<uint16_t *>(smem + li.stack_off) + tid);
         if (ANY_HIT) { t[i] = h.prim != 0xffffffffu ? 0.f : kInf; continue; }
         t[i] = h.t; if (u) u[i] = h.u; if (v) v[i] = h.v; if (prim) prim[i] = h.prim;
     }

@@ -71,9 +71,9 @@ DEV void aov_eval(SceneRef sc, AovSpecPtr A, int type, const SI &si, float v[3])
         }
         case LRT_AOV_DP_DU: v[0] = si.dp_du.x; v[1] = si.dp_du.y; v[2] = si.dp_du.z; break;
         case LRT_AOV_DP_DV: v[0] = si.dp_dv.x; v[1] = si.dp_dv.y; v[2] = si.dp_dv.z; break;
-        case LRT_AOV_PRIM_INDEX: {               // analytic shapes (rectangle) have a single primitive
+        case LRT_AOV_PRIM_INDEX: {               // analytic shapes (rectangle, sphere) have a single primitive
             const DShape sd = tab(sc.shapes, si.shape, sc.one_shape);
-            v[0] = sd.kind == LRT_SHAPE_RECTANGLE ? 0.f : (float) (si.prim - A->first_face[si.shape]);
+            v[0] = sd.kind != LRT_SHAPE_MESH ? 0.f : (float) (si.prim - A->first_face[si.shape]);
             break;
         }
         case LRT_AOV_SHAPE_INDEX: v[0] = (float) (si.shape + 1u); break;   // aov.cpp:330-343: 1 + position in scene->shapes(), 0 = background
@@ -84,7 +84,7 @@ DEV void aov_eval(SceneRef sc, AovSpecPtr A, int type, const SI &si, float v[3])
 // LDS: the BVH image in LDS, 1024-thread workgroups (as k_trace_lds); else the global BVH with LRT_BLOCK threads and the traversal
 // stack in (dynamic) LDS.  Grid-stride over lanes [lp->lane_begin, lp->lane_begin + lp->n); every wave runs the same trip count, so the
 // wave reductions below always see 64 active lanes.
-template <bool LDS, bool LD>
+template <bool LDS, bool LD, bool EXT = false>           // EXT: spheres (ExtTracer)
 __global__ void __launch_bounds__(LDS ? 1024 : LRT_BLOCK)
 k_aov(ScenePtr scp, LaunchPtr lp, AovSpecPtr A) {
     constexpr uint32_t BS = LDS ? 1024u : (uint32_t) LRT_BLOCK;
@@ -122,10 +122,17 @@ k_aov(ScenePtr scp, LaunchPtr lp, AovSpecPtr A) {
             const float spx = (float) px + jx, spy = (float) py + jy;
             ray = camera_ray(sc, fma_(spx, sc.film.scale_x, sc.film.offset_x), fma_(spy, sc.film.scale_y, sc.film.offset_y));
             if (rp.pass_out) rp.pass_out[j] = rng.state;      // no nested integrator: the next pass continues after the jitter
-            if (LDS) h = trace_lds<false, 1024>(L, ray, reinterpret_cast<uint16_t *>(smem + lp->li.stack_off) + tid);
+            if (EXT) {
+                const LdsTracer<1024> tl{ L, reinterpret_cast<uint16_t *>(smem + lp->li.stack_off) + tid };
+                const GlobalTracer tg{ sc, reinterpret_cast<int *>(smem) + tid };
+                h = LDS ? ExtTracer<LdsTracer<1024>>{ tl, sc }.closest(ray) : ExtTracer<GlobalTracer>{ tg, sc }.closest(ray);
+            }
+            else if (LDS) h = trace_lds<false, 1024>(L, ray, reinterpret_cast<uint16_t *>(smem + lp->li.stack_off) + tid);
             else h = trace<false>(sc, ray, reinterpret_cast<int *>(smem) + tid);
         }
-        const SI si = LDS ? compute_si(sc, ray, h, &L) : compute_si(sc, ray, h);
+        SI si;
+        if (EXT && h.prim != 0xffffffffu && h.prim >= sc.n_faces) si = compute_si_sphere(sc, ray, h);
+        else si = LDS ? compute_si(sc, ray, h, &L) : compute_si(sc, ray, h);
         if (sample_out) {                        // per-lane test hook: the values before film accumulation
             if (have) {
                 float *o = sample_out + i * (uint64_t) n_ch;

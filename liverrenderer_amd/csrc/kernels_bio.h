@@ -92,7 +92,7 @@ DEV V3 bio_sample_emitter(SceneRef sc, SMP &rng, V3 ref_p, V3 ref_n, uint32_t re
                           DirSample *ds_out, const TR &tr, uint32_t &n_shadow) {
     V3 transmittance(1.f);
     float sx, sy; rng.next2(sx, sy);
-    DirSample ds; V3 emitter_val = sample_emitter_direction(sc, ref_p, sx, sy, &ds);
+    DirSample ds; V3 emitter_val = sample_emitter_direction<TR::kExt>(sc, ref_p, sx, sy, &ds);
     *ds_out = ds;
     if (ds.pdf == 0.f) return V3(0.f);
     Ray ray = spawn_ray_to(ref_p, ref_n, ds.p);

@@ -63,7 +63,7 @@ DEV V3 mis_sample_emitter(SceneRef sc, SMP &rng, V3 ref_p, V3 ref_n, bool ref_is
                           uint32_t channel, DirSample *ds_out, MisW<SMIS> &nee, MisW<SMIS> &uni, const TR &tr, uint32_t &n_shadow) {
     nee = p_over_f; uni = p_over_f;
     float sx, sy; rng.next2(sx, sy);
-    DirSample ds; V3 w = sample_emitter_direction(sc, ref_p, sx, sy, &ds);
+    DirSample ds; V3 w = sample_emitter_direction<TR::kExt>(sc, ref_p, sx, sy, &ds);
     V3 emitter_val = w * ds.pdf;
     if (ds.pdf == 0.f) emitter_val = V3(0.f);
     bool active = ds.pdf != 0.f;
@@ -175,7 +175,7 @@ DEV bool volpathmis_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, con
     bool act_null_scatter = false, act_medium_scatter = false, escaped_medium = false, is_spectral = false, not_spectral = false;
     MI mei; mei.t = kInf;
     SI si; si.valid = false; si.t = kInf;
-    if (!needs_intersection) si = compute_si(sc, ray, hkeep);              // a null collision kept this interaction
+    if (!needs_intersection) si = surface_of(tr, sc, ray, hkeep);              // a null collision kept this interaction
     if (!active_medium) rng.skip(2);
     if (active_medium) {
         const DMedium M = tab(sc.media, medium);
@@ -249,10 +249,10 @@ DEV bool volpathmis_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, con
                 bool a = true; Hit h; h.prim = 0xffffffffu; h.t = kInf; h.u = h.v = 0.f;
                 while (a) {
                     h = tr.closest(r2);
-                    a = h.prim != 0xffffffffu && tab(sc.shapes, sc.face_shape[h.prim], sc.one_shape).emitter >= 0;
-                    if (a) { SI s2 = compute_si(sc, r2, h); r2 = spawn_ray(s2.p, s2.n, r2.d); }
+                    a = hit_on_emitter(tr, sc, h);
+                    if (a) { SI s2 = surface_of(tr, sc, r2, h); r2 = spawn_ray(s2.p, s2.n, r2.d); }
                 }
-                si = compute_si(sc, r2, h);
+                si = surface_of(tr, sc, r2, h);
             }
         }
         bool count_direct = (depth == 0) || specular_chain;

@@ -9,7 +9,11 @@
 // bio media carry both the homogeneous parameters that path / volpath /
 // prbvolpath see through the 4-argument sample_interaction() and the element
 // coefficients of the 5-argument one, docs/BIO_TRANSPORT_SPEC.md); phase
-// {isotropic, hg}; shape {obj, rectangle, cube}; emitter {area, envmap, constant}.
+// {isotropic, hg}; shape {obj, rectangle, cube, sphere}; emitter {area, envmap, constant, point}.
+// Plugin `type` names match without regard to case (plugin_type): the reference finds plugins by file name
+// (src/core/plugin.cpp:96-139), and the fork's SphereLiverPoint scenes, written on a case-insensitive file system, say
+// "Dielectric".  A medium child of a shape named neither "interior" nor "exterior" is ignored, as src/render/shape.cpp:40-49
+// ignores it.  A sphere is one shape without faces (lrt_shape_desc); the point emitter keeps its position in to_world.
 #include "host_scene.h"
 #include "xml.h"
 #include "image_io.h"
@@ -208,13 +212,49 @@ struct Loader {
         return T;
     }
 
+    // Plugin names are matched without regard to case: the reference looks plugins up by file name, and scenes written on a
+    // case-insensitive file system (the fork's SphereLiverPoint: type="Dielectric") load there.  Every comparison below sees the
+    // lower-case form; camel-case plugin names (glissonCapsule) are spelled the same way in their comparisons.
+    static std::string plugin_type(const std::string &t) {
+        std::string r = t; for (auto &c : r) c = (char) tolower((unsigned char) c);
+        if (r == "glissoncapsule") r = "glissonCapsule";
+        return r;
+    }
+
+    // <spectrum value="...">: a uniform value or wavelength:value pairs, checked at parse time as Properties::Spectrum(string_view)
+    // does (src/core/properties.cpp:791-851; tokens split at ", ", empty ones dropped).
+    static std::vector<std::string> tokenize(const std::string &str, const char *delim) {
+        std::vector<std::string> r; std::string cur;
+        for (char ch : str) { if (strchr(delim, ch)) { if (!cur.empty()) r.push_back(cur); cur.clear(); } else cur += ch; }
+        if (!cur.empty()) r.push_back(cur);
+        return r;
+    }
+    void check_spectrum(const std::string &v) {
+        try { check_spectrum_pairs(v); }
+        catch (const std::runtime_error &e) { fail("could not parse spectrum \"" + v.substr(0, 40) + (v.size() > 40 ? "...\": " : "\": ") + e.what()); }
+    }
+    void check_spectrum_pairs(const std::string &v) {
+        std::vector<std::string> tok = tokenize(v, ", ");
+        if (tok.size() == 1 && tok[0].find(':') == std::string::npos) { parse_f32(tok[0]); return; }
+        std::vector<double> wl;
+        for (const std::string &t : tok) {
+            std::vector<std::string> pair = tokenize(t, ":");
+            if (pair.size() != 2) fail("Invalid spectrum value \"" + t + "\" (expected wavelength:value pairs)");
+            wl.push_back(parse_f32(pair[0])); parse_f32(pair[1]);
+        }
+        if (wl.size() < 2) fail("Spectrum must have at least two entries");
+        for (size_t i = 1; i < wl.size(); ++i) if (wl[i] <= wl[i - 1]) fail("Wavelengths must be specified in increasing order.");
+    }
+    static bool is_spectrum_list(const Prop &p) { return p.tag == "spectrum" && p.node->find("value") && p.node->find("value")->find(':') != std::string::npos; }
+
     ObjP parse_object(const XmlNode &n) {
         auto o = std::make_shared<Obj>();
-        o->tag = n.tag; o->type = n.has("type") ? attr(n, "type") : ""; o->id = n.has("id") ? attr(n, "id") : ""; o->name = n.has("name") ? attr(n, "name") : "";
+        o->tag = n.tag; o->type = n.has("type") ? plugin_type(attr(n, "type")) : ""; o->id = n.has("id") ? attr(n, "id") : ""; o->name = n.has("name") ? attr(n, "name") : "";
         for (auto &c : n.children) {
             const std::string &t = c->tag;
             if (t == "float" || t == "integer" || t == "string" || t == "boolean" || t == "rgb" || t == "spectrum" || t == "point" || t == "vector") {
                 Prop p; p.tag = t; p.node = c.get(); o->props[attr(*c, "name")] = p;
+                if (t == "spectrum") check_spectrum(attr(*c, "value"));
             } else if (t == "transform") {
                 Prop p; p.tag = t; p.node = c.get(); p.xform = parse_transform(*c); o->props[attr(*c, "name")] = p;
             } else if (t == "ref") {
@@ -236,6 +276,7 @@ struct Loader {
     bool has(const Obj &o, const char *k) { return o.props.count(k) != 0; }
     float get_float(const Obj &o, const char *k, float def) {
         auto it = o.props.find(k); if (it == o.props.end()) return def;
+        if (is_spectrum_list(it->second)) fail("The property \"" + std::string(k) + "\" has the wrong type (expected float, got spectrum)");   // properties.h:832-856
         if (it->second.tag != "float" && it->second.tag != "integer") fail("property \"" + std::string(k) + "\" has the wrong type");
         return parse_f32(attr(*it->second.node, "value"));
     }
@@ -255,6 +296,9 @@ struct Loader {
     }
     void get_rgb(const Obj &o, const char *k, float def, float out[3]) {
         auto it = o.props.find(k); if (it == o.props.end()) { out[0] = out[1] = out[2] = def; return; }
+        // An RGB variant integrates wavelength:value pairs against the CIE 1931 curves (properties.cpp:656-676, spectrum.cpp:86-131);
+        // those tables are not built here.
+        if (is_spectrum_list(it->second)) fail("unsupported: wavelength:value spectrum for \"" + std::string(k) + "\" (conversion to RGB through the CIE 1931 curves is not built)");
         auto v = parse_list(attr(*it->second.node, "value"));
         if (v.size() == 1) out[0] = out[1] = out[2] = (float) v[0];
         else if (v.size() == 3) { out[0] = (float) v[0]; out[1] = (float) v[1]; out[2] = (float) v[2]; }
@@ -396,9 +440,11 @@ struct Loader {
             }
         }
         if (M.type == LRT_MEDIUM_LIVER || M.type == LRT_MEDIUM_PARENCHYMA) {     // liver.cpp:188-191, parenchyma.cpp:144-147
+            // sigma_hepatocity is a plain float there (props.get<ScalarFloat>): a wavelength:value spectrum is the reference's type error.
+            // Read first, so that such a file fails with that error rather than with the missing RGB conversion of the volumes.
+            M.sigma_hepatocity = get_float(*o, "sigma_hepatocity", 1.f);
             get_rgb(*o, "sigma_blood", 1.f, M.sigma_blood); get_rgb(*o, "sigma_bile", 1.f, M.sigma_bile);
             get_rgb(*o, "sigma_lipid_water", 1.f, M.sigma_lipid_water);
-            M.sigma_hepatocity = get_float(*o, "sigma_hepatocity", 1.f);
         }
         snprintf(M.id, sizeof(M.id), "%s", o->id.empty() ? ("medium" + std::to_string(S.media.size())).c_str() : o->id.c_str());
         S.media.push_back(M); S.meddata.resize(S.media.size()); S.meddata.back() = std::move(grid);
@@ -524,15 +570,36 @@ struct Loader {
             for (auto &t : T) for (uint32_t v : t) S.faces.push_back(base + v);
             sd.n_faces = 12; sd.has_normals = 1; sd.has_texcoords = 1;
         } else if (o->type == "obj") { sd.kind = LRT_SHAPE_MESH; load_obj(*o, tw, it, sd, base); }
+        else if (o->type == "sphere") {        // src/shapes/sphere.cpp:128-165: to_world * translate(center) * scale(radius), no faces
+            sd.kind = LRT_SHAPE_SPHERE;
+            double c[3] = { 0, 0, 0 };
+            if (has(*o, "center")) vec3_attr(*o->props["center"].node, 0.0, c);
+            const double rad = get_float(*o, "radius", 1.f);
+            Mat4 L = ident(); for (int a = 0; a < 3; ++a) { L.m[5 * a] = rad; L.m[4 * a + 3] = c[a]; }
+            Mat4 W = mul(TW, L);
+            to_float(W, sd.to_world);
+            // Shear and non-uniform scale only warn (sphere.cpp:150-157); the radius is |to_world * (1,0,0)| in any case
+            double col[3][3]; for (int j = 0; j < 3; ++j) for (int a = 0; a < 3; ++a) col[j][a] = W.m[4 * a + j];
+            auto dotd = [](const double *x, const double *y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; };
+            double l0 = sqrt(dotd(col[0], col[0])), l1 = sqrt(dotd(col[1], col[1])), l2 = sqrt(dotd(col[2], col[2]));
+            if (std::fabs(dotd(col[0], col[1])) > 1e-6 * l0 * l1 || std::fabs(dotd(col[0], col[2])) > 1e-6 * l0 * l2 || std::fabs(dotd(col[1], col[2])) > 1e-6 * l1 * l2)
+                fprintf(stderr, "[lrt] sphere: 'to_world' transform shouldn't contain any shearing!\n");
+            if (!(std::fabs(l0 - l1) < 1e-6 * l0 && std::fabs(l0 - l2) < 1e-6 * l0))
+                fprintf(stderr, "[lrt] sphere: 'to_world' transform shouldn't contain non-uniform scaling!\n");
+            sd.n_faces = 0; sd.first_face = 0;
+        }
         else fail("unsupported shape type \"" + o->type + "\"");
         uint32_t shape_ix = (uint32_t) S.shapes.size();
         for (uint32_t i = 0; i < sd.n_faces; ++i) S.face_shape.push_back(shape_ix);
         for (auto &c : o->children) {
             const ObjP &ch = c.second;
             if (ch->tag == "bsdf") sd.bsdf = make_bsdf(ch);
-            else if (ch->tag == "medium") { int m = make_medium(ch); if (c.first == "interior") sd.interior_medium = m; else if (c.first == "exterior") sd.exterior_medium = m; else fail("medium child of a shape must be named \"interior\" or \"exterior\""); }
+            else if (ch->tag == "medium") {       // src/render/shape.cpp:40-49 binds these two names and ignores any other medium
+                if (c.first == "interior") sd.interior_medium = make_medium(ch); else if (c.first == "exterior") sd.exterior_medium = make_medium(ch);
+            }
             else if (ch->tag == "emitter") {
                 if (ch->type != "area") fail("only area emitters can be attached to shapes");
+                if (sd.kind == LRT_SHAPE_SPHERE) fail("unsupported: an area emitter on a sphere (area emitters are supported on rectangle shapes only)");
                 if (sd.kind != LRT_SHAPE_RECTANGLE) fail("area emitters are supported on rectangle shapes only");
                 if (has(*ch, "to_world")) fail("Found a 'to_world' transformation -- this is not allowed. The area light inherits this transformation from its parent shape.");
                 lrt_emitter_desc E{}; E.type = LRT_EMITTER_AREA; get_rgb(*ch, "radiance", 1.f, E.radiance); E.shape = (int) shape_ix; E.scale = 1.f;
@@ -550,6 +617,18 @@ struct Loader {
         lrt_emitter_desc E{}; E.shape = -1; E.scale = 1.f; std::vector<float> data;
         Mat4 I = ident(); to_float(I, E.to_world);
         if (o->type == "constant") { E.type = LRT_EMITTER_CONSTANT; get_rgb(*o, "radiance", 1.f, E.radiance); }
+        else if (o->type == "point") {          // src/emitters/point.cpp:54-70: position = to_world * 0 (or `position`), intensity
+            E.type = LRT_EMITTER_POINT; get_rgb(*o, "intensity", 1.f, E.radiance);
+            Mat4 T = get_xform(*o, "to_world");
+            if (has(*o, "position")) {
+                if (has(*o, "to_world")) fail("Only one of the parameters 'position' and 'to_world' can be specified at the same time!'");
+                double v[3]; vec3_attr(*o->props["position"].node, 0.0, v);
+                T = ident(); for (int a = 0; a < 3; ++a) T.m[4 * a + 3] = v[a];
+            }
+            to_float(T, E.to_world);
+            S.emitters.push_back(E); S.emdata.push_back(std::move(data));
+            return;
+        }
         else if (o->type == "envmap") {         // src/emitters/envmap.cpp:109-236
             E.type = LRT_EMITTER_ENVMAP; E.scale = get_float(*o, "scale", 1.f);
             if (get_bool(*o, "mis_compensation", false)) fail("envmap: mis_compensation is not supported");
@@ -560,7 +639,7 @@ struct Loader {
             for (size_t p = 0; p < (size_t) im.width * im.height; ++p)
                 for (int c = 0; c < 3; ++c) { float v = im.data[p * im.channels + (im.channels >= 3 ? c : 0)]; if (im.srgb) v = srgb_to_linear(v); data[p * 3 + c] = v; }
         } else fail("unsupported emitter type \"" + o->type + "\"");
-        for (auto &e : S.emitters) if (e.type != LRT_EMITTER_AREA) fail("Only one environment emitter can be specified per scene.");
+        for (auto &e : S.emitters) if (e.type == LRT_EMITTER_ENVMAP || e.type == LRT_EMITTER_CONSTANT) fail("Only one environment emitter can be specified per scene.");
         S.emitters.push_back(E); S.emdata.push_back(std::move(data));
     }
 
@@ -751,6 +830,12 @@ struct Loader {
         }
         if (!have_sensor) fail("the scene has no sensor");
         for (auto &o : objs) if (o->tag == "integrator" && o->type == "aov") make_integrator(o);
+        bool ext = false;                       // spheres / point emitters: prbvolpath's adjoint is built for triangles and area / infinite emitters
+        for (auto &sh : S.shapes) ext = ext || sh.kind == LRT_SHAPE_SPHERE;
+        for (auto &e : S.emitters) ext = ext || e.type == LRT_EMITTER_POINT;
+        bool prb = S.desc.integrator.type == LRT_INTEGRATOR_PRBVOLPATH;
+        for (int k = 0; S.has_aov && k < S.aov.n_integrators; ++k) prb = prb || S.aov.integrators[k].type == LRT_INTEGRATOR_PRBVOLPATH;
+        if (ext && prb) fail("unsupported: prbvolpath on a scene with sphere shapes or point emitters");
         S.fix_pointers();
     }
 };
