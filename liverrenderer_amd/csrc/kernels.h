@@ -313,9 +313,9 @@ DEV void finish_paths_wave(SceneRef sc, RpRef rp, float *__restrict__ film, floa
 
 // ---------------------------------------------------------- volpath NEE
 // src/integrators/volpath.cpp:400-554.  ref_n is zero for medium interactions.
-template <bool HET, typename SMP, typename TR>
+template <bool HET, typename SMP, typename TR, typename CNT>
 DEV V3 volpath_sample_emitter(SceneRef sc, SMP &rng, V3 ref_p, V3 ref_n, bool ref_is_surface, uint32_t ref_shape, V3 ref_geo_n,
-                              int medium, uint32_t channel, DirSample *ds_out, const TR &tr, uint32_t &n_shadow) {
+                              int medium, uint32_t channel, DirSample *ds_out, const TR &tr, CNT &n_shadow) {
     V3 transmittance(1.f);
     float sx, sy; rng.next2(sx, sy);
     DirSample ds; V3 emitter_val = sample_emitter_direction<TR::kExt>(sc, ref_p, sx, sy, &ds);
@@ -384,6 +384,16 @@ DEV V3 volpath_sample_emitter(SceneRef sc, SMP &rng, V3 ref_p, V3 ref_n, bool re
     return transmittance * emitter_val;
 }
 
+// Event counter of the homogeneous-media volpath kernels: one 64-bit LDS add per wave and event, by the wave's first active lane, of the
+// number of active lanes.  No register carries a count through the trip (a per-lane count lived across every trip and was spilled).
+struct WaveCount {
+    unsigned long long *c;                                              // LDS, per workgroup
+    DEV void operator++(int) {
+        const unsigned long long m = __ballot(true);
+        if ((threadIdx.x & 63u) == (uint32_t) (__ffsll((long long) m) - 1)) atomicAdd(c, (unsigned long long) __popcll(m));
+    }
+};
+
 // One trip of volpath's while_loop (src/integrators/volpath.cpp:170-391).
 // Returns true when the path survives.
 // HET: the scene holds heterogeneous media (delta tracking, volpath.cpp:238-259): a null collision moves the ray origin
@@ -393,8 +403,8 @@ DEV V3 volpath_sample_emitter(SceneRef sc, SMP &rng, V3 ref_p, V3 ref_n, bool re
 // of a camera lane's first trip), on the lane's own generator: same draws in the same order.  A queued record therefore holds a path
 // that is known to run its next trip, with the throughput already divided by the survival probability, the free-flight distance
 // in the record (ff_t) and, when the distance field proves that distance free of surfaces, PF_NOHIT.
-template <bool HET, typename SMP, typename TR>
-DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const TR &tr, uint32_t &n_shadow, uint32_t &n_extra, bool fresh = false, StampClock *clk = nullptr) {
+template <bool HET, typename SMP, typename TR, typename CNT>
+DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const TR &tr, CNT &n_shadow, CNT &n_extra, bool fresh = false, StampClock *clk = nullptr) {
     constexpr bool PRE = !HET;
     uint32_t depth = s.flags & PF_DEPTH_MASK;
     bool proven_empty = (s.flags & PF_NOHIT) != 0;
@@ -402,6 +412,7 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
     const bool needs_intersection = !(HET && (s.flags & PF_HAVE_SI));
     bool act_null_scatter = false;
     Hit hkeep; hkeep.t = s.hit.x; hkeep.u = s.hit.y; hkeep.v = s.hit.z; hkeep.prim = f2u(s.hit.w);
+    if (PRE) { hkeep.t = kInf; hkeep.u = hkeep.v = 0.f; hkeep.prim = 0xffffffffu; }       // (no kept hit: the records carry none)
     int medium = (int) ((s.flags & PF_MEDIUM_MASK) >> PF_MEDIUM_SHIFT) - 1;
     const uint32_t channel = (s.flags >> PF_CHANNEL_SHIFT) & 3u;
     bool specular_chain = (s.flags & PF_SPECULAR) != 0, valid_ray = (s.flags & PF_VALID) != 0;
@@ -449,7 +460,13 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
         else { const float sample = rng.next(); mei = het ? het_sample_interaction(M, tab(sc.het, medium), ray, sample) : medium_sample_interaction(M, ray, sample, channel); }
         if (mei.valid() && !het) ray.maxt = mei.t;                              // medium->is_homogeneous() only (volpath.cpp:221)
         if (!needs_intersection) si = surface_of(tr, sc, ray, hkeep);                // the interaction a null collision kept
-        else if (!proven_empty) { hkeep = tr.closest(ray); si = tr.surface(sc, ray, hkeep); }   // else: no surface within mei.t (look-ahead of the previous trip)
+        else if (!proven_empty) {                                                    // else: no surface within mei.t (look-ahead of the previous trip)
+            hkeep = tr.closest(ray);
+            // PRE: only the distance here; the surface interaction is formed in the surface branch, for the lanes that get there (the hit
+            // came first).  Its thirty-odd values would otherwise live through the medium scatter and its emitter sampling.
+            if (PRE) { si.valid = hkeep.prim != 0xffffffffu; si.t = si.valid ? hkeep.t : kInf; }
+            else si = tr.surface(sc, ray, hkeep);
+        }
         if (si.t < mei.t) mei.t = kInf;
         if (M.has_spectral_extinction) {
             float t = fmin_(mei.t, si.t) - mei.mint;
@@ -531,8 +548,12 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
     }
     // ---- surface interactions
     active_surface = active_surface || escaped_medium;
-    bool intersect = active_surface && !escaped_medium;   // medium lanes already hold si
-    if (intersect) { Hit h = tr.closest(ray); si = tr.surface(sc, ray, h); }
+    bool intersect = active_surface && !escaped_medium;   // medium lanes already hold si (PRE: its hit, and the ray is still the one queried)
+    if (PRE) {
+        Hit h = hkeep;
+        if (intersect) h = tr.closest(ray);
+        if (active_surface) si = tr.surface(sc, ray, h);
+    } else if (intersect) { Hit h = tr.closest(ray); si = tr.surface(sc, ray, h); }
     if (active_surface) {
         if (rp.hide_emitters && depth == 0 && intersect) {         // volpath.cpp:304-320, integrator.cpp:96-123
             bool skip = si.valid && tab(sc.shapes, si.shape, sc.one_shape).emitter >= 0;
@@ -593,7 +614,7 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
     // !PRE (heterogeneous media): the same as a look-ahead on a copy of the generator; only the retirement and the proof are kept.
     if (clk) clk->at(3);                                                // (scatter: weights, NEE rejection, phase sample)
     if (PRE) {
-        if (active) { if (!termination_stage()) { active = false; n_extra += 1; } else free_flight_stage(); }
+        if (active) { if (!termination_stage()) { active = false; n_extra++; } else free_flight_stage(); }
         if (clk) clk->at(4);                                            // (termination + free-flight stage: draws, log, distance field)
     } else if (active) {
         SMP pk = rng;
@@ -601,7 +622,7 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
         float q2 = fmin_(max3(throughput) * sqr(eta), .95f);
         if (a2) { float u = pk.next(); a2 = (u < q2) || !(depth > (uint32_t) rp.rr_depth); }
         a2 = a2 && depth < max_depth;
-        if (!a2) { active = false; n_extra += 1; rng = pk; }      // the retired trip's Russian-roulette draw stays consumed (multi-pass renders)
+        if (!a2) { active = false; n_extra++; rng = pk; }      // the retired trip's Russian-roulette draw stays consumed (multi-pass renders)
         else if (medium >= 0 && sc.grid.enabled && !(HET && act_null_scatter)) {
             const DMedium M = tab(sc.media, medium);
             if (!(HET && M.het)) {                    // a heterogeneous medium does not shorten the ray: its query is always the full one
@@ -817,6 +838,13 @@ k_render(ScenePtr scp, LaunchPtr lp) {
     uint32_t parity = 0;                                      // queue the round reads: parity ? A.q1 : A.q0 (the stream pointers are scalar loads at the point of use)
     if (tid == 0) { s_in[0] = s_in[1] = s_in[2] = 0; if (LONGQ) s_in[3] = 0; }
     bool lanes_left = true;                                   // thread 0
+    // Counters: per-lane registers, summed over the wave at the end.  The homogeneous-media volpath kernels keep none in vector registers:
+    // trips and loaded records are per-wave sums of tile populations (scalar registers), shadow-ray queries and trips retired by the
+    // look-ahead per-workgroup sums in LDS (WaveCount).
+    constexpr bool VP_LDS_COUNT = INTEGRATOR == LRT_INTEGRATOR_VOLPATH;
+    __shared__ unsigned long long s_cnt[2];
+    if (VP_LDS_COUNT && tid < 2) s_cnt[tid] = 0;
+    WaveCount wc_shadow{ &s_cnt[0] }, wc_extra{ &s_cnt[1] };
     uint32_t n_shadow = 0, n_extra = 0, n_trips = 0, n_loaded = 0;
     if (rp.profile & 1u) t_loop_start = wall_clock64();
     for (;;) {
@@ -854,11 +882,16 @@ k_render(ScenePtr scp, LaunchPtr lp) {
                 else if (t < ta + tc) { i = ((t - ta) << 6) + lane_in_wave; had_path = i < n_c; i += P; }
                 else if (LONGQ && t < ta + tcl) { i = ((t - ta - tc) << 6) + lane_in_wave; had_path = i < n_l; i = P - 1u - i; }
                 else { i = ((t - ta - tcl) << 6) + lane_in_wave; had_path = i < n_b; i = 2u * P - 1u - i; }
-                if (had_path) { load_state<MODE>(parity ? A.q1 : A.q0, pool + i, s, COMPACT); n_loaded += 1; }
+                if (had_path) { load_state<MODE>(parity ? A.q1 : A.q0, pool + i, s, COMPACT); if (!VP_LDS_COUNT) n_loaded += 1; }
             } else {
                 const uint32_t i = ((t - ta - tcl - tb) << 6) + lane_in_wave;
                 had_path = i < fresh;
                 if (had_path) s = generate_camera_path<LD>(sc, rp, A.pixel_list, A.lane_begin + fresh_base + i);
+            }
+            if (VP_LDS_COUNT) {
+                const uint32_t n_had = (uint32_t) __popcll(__ballot(had_path));       // every path of the tile runs one trip
+                n_trips += n_had;
+                if (t < ta + tcl + tb) n_loaded += n_had;
             }
 #ifdef LRT_STAMP
             clk.at(0);                                                  // ticket, index arithmetic, load issue
@@ -877,13 +910,13 @@ k_render(ScenePtr scp, LaunchPtr lp) {
                 else {
                     const bool fresh_tile = t >= ta + tcl + tb;
 #ifdef LRT_STAMP
-                    alive = LDS_BVH ? volpath_iteration<false>(sc, rp, s, rng, tr_lds, n_shadow, n_extra, fresh_tile, &clk) : volpath_iteration<false>(sc, rp, s, rng, tr_glb, n_shadow, n_extra, fresh_tile, &clk);
+                    alive = LDS_BVH ? volpath_iteration<false>(sc, rp, s, rng, tr_lds, wc_shadow, wc_extra, fresh_tile, &clk) : volpath_iteration<false>(sc, rp, s, rng, tr_glb, wc_shadow, wc_extra, fresh_tile, &clk);
 #else
-                    alive = LDS_BVH ? volpath_iteration<false>(sc, rp, s, rng, tr_lds, n_shadow, n_extra, fresh_tile) : volpath_iteration<false>(sc, rp, s, rng, tr_glb, n_shadow, n_extra, fresh_tile);
+                    alive = LDS_BVH ? volpath_iteration<false>(sc, rp, s, rng, tr_lds, wc_shadow, wc_extra, fresh_tile) : volpath_iteration<false>(sc, rp, s, rng, tr_glb, wc_shadow, wc_extra, fresh_tile);
 #endif
                 }
                 s.rng_state = rng.state;
-                n_trips += 1;
+                if (!VP_LDS_COUNT) n_trips += 1;
             }
 #ifdef LRT_STAMP
             retire_and_compact_wave<MODE, READLANE, COMPACT, LONGQ>(sc, rp, had_path, alive, s, A.film, A.sample_out, A.sample_base, parity ? A.q0 : A.q1, pool, P, s_out, &clk);
@@ -917,14 +950,23 @@ k_render(ScenePtr scp, LaunchPtr lp) {
     if (tid == 0 && blockIdx.x == 7) printf("[stamp] tiles of kind %d in workgroup 7: %llu; cycles per tile: ticket+load issue %.0f, record wait+TEA %.0f, to the end of the medium interaction / ray query %.0f, scatter + surface %.0f, termination+free flight %.0f, ballots+slots %.0f, stores %.0f, film %.0f\n", LRT_STAMP_KIND, s_stamp[15],
         (double) s_stamp[0] / s_stamp[15], (double) s_stamp[1] / s_stamp[15], (double) s_stamp[2] / s_stamp[15], (double) s_stamp[3] / s_stamp[15], (double) s_stamp[4] / s_stamp[15], (double) s_stamp[5] / s_stamp[15], (double) s_stamp[6] / s_stamp[15], (double) s_stamp[7] / s_stamp[15]);
 #endif
-    n_trips += n_extra;
-    for (int off = 32; off > 0; off >>= 1) {
-        n_shadow += __shfl_down(n_shadow, off); n_trips += __shfl_down(n_trips, off); n_loaded += __shfl_down(n_loaded, off);
+    if (!VP_LDS_COUNT) {
+        n_trips += n_extra;
+        for (int off = 32; off > 0; off >>= 1) {
+            n_shadow += __shfl_down(n_shadow, off); n_trips += __shfl_down(n_trips, off); n_loaded += __shfl_down(n_loaded, off);
+        }
     }
     if (lane_in_wave == 0) {
-        if (n_shadow) atomicAdd(&A.cnt->n_shadow, (unsigned long long) n_shadow);
+        if (!VP_LDS_COUNT && n_shadow) atomicAdd(&A.cnt->n_shadow, (unsigned long long) n_shadow);
         if (n_trips) atomicAdd(&A.cnt->n_iter, (unsigned long long) n_trips);
         if (n_loaded) atomicAdd(&A.cnt->n_records, (unsigned long long) n_loaded);
+    }
+    if (VP_LDS_COUNT) {
+        __syncthreads();
+        if (tid == 0) {
+            if (s_cnt[0]) atomicAdd(&A.cnt->n_shadow, s_cnt[0]);
+            if (s_cnt[1]) atomicAdd(&A.cnt->n_iter, s_cnt[1]);
+        }
     }
 }
 
