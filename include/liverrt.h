@@ -142,12 +142,16 @@ typedef struct {
 typedef struct {
     int32_t type;             /* LRT_EMITTER_*                                     */
     float   radiance[3];      /* area / constant; point [v106]: intensity          */
-    int32_t shape;            /* area: owning shape                                */
+    int32_t shape;            /* area: owning shape, a rectangle or [v107] any LRT_SHAPE_MESH */
     float   scale;            /* envmap                                            */
     float   to_world[16];     /* envmap, row-major; point [v106]: position in column 3 */
     int32_t width, height;    /* envmap: ORIGINAL bitmap resolution (w, h)         */
     const float *data;        /* envmap: h * w * 3 linear RGB floats               */
 } lrt_emitter_desc;
+/* [v107] An area emitter on an LRT_SHAPE_MESH shape samples a face by area (src/render/mesh.cpp:449-482,861-935; the table
+   is built from positions[] and faces[] of its face range).  A mesh without faces, or one whose total area is zero, is
+   rejected (LRT_ERR_INVALID).  prbvolpath rejects scenes with such an emitter (LRT_ERR_UNSUPPORTED), and the CPU oracle
+   under oracle/ must not be handed one (it samples area emitters as rectangles).                                  */
 
 /* samplers: src/samplers/independent.cpp (PCG32 stream per lane), src/samplers/ldsampler.cpp ((0,2)-sequence,
    TEA-shuffled permutation + per-pixel scramble) */
@@ -245,7 +249,7 @@ typedef struct {
 typedef struct lrt_scene lrt_scene;
 
 LRT_API const char *lrt_last_error(void);
-LRT_API int         lrt_version(void);
+LRT_API int         lrt_version(void);   /* 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
 
 LRT_API lrt_status lrt_scene_load_xml(const char *path, const char *const *defines,
                                       int n_defines, lrt_scene **out);
@@ -302,6 +306,16 @@ LRT_API lrt_status lrt_render_backward_multi(lrt_scene *scene, const lrt_render_
  * goes through, standing in for Dr.Jit's dr::log / dr::exp / ... of include/mitsuba/core/math.h users) and its division / sqrt / rcp,
  * one value per lane.  fn: 0 log(x), 1 exp(x), 2 sincos(x) -> out, out2, 3 atan2(y, x), 4 acos(x), 5 log2(x), 6 x / y, 7 sqrt(x), 8 1 / x. */
 LRT_API lrt_status lrt_math_eval(int fn, const float *x, const float *y, uint32_t n, float *out, float *out2, int device);
+
+/* Test hook [v107]: Scene::sample_emitter_direction of the render kernels that serve spheres, point emitters and mesh
+ * emitters (csrc/dshade.h), on the device, for n reference points ref_p[3 i ..] and samples sample[2 i ..]; then a ray
+ * query from ref_p along the sampled direction and, at its hit, the emitter pdf and emitted radiance the integrators use.
+ * out: LRT_PROBE_FLOATS floats per input:
+ *   [0..2] p, [3..5] n, [6..8] d, [9] dist, [10] pdf, [11..13] weight (radiance / pdf), [14] emitter index (-1: none),
+ *   [15] shape of the hit (-1: miss), [16] pdf_emitter_direction at the hit (0 if the shape carries no emitter),
+ *   [17..19] emitter_eval at the hit (area.cpp eval: one-sided through the shading frame).  Indices are stored as floats. */
+#define LRT_PROBE_FLOATS 20
+LRT_API lrt_status lrt_emitter_probe(lrt_scene *scene, const float *ref_p, const float *sample, uint32_t n, float *out, int device);
 
 /* SoA ray queries (layout mirrors RayHit of src/render/scene_native.inl:135-142).
  * Miss: t = +inf, prim = 0xffffffff.  any_hit: only t (0 on hit, +inf on miss). */

@@ -368,6 +368,21 @@ class Scene:
         _lib.check(self._lib.lrt_trace(self._h, C.byref(rays), C.byref(hits), n, int(any_hit)))
         return t, u, v, prim
 
+    def emitter_probe(self, ref_p, sample, device=0):
+        """lrt_emitter_probe (test hook): the device's Scene::sample_emitter_direction at ref_p (n x 3) with sample (n x 2), then a ray
+        query along the sampled direction and the integrators' emitter pdf / emission at its hit.  Returns a dict of arrays:
+        p, n, d (n x 3), dist, pdf, weight (n x 3), emitter (int), hit_shape (int, -1: miss), hit_pdf, hit_le (n x 3)."""
+        ref_p = np.ascontiguousarray(ref_p, dtype=np.float32).reshape(-1, 3)
+        sample = np.ascontiguousarray(sample, dtype=np.float32).reshape(-1, 2)
+        if ref_p.shape[0] != sample.shape[0]:
+            raise ValueError("emitter_probe: ref_p and sample must have the same number of rows")
+        n = ref_p.shape[0]
+        out = np.empty((n, _lib.PROBE_FLOATS), dtype=np.float32)
+        FP = C.POINTER(C.c_float)
+        _lib.check(self._lib.lrt_emitter_probe(self._h, ref_p.ctypes.data_as(FP), sample.ctypes.data_as(FP), n, out.ctypes.data_as(FP), int(device)))
+        return {"p": out[:, 0:3], "n": out[:, 3:6], "d": out[:, 6:9], "dist": out[:, 9], "pdf": out[:, 10], "weight": out[:, 11:14],
+                "emitter": out[:, 14].astype(np.int32), "hit_shape": out[:, 15].astype(np.int32), "hit_pdf": out[:, 16], "hit_le": out[:, 17:20]}
+
     # -- parameters (mi.traverse) -------------------------------------------
     def param_set(self, key, value):
         v = np.atleast_1d(np.asarray(value, dtype=np.float32))
@@ -484,9 +499,11 @@ def render_stats(scene):
 
 
 def scene_from_buffers(positions, faces, normals=None, texcoords=None, reflectance=(0.5, 0.5, 0.5), film=(64, 64),
-                       sensor_to_world=None, fov=45.0, spp=4, integrator="path", max_depth=-1, constant_radiance=None):
+                       sensor_to_world=None, fov=45.0, spp=4, integrator="path", max_depth=-1, constant_radiance=None,
+                       area_radiance=None, flip_normals=False):
     """Build a one-mesh scene from raw buffers through `lrt_scene_from_desc` (the "from buffers" entry of the C ABI).
-    The mesh gets a diffuse BSDF; an optional constant environment emitter lights it."""
+    The mesh gets a diffuse BSDF; an optional constant environment emitter lights it, and `area_radiance` makes the mesh
+    itself an area emitter of that radiance."""
     L = _lib.lib()
     pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
     fc = np.ascontiguousarray(faces, dtype=np.uint32).reshape(-1, 3)
@@ -496,7 +513,7 @@ def scene_from_buffers(positions, faces, normals=None, texcoords=None, reflectan
     fshape = np.zeros(nf, np.uint32)
     FP, UP = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
     shape = _lib.ShapeDesc(kind=0, first_face=0, n_faces=nf, bsdf=0, emitter=-1, interior_medium=-1, exterior_medium=-1,
-                           has_normals=int(normals is not None), has_texcoords=int(texcoords is not None), flip_normals=0)
+                           has_normals=int(normals is not None), has_texcoords=int(texcoords is not None), flip_normals=int(bool(flip_normals)))
     shape.to_world[:] = list(np.eye(4, dtype=np.float32).reshape(-1))
     tex = _lib.TextureDesc(type=0, width=0, height=0, channels=0)
     tex.color0[:] = list(reflectance); tex.color1[:] = list(reflectance); tex.to_uv[:] = [1, 0, 0, 0, 1, 0, 0, 0, 1]
@@ -506,10 +523,18 @@ def scene_from_buffers(positions, faces, normals=None, texcoords=None, reflectan
     d.positions, d.normals, d.texcoords = pos.ctypes.data_as(FP), nrm.ctypes.data_as(FP), uv.ctypes.data_as(FP)
     d.faces, d.face_shape = fc.ctypes.data_as(UP), fshape.ctypes.data_as(UP)
     d.shapes, d.bsdfs, d.textures = C.pointer(shape), C.pointer(bsdf), C.pointer(tex)
-    em = _lib.EmitterDesc(type=2, shape=-1, scale=1.0)
+    ems = []
+    if area_radiance is not None:
+        area = _lib.EmitterDesc(type=0, shape=0, scale=1.0)
+        area.radiance[:] = list(area_radiance); area.to_world[:] = list(np.eye(4, dtype=np.float32).reshape(-1))
+        shape.emitter = len(ems); ems.append(area)
     if constant_radiance is not None:
+        em = _lib.EmitterDesc(type=2, shape=-1, scale=1.0)
         em.radiance[:] = list(constant_radiance); em.to_world[:] = list(np.eye(4, dtype=np.float32).reshape(-1))
-        d.n_emitters, d.emitters = 1, C.pointer(em)
+        ems.append(em)
+    em_arr = (_lib.EmitterDesc * max(len(ems), 1))(*ems)
+    if ems:
+        d.n_emitters, d.emitters = len(ems), C.cast(em_arr, C.POINTER(_lib.EmitterDesc))
     tw = ScalarTransform4f() if sensor_to_world is None else sensor_to_world
     d.sensor.to_world[:] = [float(x) for x in np.asarray(tw.matrix, dtype=np.float32).reshape(-1)]
     d.sensor.fov_x, d.sensor.near_clip, d.sensor.far_clip, d.sensor.medium = fov, 1e-2, 1e4, -1

@@ -14,6 +14,7 @@ OK = 0
 INTEGRATOR = {"path": 0, "volpath": 1, "prbvolpath": 2, "biovolpath": 3, "biovolpath06": 4, "volpathmis": 5}
 MEDIUM = {"homogeneous": 0, "liver": 1, "parenchyma": 2, "glissonCapsule": 3, "heterogeneous": 4}
 EMITTER = {"area": 0, "envmap": 1, "constant": 2}
+PROBE_FLOATS = 20      # include/liverrt.h LRT_PROBE_FLOATS (lrt_emitter_probe)
 
 
 class ShapeDesc(C.Structure):
@@ -186,6 +187,7 @@ def lib():
     L.lrt_render_samples.argtypes = [C.c_void_p, P(RenderOpts), C.c_uint64, C.c_uint32, C.c_void_p]
     L.lrt_render_backward.argtypes = [C.c_void_p, P(RenderOpts), C.c_void_p, P(ParamGrads)]
     L.lrt_trace.argtypes = [C.c_void_p, P(RaysSoA), P(HitsSoA), C.c_uint32, C.c_int]
+    L.lrt_emitter_probe.argtypes = [C.c_void_p, P(C.c_float), P(C.c_float), C.c_uint32, P(C.c_float), C.c_int]
     L.lrt_param_set.argtypes = [C.c_void_p, C.c_char_p, P(C.c_float), C.c_int]
     L.lrt_param_get.argtypes = [C.c_void_p, C.c_char_p, P(C.c_float), C.c_int]
     L.lrt_image_read.argtypes = [C.c_char_p, P(C.c_int), P(C.c_int), P(C.c_int), P(P(C.c_float))]
@@ -200,7 +202,7 @@ def lib():
     L.lrt_render_aov.argtypes = [C.c_void_p, P(RenderOpts), C.c_void_p, C.c_void_p]
     L.lrt_render_aov_samples.argtypes = [C.c_void_p, P(RenderOpts), C.c_uint64, C.c_uint32, C.c_void_p]
     for name in ("lrt_image_read", "lrt_image_write_exr", "lrt_image_write_png", "lrt_scene_load_xml", "lrt_scene_load_xml_string", "lrt_scene_from_desc", "lrt_render", "lrt_render_multi", "lrt_render_backward_multi", "lrt_math_eval", "lrt_render_stats_get",
-                 "lrt_film_develop", "lrt_render_samples", "lrt_render_backward", "lrt_trace", "lrt_param_set", "lrt_param_get",
+                 "lrt_film_develop", "lrt_render_samples", "lrt_render_backward", "lrt_trace", "lrt_emitter_probe", "lrt_param_set", "lrt_param_get",
                  "lrt_image_write_exr_channels", "lrt_scene_aov_get", "lrt_render_aov", "lrt_render_aov_samples"):
         getattr(L, name).restype = C.c_int
     _lib = L
@@ -209,7 +211,7 @@ def lib():
 
 EXPORTED_SYMBOLS = ["lrt_last_error", "lrt_version", "lrt_scene_load_xml", "lrt_scene_load_xml_string", "lrt_scene_from_desc",
                     "lrt_scene_desc_get", "lrt_scene_free", "lrt_render", "lrt_render_multi", "lrt_render_backward_multi", "lrt_math_eval", "lrt_render_stats_get", "lrt_film_develop",
-                    "lrt_render_samples", "lrt_render_backward", "lrt_trace", "lrt_param_set", "lrt_param_get",
+                    "lrt_render_samples", "lrt_render_backward", "lrt_trace", "lrt_emitter_probe", "lrt_param_set", "lrt_param_get",
                     "lrt_image_read", "lrt_image_free", "lrt_image_write_exr", "lrt_image_write_png",
                     "lrt_vae_model_create", "lrt_vae_model_free", "lrt_vae_scatter",
                     "lrt_scene_aov_get", "lrt_aov_channel_name", "lrt_render_aov", "lrt_render_aov_samples", "lrt_image_write_exr_channels"]

@@ -28,7 +28,7 @@ static lrt_status fail(lrt_status st, const std::string &msg) { g_error = msg; r
 extern "C" {
 
 const char *lrt_last_error(void) { return g_error.c_str(); }
-int lrt_version(void) { return 106; }    // 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
+int lrt_version(void) { return 107; }    // 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
 
 static std::vector<std::pair<std::string, std::string>> parse_defines(const char *const *defines, int n) {
     std::vector<std::pair<std::string, std::string>> r;
@@ -110,7 +110,9 @@ static void validate_desc(const lrt_scene_desc &d) {
         if (E.type == LRT_EMITTER_AREA) {
             if (E.shape < 0 || (uint32_t) E.shape >= d.n_shapes) bad("area emitter references an invalid shape");
             const lrt_shape_desc &s = d.shapes[E.shape];
-            if (s.kind != LRT_SHAPE_RECTANGLE || s.n_faces < 1) bad("area emitters are supported on rectangle shapes only");
+            if (s.kind == LRT_SHAPE_SPHERE) throw std::runtime_error("unsupported: an area emitter on a sphere (area emitters are supported on rectangles and triangle meshes)");
+            if (s.kind == LRT_SHAPE_RECTANGLE && s.n_faces < 1) bad("area emitter on a rectangle without faces");
+            if (s.kind == LRT_SHAPE_MESH) { MeshEmitterTable tab; mesh_emitter_table(d.positions, d.faces, s.first_face, s.n_faces, "shapes[" + std::to_string(E.shape) + "]", tab); }
         } else if (E.type != LRT_EMITTER_POINT) ++n_env;
         if (E.type == LRT_EMITTER_ENVMAP && (!E.data || E.width < 2 || E.height < 3)) bad("environment map without data or smaller than 2x3 pixels");
     }
@@ -294,6 +296,15 @@ lrt_status lrt_trace(lrt_scene *scene, const lrt_rays_soa *rays, const lrt_hits_
     LRT_TRY
         ensure_device(scene, -1);
         device_trace(scene->dev, rays, hits, n, any_hit);
+        return LRT_OK;
+    LRT_CATCH
+}
+
+lrt_status lrt_emitter_probe(lrt_scene *scene, const float *ref_p, const float *sample, uint32_t n, float *out, int device) {
+    if (!scene || ((!ref_p || !sample || !out) && n)) return fail(LRT_ERR_INVALID, "lrt_emitter_probe: null argument");
+    LRT_TRY
+        ensure_device(scene, device);
+        device_emitter_probe(scene->dev, ref_p, sample, n, out);
         return LRT_OK;
     LRT_CATCH
 }

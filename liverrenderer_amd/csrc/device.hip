@@ -64,7 +64,7 @@ struct DeviceScene {
     std::vector<DMedium> h_media; DMedium *d_media = nullptr;
     std::vector<DBioMedium> h_bio; DBioMedium *d_bio = nullptr;
     std::vector<DHetMedium> h_het; DHetMedium *d_het = nullptr; std::vector<float *> het_data; bool has_het = false, has_non_bio = false, need_mis = false, mis_alloc = false;
-    bool ext = false;                      // spheres or point emitters: the EXT kernel instances (ExtTracer, point-emitter sampling), wide records
+    bool ext = false;                      // spheres, point emitters or area emitters on meshes: the EXT kernel instances (ExtTracer, point- / mesh-emitter sampling), wide records
     bool has_area_emitter = false;         // decides the record layout: only an area emitter's pdf reads the last scatter position (kernels.h, store_state)
     bool prb_null = false;                 // prbvolpath.py:84-91 `handle_null_scattering`: a heterogeneous medium is attached to a shape
     DLdsInfo lds{}; bool use_lds = false; int n_cus = 256; int bvh_leaf = 4;
@@ -295,7 +295,10 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
     }
     sc.n_spheres = (uint32_t) spheres.size();
     sc.spheres = spheres.empty() ? nullptr : D->track(dev_upload(spheres.data(), spheres.size(), st));
-    for (uint32_t i = 0; i < d.n_emitters; ++i) if (d.emitters[i].type == LRT_EMITTER_POINT) D->ext = true;
+    for (uint32_t i = 0; i < d.n_emitters; ++i) {
+        const lrt_emitter_desc &e = d.emitters[i];
+        if (e.type == LRT_EMITTER_POINT || (e.type == LRT_EMITTER_AREA && e.shape >= 0 && (uint32_t) e.shape < d.n_shapes && d.shapes[e.shape].kind == LRT_SHAPE_MESH)) D->ext = true;
+    }
     if (!spheres.empty()) D->ext = true;
     HostBVH bvh;
     {
@@ -373,7 +376,7 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
             LRT_SMEM((k_render_prb<false, 1024, true, false, true>)); LRT_SMEM((k_render_prb<true, 1024, true, false, true>));
             LRT_SMEM((k_render_prb<false, 1024, true, true, true>)); LRT_SMEM((k_render_prb<true, 1024, true, true, true>));
             LRT_SMEM((k_trace_lds<true>)); LRT_SMEM((k_trace_lds<false>)); LRT_SMEM((k_aov<true, false>)); LRT_SMEM((k_aov<true, true>));
-            if (D->ext) {                              // spheres / point emitters: the EXT instances (kernels.h)
+            if (D->ext) {                              // spheres / point emitters / mesh emitters: the EXT instances (kernels.h)
 #define LRT_SMEM_EXT(I, BS) LRT_SMEM((k_render<I, BS, true, false, false, true>)); LRT_SMEM((k_render<I, BS, true, true, false, true>))
                 LRT_SMEM_EXT(LRT_INTEGRATOR_PATH, 1024); LRT_SMEM_EXT(LRT_INTEGRATOR_VOLPATH, 1024); LRT_SMEM_EXT(LRT_INTEGRATOR_BIOVOLPATH, 1024);
                 LRT_SMEM_EXT(LRT_INTEGRATOR_BIOVOLPATH06, 1024); LRT_SMEM_EXT(LRT_INTEGRATOR_VOLPATH_HET, LRT_WIDE_BLOCK);
@@ -492,14 +495,23 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
     upload_media(D.get(), d); sc.media = D->d_media; sc.bio = D->d_bio; sc.het = D->d_het;
     // ---- emitters
     std::vector<DEmitter> em(d.n_emitters); std::vector<float> env_rgbx, hier; bool env_interior_positive = false;
+    std::vector<DMeshEmitter> mesh_em(d.n_emitters); std::vector<float> mesh_tab;      // (all zero: no mesh emitter)
     for (uint32_t i = 0; i < d.n_emitters; ++i) {
         const lrt_emitter_desc &S = d.emitters[i]; DEmitter &o = em[i]; memset(&o, 0, sizeof(o));
         o.type = S.type; o.shape = S.shape; o.scale = S.scale; for (int k = 0; k < 3; ++k) o.radiance[k] = S.radiance[k];
         if (S.type == LRT_EMITTER_AREA) {
             D->has_area_emitter = true;
             const lrt_shape_desc &sd = d.shapes[S.shape];
-            if (sd.kind == LRT_SHAPE_SPHERE) throw std::runtime_error("unsupported: an area emitter on a sphere (area emitters are supported on rectangle shapes only)");
-            if (sd.kind != LRT_SHAPE_RECTANGLE) throw std::runtime_error("area emitters are supported on rectangle shapes only");
+            if (sd.kind == LRT_SHAPE_SPHERE) throw std::runtime_error("unsupported: an area emitter on a sphere (area emitters are supported on rectangles and triangle meshes)");
+            if (sd.kind == LRT_SHAPE_MESH) {                   // src/render/mesh.cpp:449-482: the area table and its CDF (host_scene.h)
+                MeshEmitterTable T; mesh_emitter_table(d.positions, d.faces, sd.first_face, sd.n_faces, "shapes[" + std::to_string(S.shape) + "]", T);
+                DMeshEmitter &M = mesh_em[i];
+                M.first_face = sd.first_face; M.n_faces = sd.n_faces; M.sum = T.sum; M.normalization = T.normalization;
+                M.has_normals = sd.has_normals; M.flip_normals = sd.flip_normals; M.mesh = 1;
+                M.pmf_offset = (uint32_t) mesh_tab.size(); mesh_tab.insert(mesh_tab.end(), T.pmf.begin(), T.pmf.end());
+                M.cdf_offset = (uint32_t) mesh_tab.size(); mesh_tab.insert(mesh_tab.end(), T.cdf.begin(), T.cdf.end());
+                continue;
+            }
             memcpy(o.to_world, sd.to_world, sizeof(float) * 12);
             auto xv = [&](float x, float y, float z, float *r) { const float *m = sd.to_world; for (int a = 0; a < 3; ++a) r[a] = fmaf(m[4 * a + 2], z, fmaf(m[4 * a + 1], y, m[4 * a] * x)); };
             float du[3], dv[3]; xv(2.f, 0.f, 0.f, du); xv(0.f, 2.f, 0.f, dv);
@@ -539,6 +551,8 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
     sc.nee_fast_reject = (d.n_emitters == 1 && !sc.has_null_bsdf && !D->has_het && !getenv("LRT_NO_NEE_REJECT") &&
                           (E.type == LRT_EMITTER_CONSTANT || (E.type == LRT_EMITTER_ENVMAP && env_interior_positive))) ? 1 : 0;
     sc.emitters = D->track(dev_upload(em.data(), em.size(), st));
+    sc.mesh_emitters = D->track(dev_upload(mesh_em.data(), mesh_em.size(), st));
+    sc.mesh_emitter_tab = D->track(dev_upload(mesh_tab.data(), mesh_tab.size(), st));
     sc.env_data = (const float4 *) D->track(dev_upload(env_rgbx.data(), env_rgbx.size(), st));
     sc.env_hier = D->track(dev_upload(hier.data(), hier.size(), st));
     build_camera(d, sc.cam, sc.film);
@@ -773,7 +787,7 @@ static void check_integrator_media(DeviceScene *D, int integrator) {
     if ((integrator == LRT_INTEGRATOR_BIOVOLPATH || integrator == LRT_INTEGRATOR_BIOVOLPATH06) && D->has_non_bio)
         throw std::runtime_error("NotImplementedError: sample_interaction (the bio integrators need liver / parenchyma / glissonCapsule media)");
     if (integrator == LRT_INTEGRATOR_PRBVOLPATH && D->ext)
-        throw std::runtime_error("unsupported: prbvolpath on a scene with sphere shapes or point emitters (its adjoint is built for triangles and area / infinite emitters)");
+        throw std::runtime_error("unsupported: prbvolpath on a scene with sphere shapes, point emitters or area emitters on meshes (its adjoint is built for triangles and rectangle / infinite emitters)");
     if (integrator == LRT_INTEGRATOR_VOLPATHMIS) D->need_mis = true;          // its wider path record is allocated on first use
 }
 
@@ -1385,6 +1399,22 @@ void device_render_backward_multi(std::vector<DeviceScene *> &devs, MultiContext
     for (auto &x : st) { total.n_samples += x.n_samples; total.n_iter += x.n_iter; total.n_shadow += x.n_shadow; total.n_launches += x.n_launches; total.n_records += x.n_records;
                          total.kernel_ms = std::max(total.kernel_ms, x.kernel_ms); total.total_ms = std::max(total.total_ms, x.total_ms); total.lds_resident = x.lds_resident; }
     stats = total;
+}
+
+// Test hook (include/liverrt.h lrt_emitter_probe): k_emitter_probe (kernels.h) on the scene's device image
+void device_emitter_probe(DeviceScene *D, const float *ref_p, const float *sample, uint32_t n, float *out) {
+    HIP_CHECK(hipSetDevice(D->device));
+    if (!n) return;
+    hipStream_t st = D->stream;
+    struct Tmp { float *p = nullptr; ~Tmp() { if (p) (void) hipFree(p); } } dr, ds, dout;
+    HIP_CHECK(hipMalloc((void **) &dr.p, (size_t) n * 3 * 4)); HIP_CHECK(hipMalloc((void **) &ds.p, (size_t) n * 2 * 4));
+    HIP_CHECK(hipMalloc((void **) &dout.p, (size_t) n * LRT_PROBE_FLOATS * 4));
+    HIP_CHECK(hipMemcpyAsync(dr.p, ref_p, (size_t) n * 3 * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(ds.p, sample, (size_t) n * 2 * 4, hipMemcpyHostToDevice, st));
+    k_emitter_probe<<<(n + LRT_BLOCK - 1) / LRT_BLOCK, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, dr.p, ds.p, n, dout.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * LRT_PROBE_FLOATS * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
 }
 
 // Test hook (include/liverrt.h lrt_math_eval): the transcendental kernels of csrc/dmath.h evaluated on the device, one lane per value.

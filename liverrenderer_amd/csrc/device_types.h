@@ -70,6 +70,16 @@ struct DSphere {
     float pad[2];
 };
 
+// area emitters on triangle meshes (src/render/mesh.cpp:449-482,861-935): one entry per emitter (DScene::mesh_emitters, indexed like
+// DScene::emitters; `mesh` is 0 for every other emitter).  pmf / cdf: the face areas and their inclusive float32 prefix sum, n_faces
+// floats each at pmf_offset / cdf_offset of DScene::mesh_emitter_tab.
+struct DMeshEmitter {
+    uint32_t first_face, n_faces, pmf_offset, cdf_offset;
+    float sum, normalization;            // cdf[n_faces - 1] and 1 / sum (DiscreteDistribution::m_sum, m_normalization)
+    int32_t has_normals, flip_normals;
+    int32_t mesh, pad[3];
+};
+
 #define LRT_MAX_HIER_LEVELS 16
 
 struct DCamera {
@@ -136,6 +146,8 @@ struct DScene {
     DDistGrid grid;
     const DSphere *spheres;          // sphere k is primitive n_faces + k
     uint32_t n_spheres, pad_sph;
+    const DMeshEmitter *mesh_emitters;   // n_emitters entries (the EXT instances only read them)
+    const float *mesh_emitter_tab;       // every mesh emitter's pmf and cdf
 };
 
 // The scene record lives in device memory and is read through the CONSTANT address space: every `sc.field` is a scalar

@@ -109,7 +109,7 @@ DEV Hit trace(SceneRef sc, const Ray &r, int *__restrict__ stack /* &lds[threadI
 
 // Ray-query back-ends the integrator loops are templated on.
 struct GlobalTracer {                      // BVH in global memory (any scene size), 32-bit stack entries in LDS
-    static constexpr bool kExt = false;    // (ExtTracer below: spheres and point emitters)
+    static constexpr bool kExt = false;    // (ExtTracer below: spheres, point emitters and area emitters on meshes)
     SceneRef sc; int *stack;
     DEV Hit closest(const Ray &r) const { return trace<false>(sc, r, stack); }
     DEV Hit any(const Ray &r) const { return trace<true>(sc, r, stack); }
@@ -480,7 +480,7 @@ DEV SI compute_si_sphere(SceneRef sc, const Ray &r, const Hit &h) {
     return si;
 }
 
-// The tracer of the EXT kernel instances (scenes with spheres or point emitters): a triangle tracer plus the spheres.  The
+// The tracer of the EXT kernel instances (scenes with spheres, point emitters or mesh area emitters): a triangle tracer plus the spheres.  The
 // other instances keep the plain tracers, so triangle-only scenes run the code they ran before.
 template <class BASE> struct ExtTracer {
     static constexpr bool kExt = true;
@@ -780,9 +780,53 @@ DEV V3 emitter_eval_env(SceneRef sc, V3 dir_world) {
     return env_eval_uv(sc, uu, vv);
 }
 
+// ------------------------------------------------------- mesh area emitters
+// DiscreteDistribution::sample (include/mitsuba/core/distr_1d.h:117-135, the JIT predicate) inside Dr.Jit's binary_search, restated
+// from Dr.Jit's public header (the reference tree leaves ext/drjit empty): log2i(end - start) + 1 trips over [0, n - 1], each
+// middle = (start + end) >> 1, start = pred ? min(middle + 1, end) : start, end = pred ? end : middle.  The trip count depends on n
+// alone, so the lanes of a wave that sample one emitter run the same loop.
+DEV uint32_t mesh_emitter_search(const float *__restrict__ cdf, uint32_t n, float sum, float value) {
+    const float s = value * sum;
+    uint32_t start = 0u, end = n - 1u;
+    const uint32_t trips = n > 1u ? 32u - (uint32_t) __builtin_clz(n - 1u) : 0u;
+    for (uint32_t i = 0; i < trips; ++i) {
+        const uint32_t middle = (start + end) >> 1;
+        const float c = cdf[middle];
+        const bool pred = (c < s || c == 0.f) && c != sum;
+        start = pred ? min(middle + 1u, end) : start;
+        end = pred ? end : middle;
+    }
+    return start;
+}
+// Mesh::sample_position (src/render/mesh.cpp:861-935): `sy` picks the face (DiscreteDistribution::sample_reuse, distr_1d.h:174-182)
+// and is replaced by its re-scaled value, then warp::square_to_uniform_triangle (include/mitsuba/core/warp.h:153-156).
+DEV void mesh_emitter_position(SceneRef sc, const DMeshEmitter &M, float sx, float sy, V3 *p_out, V3 *n_out) {
+    const float *tab_f = sc.mesh_emitter_tab;
+    const uint32_t idx = mesh_emitter_search(tab_f + M.cdf_offset, M.n_faces, M.sum, sy);
+    const float pmf = tab_f[M.pmf_offset + idx] * M.normalization;
+    const float cdf = idx > 0u ? tab_f[M.cdf_offset + idx - 1u] * M.normalization : 0.f;
+    sy = (sy - cdf) / pmf;
+    const uint32_t f = M.first_face + idx;
+    const uint32_t i0 = sc.faces[3 * f], i1 = sc.faces[3 * f + 1], i2 = sc.faces[3 * f + 2];
+    const V3 p0(sc.positions[3 * i0], sc.positions[3 * i0 + 1], sc.positions[3 * i0 + 2]);
+    const V3 p1(sc.positions[3 * i1], sc.positions[3 * i1 + 1], sc.positions[3 * i1 + 2]);
+    const V3 p2(sc.positions[3 * i2], sc.positions[3 * i2 + 1], sc.positions[3 * i2 + 2]);
+    const V3 e0 = p1 - p0, e1 = p2 - p0;
+    const float t = safe_sqrt(1.f - sx), bx = 1.f - t, by = t * sy;
+    *p_out = V3(fma_(e0.x, bx, fma_(e1.x, by, p0.x)), fma_(e0.y, bx, fma_(e1.y, by, p0.y)), fma_(e0.z, bx, fma_(e1.z, by, p0.z)));
+    V3 n;
+    if (M.has_normals) {
+        const float4 a0 = sc.vattr[2 * (size_t) i0], a1 = sc.vattr[2 * (size_t) i1], a2 = sc.vattr[2 * (size_t) i2];
+        const float b0 = 1.f - bx - by;
+        n = V3(fma_(a0.x, b0, fma_(a1.x, bx, a2.x * by)), fma_(a0.y, b0, fma_(a1.y, bx, a2.y * by)), fma_(a0.z, b0, fma_(a1.z, bx, a2.z * by)));
+    } else n = cross(e0, e1);
+    n = normalize(n);
+    *n_out = M.flip_normals ? -n : n;
+}
+
 // Scene::sample_emitter_direction without visibility test (src/render/scene.cpp:333-383)
-// POINT: the scene may hold point emitters (the EXT kernel instances only)
-template <bool POINT = false>
+// EXT: the scene may hold point emitters or area emitters on meshes (the EXT kernel instances only)
+template <bool EXT = false>
 DEV V3 sample_emitter_direction(SceneRef sc, V3 ref_p, float sx, float sy, DirSample *ds) {
     uint32_t ne = sc.n_emitters;
     ds->p = V3(0.f); ds->n = V3(0.f); ds->d = V3(0.f); ds->pdf = 0.f; ds->dist = 0.f; ds->delta = false; ds->emitter = -1;
@@ -797,10 +841,16 @@ DEV V3 sample_emitter_direction(SceneRef sc, V3 ref_p, float sx, float sy, DirSa
     ds->emitter = (int) index;
     V3 spec(0.f);
     if (E.type == LRT_EMITTER_AREA) {
-        // src/shapes/rectangle.cpp:181-199, src/render/shape.cpp:343-361, src/emitters/area.cpp sample_direction
-        ds->p = xform_point12(E.to_world, V3(fma_(sx, 2.f, -1.f), fma_(sy, 2.f, -1.f), 0.f));
-        ds->n = V3(E.n[0], E.n[1], E.n[2]);
-        ds->pdf = E.inv_area;
+        // src/shapes/rectangle.cpp:181-199 (a mesh: mesh.cpp:861-935), src/render/shape.cpp:343-361, src/emitters/area.cpp:118-168 sample_direction
+        const DMeshEmitter M = EXT ? tab(sc.mesh_emitters, index) : DMeshEmitter{};
+        if (EXT && M.mesh) {
+            mesh_emitter_position(sc, M, sx, sy, &ds->p, &ds->n);
+            ds->pdf = M.normalization;
+        } else {
+            ds->p = xform_point12(E.to_world, V3(fma_(sx, 2.f, -1.f), fma_(sy, 2.f, -1.f), 0.f));
+            ds->n = V3(E.n[0], E.n[1], E.n[2]);
+            ds->pdf = E.inv_area;
+        }
         ds->d = ds->p - ref_p;
         float dist2 = squared_norm(ds->d);
         ds->dist = __builtin_sqrtf(dist2);
@@ -810,7 +860,7 @@ DEV V3 sample_emitter_direction(SceneRef sc, V3 ref_p, float sx, float sy, DirSa
         bool active = dot(ds->d, ds->n) < 0.f && ds->pdf != 0.f;
         V3 rad(E.radiance[0], E.radiance[1], E.radiance[2]);
         spec = active ? rad / ds->pdf : V3(0.f);
-    } else if (POINT && E.type == LRT_EMITTER_POINT) {   // src/emitters/point.cpp:119-148: a delta position, pdf 1, no surface reaches it
+    } else if (EXT && E.type == LRT_EMITTER_POINT) {   // src/emitters/point.cpp:119-148: a delta position, pdf 1, no surface reaches it
         ds->p = V3(E.to_world[3], E.to_world[7], E.to_world[11]);
         ds->pdf = 1.f; ds->delta = true;
         ds->d = ds->p - ref_p;
@@ -850,7 +900,10 @@ DEV V3 sample_emitter_direction(SceneRef sc, V3 ref_p, float sx, float sy, DirSa
 }
 
 // DirectionSample(scene, si, ref) + Scene::pdf_emitter_direction
-// (include/mitsuba/render/records.h:173-180, src/render/scene.cpp:395-406)
+// (include/mitsuba/render/records.h:76-78,173-180, src/render/scene.cpp:395-406, src/render/shape.cpp:363-374, area.cpp:170-197)
+// The record's normal is si.sh_frame.n, the interpolated shading normal.  A rectangle's equals si.n; on a mesh with vertex normals
+// it does not, and the EXT instances read it there (a mesh emitter samples with the interpolated normal too, mesh.cpp:914-925).
+template <bool EXT = false>
 DEV float pdf_emitter_direction(SceneRef sc, V3 ref_p, const SI &si, int emitter) {
     V3 rel = si.p - ref_p;
     float dist = norm(rel);
@@ -859,10 +912,12 @@ DEV float pdf_emitter_direction(SceneRef sc, V3 ref_p, const SI &si, int emitter
     const DEmitter &E = sc.emitters[emitter];
     float value;
     if (E.type == LRT_EMITTER_AREA) {
-        float dp = dot(d, si.n);
+        float pos_pdf = E.inv_area; V3 n = si.n;
+        if (EXT) { const DMeshEmitter M = tab(sc.mesh_emitters, (uint32_t) emitter); if (M.mesh) { pos_pdf = M.normalization; n = si.sh.n; } }
+        float dp = dot(d, n);
         if (!(dp < 0.f)) return 0.f;
         float adp = __builtin_fabsf(dp);
-        value = E.inv_area * (adp != 0.f ? (dist * dist) / adp : 0.f);
+        value = pos_pdf * (adp != 0.f ? (dist * dist) / adp : 0.f);
     } else if (E.type == LRT_EMITTER_ENVMAP) {          // src/emitters/envmap.cpp:461-475
         EnvRef EV = sc.env;
         V3 dl = xform_vec9(EV.to_local, d);

@@ -31,6 +31,13 @@ struct SceneStorage {
     void copy_from(const lrt_scene_desc &d);
 };
 
+// Sampling table of an area emitter on a triangle mesh (loader.cpp): face areas .5 |(p1 - p0) x (p2 - p0)| in float32
+// (src/render/mesh.cpp:449-482 build_pmf) and their inclusive prefix sum, summed left to right in float32
+// (include/mitsuba/core/distr_1d.h:219-234 compute_cdf).  `positions` / `faces`: the scene's arrays (faces hold vertex indices).
+// Throws for a mesh without faces, and for one whose total area is zero (named `name` in the message).
+struct MeshEmitterTable { std::vector<float> pmf, cdf; float sum = 0.f, normalization = 0.f; };
+void mesh_emitter_table(const float *positions, const uint32_t *faces, uint32_t first_face, uint32_t n_faces, const std::string &name, MeshEmitterTable &out);
+
 // XML -> storage (loader.cpp).  Throws std::runtime_error.
 void load_scene_xml(const std::string &xml_text, const std::string &base_dir,
                     const std::vector<std::pair<std::string, std::string>> &defines, SceneStorage &out);

@@ -573,7 +573,7 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
         bool active_e = emitter >= 0 && !(depth == 0 && rp.hide_emitters);
         if (active_e) {
             float emitter_pdf = 1.f;
-            if (!count_direct) emitter_pdf = pdf_emitter_direction(sc, s.lp, si, emitter);
+            if (!count_direct) emitter_pdf = pdf_emitter_direction<TR::kExt>(sc, s.lp, si, emitter);
             V3 emitted = emitter_eval(sc, emitter, si);
             V3 contrib = count_direct ? throughput * emitted : throughput * mis_weight(s.last_pdf, emitter_pdf) * emitted;
             result = result + contrib;
@@ -673,7 +673,7 @@ DEV bool path_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const TR 
     int emitter = si_emitter(sc, si);
     if (emitter >= 0) {
         float em_pdf = 0.f;
-        if (!prev_bsdf_delta) em_pdf = pdf_emitter_direction(sc, s.lp, si, emitter);
+        if (!prev_bsdf_delta) em_pdf = pdf_emitter_direction<TR::kExt>(sc, s.lp, si, emitter);
         float mis_bsdf = mis_weight(s.last_pdf, em_pdf);
         V3 em = (s.last_pdf > 0.f) ? emitter_eval(sc, emitter, si) : V3(0.f);
         em = em * mis_bsdf;
@@ -797,7 +797,8 @@ DEV void retire_and_compact_wave(SceneRef sc, RpRef rp, bool had_path, bool aliv
 // 4 waves per SIMD (128 VGPRs): one 1024-thread workgroup per CU, or four 256-thread ones.  BLOCK = 512 (one workgroup per CU, 2 waves per
 // SIMD, 256 VGPRs): the wide-record integrators (volpathmis: 18 weights per path), which at 128 registers spill 430 B per lane
 // COMPACT: 80-byte records (store_state): the host launches these instances for scenes without area emitters (DRenderParams::compact)
-// EXT: the scene holds spheres or point emitters (ExtTracer, point-emitter sampling); the triangle-only instances are unchanged
+// EXT: the scene holds spheres, point emitters or area emitters on meshes (ExtTracer, point- and mesh-emitter sampling, the mesh emitter's
+// pdf on the shading normal); the instances for triangles with rectangle / infinite emitters are unchanged
 template <int INTEGRATOR, int BLOCK, bool LDS_BVH, bool LD, bool COMPACT = false, bool EXT = false>
 __global__ void __launch_bounds__(BLOCK, BLOCK == 512 ? 2 : (BLOCK == 768 ? 3 : 4))
 k_render(ScenePtr scp, LaunchPtr lp) {
@@ -1147,5 +1148,32 @@ k_trace_lds(ScenePtr scp, DLdsInfo li, const float *ox, const float *oy, const f
     }
 }
 
+// Test hook (lrt_emitter_probe): the EXT instances' Scene::sample_emitter_direction for one reference point and sample per lane, then a
+// closest-hit query from the reference point along the sampled direction and what the integrators evaluate at its hit
+// (pdf_emitter_direction, emitter_eval).  No ray offset: the tests put the reference points in free space.
+__global__ void __launch_bounds__(LRT_BLOCK)
+k_emitter_probe(ScenePtr scp, const float *__restrict__ ref_p, const float *__restrict__ smp, uint32_t n, float *__restrict__ out) {
+    SceneRef sc = *scp;
+    __shared__ int s_stack[LRT_STACK * LRT_BLOCK];
+    const uint32_t i = blockIdx.x * LRT_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const V3 ref(ref_p[3 * (size_t) i], ref_p[3 * (size_t) i + 1], ref_p[3 * (size_t) i + 2]);
+    DirSample ds; const V3 w = sample_emitter_direction<true>(sc, ref, smp[2 * (size_t) i], smp[2 * (size_t) i + 1], &ds);
+    float *o = out + (size_t) LRT_PROBE_FLOATS * i;
+    o[0] = ds.p.x; o[1] = ds.p.y; o[2] = ds.p.z; o[3] = ds.n.x; o[4] = ds.n.y; o[5] = ds.n.z; o[6] = ds.d.x; o[7] = ds.d.y; o[8] = ds.d.z;
+    o[9] = ds.dist; o[10] = ds.pdf; o[11] = w.x; o[12] = w.y; o[13] = w.z; o[14] = (float) ds.emitter;
+    float shape = -1.f, pdf = 0.f; V3 le(0.f);
+    if (ds.pdf > 0.f) {
+        const GlobalTracer tg{ sc, s_stack + threadIdx.x };
+        const ExtTracer<GlobalTracer> tr{ tg, sc };
+        Ray r; r.o = ref; r.d = ds.d; r.maxt = kLargest;
+        const Hit h = tr.closest(r);
+        const SI si = tr.surface(sc, r, h);
+        if (si.valid) shape = (float) si.shape;
+        const int e = si_emitter(sc, si);
+        if (e >= 0) { pdf = pdf_emitter_direction<true>(sc, ref, si, e); le = emitter_eval(sc, e, si); }
+    }
+    o[15] = shape; o[16] = pdf; o[17] = le.x; o[18] = le.y; o[19] = le.z;
+}
 
 } // namespace lrt

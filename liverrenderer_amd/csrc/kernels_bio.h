@@ -265,7 +265,7 @@ DEV bool biovolpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, con
         bool active_e = emitter >= 0 && !(depth == 0 && rp.hide_emitters);
         if (active_e) {
             float emitter_pdf = 1.f;
-            if (!count_direct) emitter_pdf = pdf_emitter_direction(sc, s.lp, si, emitter);
+            if (!count_direct) emitter_pdf = pdf_emitter_direction<TR::kExt>(sc, s.lp, si, emitter);
             V3 emitted = emitter_eval(sc, emitter, si);
             V3 contrib = count_direct ? throughput * emitted : throughput * mis_weight(s.last_pdf, emitter_pdf) * emitted;
             result = result + contrib;

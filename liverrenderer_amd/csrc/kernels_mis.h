@@ -259,7 +259,7 @@ DEV bool volpathmis_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, con
         int emitter = si_emitter(sc, si);
         bool active_e = emitter >= 0 && !(depth == 0 && rp.hide_emitters);
         if (active_e) {                                                 // :384-389: the weight update is masked by active_e alone
-            float emitter_pdf = pdf_emitter_direction(sc, s.lp, si, emitter);
+            float emitter_pdf = pdf_emitter_direction<TR::kExt>(sc, s.lp, si, emitter);
             mis_update(p_over_f_nee, V3(emitter_pdf), V3(1.f), channel, true);
             V3 emitted = emitter_eval(sc, emitter, si);
             V3 contrib = count_direct ? mis_weight1(p_over_f) * emitted : mis_weight2(p_over_f, p_over_f_nee) * emitted;

@@ -14,6 +14,7 @@
 // (src/core/plugin.cpp:96-139), and the fork's SphereLiverPoint scenes, written on a case-insensitive file system, say
 // "Dielectric".  A medium child of a shape named neither "interior" nor "exterior" is ignored, as src/render/shape.cpp:40-49
 // ignores it.  A sphere is one shape without faces (lrt_shape_desc); the point emitter keeps its position in to_world.
+// An area emitter may be the child of a rectangle or of any triangle mesh (obj, cube); not of a sphere.
 #include "host_scene.h"
 #include "xml.h"
 #include "image_io.h"
@@ -599,9 +600,12 @@ struct Loader {
             }
             else if (ch->tag == "emitter") {
                 if (ch->type != "area") fail("only area emitters can be attached to shapes");
-                if (sd.kind == LRT_SHAPE_SPHERE) fail("unsupported: an area emitter on a sphere (area emitters are supported on rectangle shapes only)");
-                if (sd.kind != LRT_SHAPE_RECTANGLE) fail("area emitters are supported on rectangle shapes only");
+                if (sd.kind == LRT_SHAPE_SPHERE) fail("unsupported: an area emitter on a sphere (area emitters are supported on rectangles and triangle meshes)");
                 if (has(*ch, "to_world")) fail("Found a 'to_world' transformation -- this is not allowed. The area light inherits this transformation from its parent shape.");
+                if (sd.kind == LRT_SHAPE_MESH) {        // the sampling table is built again with the device scene; here it only validates the mesh
+                    MeshEmitterTable tab;
+                    mesh_emitter_table(S.positions.data(), S.faces.data(), sd.first_face, sd.n_faces, o->id.empty() ? o->type : o->id, tab);
+                }
                 lrt_emitter_desc E{}; E.type = LRT_EMITTER_AREA; get_rgb(*ch, "radiance", 1.f, E.radiance); E.shape = (int) shape_ix; E.scale = 1.f;
                 S.emitters.push_back(E); S.emdata.emplace_back(); sd.emitter = (int) S.emitters.size() - 1;
             } else fail("unsupported child <" + ch->tag + "> of a shape");
@@ -830,17 +834,36 @@ struct Loader {
         }
         if (!have_sensor) fail("the scene has no sensor");
         for (auto &o : objs) if (o->tag == "integrator" && o->type == "aov") make_integrator(o);
-        bool ext = false;                       // spheres / point emitters: prbvolpath's adjoint is built for triangles and area / infinite emitters
+        bool ext = false;                       // spheres / point / mesh emitters: prbvolpath's adjoint is built for triangles and rectangle / infinite emitters
         for (auto &sh : S.shapes) ext = ext || sh.kind == LRT_SHAPE_SPHERE;
-        for (auto &e : S.emitters) ext = ext || e.type == LRT_EMITTER_POINT;
+        for (auto &e : S.emitters) ext = ext || e.type == LRT_EMITTER_POINT || (e.type == LRT_EMITTER_AREA && S.shapes[e.shape].kind == LRT_SHAPE_MESH);
         bool prb = S.desc.integrator.type == LRT_INTEGRATOR_PRBVOLPATH;
         for (int k = 0; S.has_aov && k < S.aov.n_integrators; ++k) prb = prb || S.aov.integrators[k].type == LRT_INTEGRATOR_PRBVOLPATH;
-        if (ext && prb) fail("unsupported: prbvolpath on a scene with sphere shapes or point emitters");
+        if (ext && prb) fail("unsupported: prbvolpath on a scene with sphere shapes, point emitters or area emitters on meshes");
         S.fix_pointers();
     }
 };
 
 } // namespace
+
+void mesh_emitter_table(const float *positions, const uint32_t *faces, uint32_t first_face, uint32_t n_faces, const std::string &name, MeshEmitterTable &out) {
+    if (n_faces == 0) throw std::runtime_error("Cannot create sampling table for an empty mesh: " + name);
+    out.pmf.resize(n_faces); out.cdf.resize(n_faces);
+    float acc = 0.f;
+    for (uint32_t i = 0; i < n_faces; ++i) {
+        const uint32_t *f = faces + 3 * ((size_t) first_face + i);
+        const float *p0 = positions + 3 * (size_t) f[0], *p1 = positions + 3 * (size_t) f[1], *p2 = positions + 3 * (size_t) f[2];
+        const float a[3] = { p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2] }, b[3] = { p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2] };
+        // Dr.Jit's cross (fmsub) and dot (fmadd chain from x), as the device's dmath.h
+        const float cx = fmaf(a[1], b[2], -(a[2] * b[1])), cy = fmaf(a[2], b[0], -(a[0] * b[2])), cz = fmaf(a[0], b[1], -(a[1] * b[0]));
+        out.pmf[i] = .5f * sqrtf(fmaf(cz, cz, fmaf(cy, cy, cx * cx)));
+        acc += out.pmf[i]; out.cdf[i] = acc;          // sequential float32 scan
+    }
+    out.sum = out.cdf[n_faces - 1]; out.normalization = 1.f / out.sum;
+    // The reference's release build accepts a zero total and samples with infinite pdfs; here that is an error.
+    if (!(out.sum > 0.f) || !std::isfinite(out.sum))
+        throw std::runtime_error("area emitter on shape \"" + name + "\": the mesh has no surface area to sample (total area " + std::to_string(out.sum) + ")");
+}
 
 void load_scene_xml(const std::string &xml_text, const std::string &base_dir,
                     const std::vector<std::pair<std::string, std::string>> &defines, SceneStorage &out) {
