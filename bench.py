@@ -21,6 +21,11 @@ film all-reduce when N > 1).  Default workload (`--config c3`): BASELINE config 
 For N > 1 the SAME image is sharded by 32x32 pixel tiles over the ranks (strong scaling) and the per-rank raw films are
 summed with one all-reduce before develop.  Prints ONE JSON line on rank 0 (contract: see the task statement).
 
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` if asked and prints the line: `value`, `ms_per_step` and the
+`roofline` of the timed launches.  `--full` adds what takes runs of its own (single GPU, forward integrators): `host_visible` (the same
+renders into host memory), `hg_phase` (C3 only: the c3hg workload timed beside it), `cpu_baseline` (the oracle's scalar renderer built
+for the host CPU) and `rmse_vs_oracle`.  `--main-only` and `--no-cpu-baseline` drop legs of a `--full` run.
+
 `--dump-outputs DIR` writes what the last timed step computed (image + raw film, or the PRB gradients) as DIR/<name>.npy once the
 clock has stopped.  Step k renders with seed k, so the same arguments give the same inputs on every run: two builds can be compared
 output for output (to float-atomic order in the film, see rmse_vs_oracle).
@@ -84,15 +89,17 @@ def parse():
     p.add_argument("--height", type=int, default=0)
     p.add_argument("--scene", default=None, help="override the config's scene file")
     p.add_argument("--integrator", default=None, help="override the config's integrator")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--main-only", action="store_true", help="only the timed steps of the named configuration: no host_visible / hg_phase / cpu_baseline legs (profiling: every dispatch of the render kernel then belongs to the workload)")
+    p.add_argument("--full", action="store_true", help="after the headline figure, also run the host_visible / hg_phase / cpu_baseline (+ rmse_vs_oracle) legs")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline / rmse_vs_oracle leg")
+    p.add_argument("--main-only", action="store_true", help="only the timed steps of the named configuration, even with --full: no host_visible / hg_phase / cpu_baseline legs (profiling: every dispatch of the render kernel then belongs to the workload)")
     p.add_argument("--backend", default="nccl", help="process-group backend; gloo allows a multi-rank rehearsal on a single GPU")
-    p.add_argument("--cpu-spp", type=int, default=0, help="spp of the bounded CPU-baseline sample (0: calibrate to ~15 s)")
+    p.add_argument("--cpu-spp", type=int, default=0, help="with --full: spp of the bounded CPU-baseline sample (0: calibrate to ~15 s)")
     p.add_argument("--dump-outputs", metavar="DIR", default=None,
                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     a = p.parse_args()
     if a.steps < 1:
         p.error("--steps must be at least 1")
+    a.extra_legs = a.full and not a.main_only
     return a
 
 
@@ -329,7 +336,7 @@ def main():
         out["vs_baseline"] = round(value / cfg["published_msamples"], 2)
         out["config"]["published"] = {"value": cfg["published_msamples"], "unit": "Msamples/s", "source": "scenes/Liver-MultiMesh/mitsuba3/time.txt (BASELINE.md), GPU unstated"}
 
-    if rank == 0 and world == 1 and not backward and not a.main_only:
+    if rank == 0 and world == 1 and not backward and a.extra_legs:
         # SURVEY.md 8d's form of the metric: lrt_render entry to the developed image AND raw film in host memory (PCIe included).
         # Reported beside `value`, never as it: the bench contract takes `value` with everything resident in HBM.
         scene.render(spp=spp, seed=77, return_raw=True)
@@ -339,9 +346,9 @@ def main():
         out["host_visible"] = {"value": round(n_samples / hdt / 1e6, 3), "unit": "Msamples/s", "ms_per_step": round(hdt * 1e3, 3),
                                "note": "lrt_render with host output buffers: developed image + raw film copied over PCIe inside the call (SURVEY.md 8d t_render); reported beside `value`, never as it"}
 
-    if rank == 0 and world == 1 and a.config == "c3" and not (a.scene or a.integrator) and not a.main_only:
-        # BASELINE.json config 3 is worded "homogeneous medium + HG phase"; the scene file says isotropic.  The driver's
-        # default line carries both: `value` on the file as committed, `hg_phase` on the same workload with the phase function set to
+    if rank == 0 and world == 1 and a.config == "c3" and not (a.scene or a.integrator) and a.extra_legs:
+        # BASELINE.json config 3 is worded "homogeneous medium + HG phase"; the scene file says isotropic.  A --full
+        # line carries both: `value` on the file as committed, `hg_phase` on the same workload with the phase function set to
         # HG, g = 0.7, through the parameter interface (mi.traverse) - same size, same timed region, same number of steps.
         hg = load(mi, CONFIGS["c3hg"], spp, w, h, integrator_override)
         dev = torch.device("cuda", local_rank)
@@ -359,7 +366,7 @@ def main():
                            "roofline_frac": round(hb / (hk * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if hk > 0 else None,
                            "iterations_per_sample": hi / (n_samples * a.steps), "records_per_sample": hr / (n_samples * a.steps)}
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not backward and not a.main_only:
+    if rank == 0 and world == 1 and not a.no_cpu_baseline and not backward and a.extra_legs:
         # ---- CPU baseline (reported, not a target): the oracle's scalar_rgb restatement - SamplingIntegrator::render's scalar branch,
         # 32x32 blocks in Morton order, one std::thread per granted core (oracle/orc_render.cpp orc_render_scalar; SURVEY.md 8d,
         # BASELINE.md section 3.5) - on a bounded sample of the same workload: same scene and resolution at a reduced spp.

@@ -21,8 +21,27 @@ def last_json(out):
     return json.loads(lines[0])
 
 
+EXTRA_LEGS = ("host_visible", "hg_phase", "cpu_baseline", "rmse_vs_oracle")
+
+
+def test_bench_line_plain_n1():
+    """a plain run is the headline figure alone: the contract keys and the roofline of the timed launches, none of the legs of --full"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--spp", "16"],
+                       capture_output=True, text=True, cwd=ROOT, env=ENV, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = last_json(r.stdout)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
+        assert k in j, k
+    assert j["metric"] == "Msamples/s" and j["unit"] == "Msamples/s" and j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1
+    assert j["higher_is_better"] is True and j["dtype"] == "f32" and j["config"]["spp"] == 16
+    assert abs(j["value"] - j["config"]["samples_per_step"] / (j["ms_per_step"] * 1e-3) / 1e6) < 1e-2 * j["value"]
+    assert j["roofline"]["kernel"].startswith("lrt::k_render<1, 1024, true") and j["roofline"]["avg_launch_ms"] > 0
+    assert not any(k in j for k in EXTRA_LEGS), [k for k in EXTRA_LEGS if k in j]
+
+
 def test_bench_line_n1():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--spp", "16", "--cpu-spp", "1"],
+    """--full: the headline figure and, beside it, the legs that take runs of their own"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--spp", "16", "--cpu-spp", "1", "--full"],
                        capture_output=True, text=True, cwd=ROOT, env=ENV, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     j = last_json(r.stdout)
@@ -38,7 +57,7 @@ def test_bench_line_n1():
     cb = j["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "spp" in cb["sample"] and "orc_render_scalar" in cb["build"]
     assert j["rmse_vs_oracle"]["value"] <= j["rmse_vs_oracle"]["tolerance"]
-    hg = j["hg_phase"]                                            # BASELINE.json config 3 as worded (HG phase) rides in the default line
+    hg = j["hg_phase"]                                            # BASELINE.json config 3 as worded (HG phase) rides in the --full line
     assert hg["g"] == 0.7 and hg["value"] > 0 and "HG phase" in hg["workload"]
     assert j["host_visible"]["value"] > 0 and j["host_visible"]["value"] <= j["value"] * 1.05
 
