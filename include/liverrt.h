@@ -235,6 +235,11 @@ typedef struct {
     double   total_ms;        /* whole lrt_render device time (HIP events)         */
     uint64_t lds_resident;    /* 1: the kernels ran on the LDS-resident BVH image (1024-thread workgroups);
                                  0: the mesh did not fit, BVH in global memory (256-thread workgroups)  [v103] */
+    uint64_t record_bytes;    /* bytes per queued path record of the forward render kernel's layout: 64 (volpath where
+                                 only a path's last trip adds radiance), 80 / 88 (compact), 88 / 96 / 104 / 168 (wide);
+                                 0 for the PRB adjoint  [v108] */
+    uint64_t n_closed_guard;  /* 64-byte records: trips that broke the layout's premise (nonzero radiance on a path that
+                                 goes on, an emitter hit that needs its MIS weight); the render then fails  [v108] */
 } lrt_render_stats;
 
 typedef struct {
@@ -249,7 +254,7 @@ typedef struct {
 typedef struct lrt_scene lrt_scene;
 
 LRT_API const char *lrt_last_error(void);
-LRT_API int         lrt_version(void);   /* 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
+LRT_API int         lrt_version(void);   /* 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
 
 LRT_API lrt_status lrt_scene_load_xml(const char *path, const char *const *defines,
                                       int n_defines, lrt_scene **out);

@@ -356,7 +356,9 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
 #ifndef LRT_DEV_BLOCK
 #define LRT_DEV_BLOCK 1024
 #endif
-            LRT_SMEM((k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD>)); LRT_SMEM((k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD, true>)); LRT_SMEM((k_trace_lds<true>)); LRT_SMEM((k_trace_lds<false>)); LRT_SMEM((k_aov<true, false>)); LRT_SMEM((k_aov<true, true>));
+            // the 64-byte-record instance stands in for "the C3 kernel" of a volpath developer build (any other integrator: its compact instance again)
+#define LRT_DEV_CLOSED (LRT_DEV_INTEGRATOR == LRT_INTEGRATOR_VOLPATH ? LRT_INTEGRATOR_VOLPATH_CLOSED : LRT_DEV_INTEGRATOR)
+            LRT_SMEM((k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD>)); LRT_SMEM((k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD, true>)); LRT_SMEM((k_render<LRT_DEV_CLOSED, LRT_DEV_BLOCK, true, LRT_DEV_LD, true>)); LRT_SMEM((k_trace_lds<true>)); LRT_SMEM((k_trace_lds<false>)); LRT_SMEM((k_aov<true, false>)); LRT_SMEM((k_aov<true, true>));
 #else
             LRT_SMEM((k_render<LRT_INTEGRATOR_PATH, 1024, true, false>)); LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH, 1024, true, false>));
             LRT_SMEM((k_render<LRT_INTEGRATOR_PATH, 1024, true, true>)); LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH, 1024, true, true>));
@@ -366,6 +368,7 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
             LRT_SMEM((k_render<LRT_INTEGRATOR_PATH, 1024, true, true, true>)); LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH, 1024, true, true, true>));
             LRT_SMEM((k_render<LRT_INTEGRATOR_BIOVOLPATH, 1024, true, false, true>)); LRT_SMEM((k_render<LRT_INTEGRATOR_BIOVOLPATH, 1024, true, true, true>));
             LRT_SMEM((k_render<LRT_INTEGRATOR_BIOVOLPATH06, 1024, true, false, true>)); LRT_SMEM((k_render<LRT_INTEGRATOR_BIOVOLPATH06, 1024, true, true, true>));
+            LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH_CLOSED, 1024, true, false, true>)); LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH_CLOSED, 1024, true, true, true>));   // (64-byte records)
             // (the wide-record integrators run 768-thread workgroups: 3 waves per SIMD, 168 VGPRs instead of 128 + 200 - 430 B of scratch per lane;
             //  measured on the f4 bench configs: volpathmis +58 %, volpath with heterogeneous media +9 %; 512 threads: +54 % / -18 %)
             LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH_HET, LRT_WIDE_BLOCK, true, false>)); LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH_HET, LRT_WIDE_BLOCK, true, true>));
@@ -791,6 +794,51 @@ static void check_integrator_media(DeviceScene *D, int integrator) {
     if (integrator == LRT_INTEGRATOR_VOLPATHMIS) D->need_mis = true;          // its wider path record is allocated on first use
 }
 
+// 64-byte path records (kernels.h, MODE 4; instances k_render<LRT_INTEGRATOR_VOLPATH_CLOSED, ...>): volpath on a scene where only a path's last
+// trip can add radiance, so that a record carries no radiance and no last-scatter pdf.  Called for every render with the current scene
+// description (lrt_param_set may have changed sigma_t since the load); the caller also requires compact records (no area emitter, no EXT
+// scene, BVH in LDS) and the volpath integrator.  Conditions:
+//   (a) no medium is heterogeneous, every medium has sigma_t * scale finite and >= 1e-30 in every channel, the sensor sits in no medium and no shape has an
+//       exterior medium (every medium is the inside of a shape);
+//   (b) every shape has a delta-only BSDF: dielectric, or a bumpmap over a dielectric (no F_SMOOTH lobe, no null BSDF);
+//   (c) the only emitter is one envmap or constant emitter.
+// Proof that a record's radiance is +0 and last_pdf is never read (volpath_iteration):
+//   1. surface NEE needs F_SMOOTH (b): it never runs;
+//   2. in-medium NEE is +0: the shadow ray's free-flight draw -log(1 - u) / sigma_t is finite (a 24-bit uniform gives 1 - u >= 2^-24, so at
+//      most 16.7 / 1e-30 < the largest float, (a)).  Either it lands inside the medium, a real collision (sigma_n = 0 in a homogeneous
+//      medium) that zeroes the transmittance, or beyond the medium's boundary, a non-null surface (b) whose null transmission is 0; the
+//      emitter sample lies at distance >= 2 r, beyond every surface;
+//   3. the only emitter hit is the escape to the infinite emitter (c), and it ends the path.  A lane inside a medium never escapes (its
+//      free flight is finite, (a)), so the escape follows a surface event, a delta bounce (b), which sets specular_chain; or it happens
+//      at depth 0.  Either way count_direct holds and last_pdf / the last scatter position are not read.
+// So every queued record's radiance is +0 and a path's radiance is its last trip's: 0 + ... + 0 + c = c, bit for bit.  The kernels check 3. on every
+// trip (DCounters::n_closed_guard: nonzero radiance on a lane that goes on, an emitter hit without count_direct) and the render fails instead of
+// returning a wrong image.  2. is not checked (that check cost 2.5 % on C3): it rests on the conditions above alone.
+static bool closed_records(const DeviceScene *D, const lrt_scene_desc &d) {
+    if (d.n_emitters != 1 || (d.emitters[0].type != LRT_EMITTER_ENVMAP && d.emitters[0].type != LRT_EMITTER_CONSTANT)) return false;
+    if (D->sc.cam.medium >= 0) return false;
+    for (uint32_t i = 0; i < d.n_media; ++i) {
+        const lrt_medium_desc &M = d.media[i];
+        if (M.type == LRT_MEDIUM_HETEROGENEOUS) return false;           // (volpath reads the bio media as homogeneous ones: sigma_t * scale)
+        for (int k = 0; k < 3; ++k) { const float st = M.sigma_t[k] * M.scale; if (!(std::isfinite(st) && st >= 1e-30f)) return false; }   // as upload_media forms it
+    }
+    for (uint32_t i = 0; i < d.n_shapes; ++i) {
+        const lrt_shape_desc &S = d.shapes[i];
+        if (S.exterior_medium >= 0 || S.bsdf < 0 || (uint32_t) S.bsdf >= d.n_bsdfs) return false;
+        const lrt_bsdf_desc *B = &d.bsdfs[S.bsdf];
+        if (B->type == LRT_BSDF_BUMPMAP) { if (B->nested < 0 || (uint32_t) B->nested >= d.n_bsdfs) return false; B = &d.bsdfs[B->nested]; }
+        if (B->type != LRT_BSDF_DIELECTRIC) return false;
+    }
+    return true;
+}
+// bytes per queued path record of the wide (not compact) layouts, as lrt_render_stats reports them
+static uint32_t wide_record_bytes(const DeviceScene *D, int integrator) {
+    if (integrator == LRT_INTEGRATOR_VOLPATHMIS) return LRT_STATE_BYTES_MIS;
+    if (integrator == LRT_INTEGRATOR_BIOVOLPATH || integrator == LRT_INTEGRATOR_BIOVOLPATH06) return LRT_STATE_BYTES_BIO;
+    if (integrator == LRT_INTEGRATOR_VOLPATH && D->has_het) return LRT_STATE_BYTES_HET;
+    return LRT_STATE_BYTES;
+}
+
 // One persistent launch per render (k_render / k_render_prb): per-workgroup path pools, in-kernel regeneration; see
 // kernels.h.  sample_out != nullptr: per-lane test hook for lanes [lane_begin, lane_begin + n_lanes).
 static void run_wavefront(DeviceScene *D, const lrt_scene_desc &d, const ResolvedOpts &O, uint64_t lane_begin, uint64_t n_lanes,
@@ -821,12 +869,17 @@ static void run_wavefront(DeviceScene *D, const lrt_scene_desc &d, const Resolve
         // Compact records (kernels.h, store_state): only an area emitter's pdf reads the last scatter position, so a scene without one does not queue it.
         // Instances exist for the 1024-thread LDS kernels of path / volpath (homogeneous media) / biovolpath / biovolpath06.  LRT_WIDE_RECORDS: developer switch.
         const bool compact = D->use_lds && !D->has_area_emitter && !D->ext && !getenv("LRT_WIDE_RECORDS") && O.integrator != LRT_INTEGRATOR_VOLPATHMIS && !(O.integrator == LRT_INTEGRATOR_VOLPATH && D->has_het);
+        // 64-byte records (volpath only; LRT_NO_CLOSED_RECORDS: developer switch back to the 80-byte layout): decided per render, since
+        // lrt_param_set can change sigma_t after the scene was loaded
+        const bool closed = compact && O.integrator == LRT_INTEGRATOR_VOLPATH && closed_records(D, d) && !getenv("LRT_NO_CLOSED_RECORDS");
         a.rp.compact = compact ? 1u : 0u;
+        stats.record_bytes = closed ? LRT_STATE_BYTES_CLOSED : (compact ? (O.integrator == LRT_INTEGRATOR_BIOVOLPATH || O.integrator == LRT_INTEGRATOR_BIOVOLPATH06 ? LRT_STATE_BYTES_BIO - 8 : LRT_STATE_BYTES_COMPACT) : wide_record_bytes(D, O.integrator));
         const LaunchPtr lp = push_launch(D, a);
 #ifdef LRT_DEV_VOLPATH_ONLY
         if (D->ext) throw std::runtime_error("developer build: no EXT instances (spheres / point emitters)");
         if (!(D->use_lds && (O.integrator == LRT_DEV_INTEGRATOR || (LRT_DEV_INTEGRATOR == LRT_INTEGRATOR_VOLPATH_HET && D->has_het)) && (rp.ld_count != 0) == LRT_DEV_LD)) throw std::runtime_error("developer build: one integrator / sampler / LDS BVH only");
-        if (compact) k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD, true><<<g.n_wg, LRT_DEV_BLOCK, g.smem, st>>>((ScenePtr) D->d_sc, lp);
+        if (closed) k_render<LRT_DEV_CLOSED, LRT_DEV_BLOCK, true, LRT_DEV_LD, true><<<g.n_wg, LRT_DEV_BLOCK, g.smem, st>>>((ScenePtr) D->d_sc, lp);
+        else if (compact) k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD, true><<<g.n_wg, LRT_DEV_BLOCK, g.smem, st>>>((ScenePtr) D->d_sc, lp);
         else k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD><<<g.n_wg, LRT_DEV_BLOCK, g.smem, st>>>((ScenePtr) D->d_sc, lp);
         #define LRT_LAUNCH_I(BS, LDSB)
         #define LRT_LAUNCH(I, BS, LDSB)
@@ -847,7 +900,7 @@ static void run_wavefront(DeviceScene *D, const lrt_scene_desc &d, const Resolve
             case LRT_INTEGRATOR_PATH: LRT_LAUNCH_COMPACT(LRT_INTEGRATOR_PATH); break;
             case LRT_INTEGRATOR_BIOVOLPATH: LRT_LAUNCH_COMPACT(LRT_INTEGRATOR_BIOVOLPATH); break;
             case LRT_INTEGRATOR_BIOVOLPATH06: LRT_LAUNCH_COMPACT(LRT_INTEGRATOR_BIOVOLPATH06); break;
-            default: LRT_LAUNCH_COMPACT(LRT_INTEGRATOR_VOLPATH); }
+            default: if (closed) LRT_LAUNCH_COMPACT(LRT_INTEGRATOR_VOLPATH_CLOSED); else LRT_LAUNCH_COMPACT(LRT_INTEGRATOR_VOLPATH); }
         else if (D->use_lds) LRT_LAUNCH_I(1024, true); else LRT_LAUNCH_I(LRT_BLOCK, false);
         #undef LRT_LAUNCH_COMPACT
 #endif
@@ -862,6 +915,10 @@ static void run_wavefront(DeviceScene *D, const lrt_scene_desc &d, const Resolve
     log.n_iter = count_iter ? D->h_counters->n_iter : 0;
     log.n_records = D->h_counters->n_records;
     finish_stats(D, log, e_begin, e_end, n_lanes, stats);
+    stats.n_closed_guard = D->h_counters->n_closed_guard;
+    if (stats.n_closed_guard)
+        throw std::runtime_error("64-byte path records: " + std::to_string(stats.n_closed_guard) + " trips broke the premise of the layout (radiance before a path's last trip, "
+                                 "or an emitter hit that needs its MIS weight); the scene test in closed_records() is wrong for this scene: LRT_NO_CLOSED_RECORDS=1 renders it with 80-byte records");
 }
 
 // after_pass (the aov integrator with one nested integrator): called after each pass's colour work, while D->cur_pass_in still
@@ -904,6 +961,7 @@ static void render_passes(DeviceScene *D, const lrt_scene_desc &d, const lrt_ren
             run_wavefront(D, d, O, 0, n_lanes, pixel_list, film, nullptr, st1);
             total.n_samples += st1.n_samples; total.n_iter += st1.n_iter; total.n_shadow += st1.n_shadow; total.n_launches += st1.n_launches;
             total.n_records += st1.n_records; total.kernel_ms += st1.kernel_ms; total.total_ms += st1.total_ms;
+            total.record_bytes = st1.record_bytes; total.n_closed_guard += st1.n_closed_guard;
             if (after_pass) after_pass(O);
             continue;
         }
@@ -921,6 +979,7 @@ static void render_passes(DeviceScene *D, const lrt_scene_desc &d, const lrt_ren
             HIP_CHECK(hipGetLastError());
             total.n_samples += st1.n_samples; total.n_iter += st1.n_iter; total.n_shadow += st1.n_shadow; total.n_launches += st1.n_launches;
             total.n_records += st1.n_records; total.kernel_ms += st1.kernel_ms; total.total_ms += st1.total_ms;
+            total.record_bytes = st1.record_bytes; total.n_closed_guard += st1.n_closed_guard;
         }
         if (after_pass) after_pass(O);
     }
@@ -1078,6 +1137,7 @@ void device_render_aov(DeviceScene *D, const lrt_scene_desc &d, const lrt_aov_de
         if (image) { k_aov_copy<<<(uint32_t) ((np + 255) / 256), 256, 0, st>>>(inner, IC, img, T, k * IC, (uint32_t) np); HIP_CHECK(hipGetLastError()); }
         total.n_samples += sk.n_samples; total.n_iter += sk.n_iter; total.n_shadow += sk.n_shadow; total.n_launches += sk.n_launches;
         total.n_records += sk.n_records; total.kernel_ms += sk.kernel_ms; total.total_ms += sk.total_ms;
+        total.record_bytes = sk.record_bytes; total.n_closed_guard += sk.n_closed_guard;
     }
     // 2. the AOV pass (Base::render, aov.cpp:382-391)
     if (!aov_done) {
@@ -1375,7 +1435,7 @@ void device_render_multi(std::vector<DeviceScene *> &devs, MultiContext *&ctx, c
     HIP_CHECK(hipStreamSynchronize(D0->stream)); HIP_CHECK(hipGetLastError());
     lrt_render_stats total{};
     for (auto &x : st) { total.n_samples += x.n_samples; total.n_iter += x.n_iter; total.n_shadow += x.n_shadow; total.n_launches += x.n_launches; total.n_records += x.n_records;
-                         total.kernel_ms = std::max(total.kernel_ms, x.kernel_ms); total.lds_resident = x.lds_resident; }
+                         total.kernel_ms = std::max(total.kernel_ms, x.kernel_ms); total.lds_resident = x.lds_resident; total.record_bytes = x.record_bytes; total.n_closed_guard += x.n_closed_guard; }
     total.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     stats = total;
 }

@@ -194,10 +194,13 @@ struct DPathStreams {
 #define LRT_STATE_BYTES 88     // bytes per path record across all streams (path / volpath)
 #define LRT_STATE_BYTES_MIS 168 // volpathmis: o, d, res, lp, rng, hit + five float4 of MIS weights
 #define LRT_STATE_BYTES_HET 104 // volpath with heterogeneous media: + the kept surface hit (float4)
+#define LRT_STATE_BYTES_COMPACT 80 // path / volpath / biovolpath* without area emitters: the lane id and the sampler word ride with the generator state (store_state)
+#define LRT_STATE_BYTES_CLOSED 64 // volpath where only the last trip adds radiance: no radiance, no last-scatter pdf, the flags in the throughput's .w
 #define LRT_STATE_BYTES_BIO 96 // biovolpath*: + tissueDepth and the look-ahead's free-flight distance; the maxt slot carries the previous ray query's distance
 
 #define LRT_INTEGRATOR_VOLPATHMIS_PLAIN 102   // kernel selector: volpathmis with use_spectral_mis = false
 #define LRT_INTEGRATOR_VOLPATH_HET 101   // kernel selector (not an API value): volpath on a scene with heterogeneous media
+#define LRT_INTEGRATOR_VOLPATH_CLOSED 103   // kernel selector: volpath with 64-byte records, for scenes where only a path's last trip adds radiance (device.hip, closed_records)
 
 // flag word layout
 #define PF_DEPTH_MASK   0x0000ffffu
@@ -222,6 +225,7 @@ struct DCounters {             // device-resident queue / statistics words
     unsigned long long n_records;  // path records loaded from the queues
     unsigned long long prof_cycles[4], prof_tiles[4];   // per tile kind (A, C, B, fresh): wall_clock64 ticks and tiles (LRT_DEBUG_LAUNCH)
     unsigned long long prof_wg[6];   // LRT_DEBUG_LAUNCH: workgroup timeline, 100 MHz ticks: sum of start, sum of (loop start - start), sum of end, max end, min start + 2^62 trick see kernels.h, sum of barrier waits of thread 0
+    unsigned long long n_closed_guard;   // 64-byte-record kernels: trips that broke the layout's premise (radiance before the last trip, an emitter hit that needs MIS)
 };
 
 // LDS image of the scene for the persistent traversal kernel: [nodes | verts (float4) | tris (4 x u16)] copied verbatim

@@ -38,13 +38,17 @@ struct PathState {
 
 // BIO: a queued path's ray always comes from spawn_ray (maxt = largest float), so its maxt slot carries si_t instead, and
 // the seventh stream holds tissueDepth and the element competition the look-ahead already ran (96 B records)
-// MODE: 0 path / volpath (88 B), 1 biovolpath* (96 B), 2 volpath with heterogeneous media (104 B), 3 volpathmis (168 B)
+// MODE: 0 path / volpath (88 B), 1 biovolpath* (96 B), 2 volpath with heterogeneous media (104 B), 3 volpathmis (168 B),
+// 4 volpath where only a path's last trip adds radiance (64 B, always compact: o | ff_t, d | eta, tp | flags, state | lane | sampler word; no
+// radiance and no last-scatter pdf: see closed_records in device.hip)
 // A record as the stream loads return it.  Fetching (the loads) and unpacking (the first use of their results) are apart so that the
 // render kernel can ask for a tile's records while the previous tile is still being compacted and stored.
 struct RawState { float4 a, b, c, d, e; uint2 r; uint4 r4; float2 td; float4 hit, w1, w2, w3, w4; };
 template <int MODE = 0, typename QS>
 DEV void fetch_state(const QS &q, size_t i, RawState &w, bool compact = false) {
-    w.a = q.o_maxt[i]; w.b = q.d_eta[i]; w.c = q.tp_pdf[i]; w.d = q.res_flags[i];
+    w.a = q.o_maxt[i]; w.b = q.d_eta[i]; w.c = q.tp_pdf[i];
+    if (MODE == 4) { w.r4 = reinterpret_cast<const uint4 *>(q.rng)[i]; return; }
+    w.d = q.res_flags[i];
     if (compact) w.r4 = reinterpret_cast<const uint4 *>(q.rng)[i];                       // state | lane | sampler word: no last-scatter-position stream
     else { w.e = q.lp_lane[i]; w.r = q.rng[i]; }
     if (MODE == 1) w.td = q.tdepth[i];
@@ -53,6 +57,13 @@ DEV void fetch_state(const QS &q, size_t i, RawState &w, bool compact = false) {
 }
 template <int MODE = 0>
 DEV void unpack_state(const RawState &w, PathState &s, bool compact = false) {
+    if (MODE == 4) {
+        const float4 a = w.a, b = w.b, c = w.c; const uint4 r4 = w.r4;
+        s.o = V3(a.x, a.y, a.z); s.ff_t = a.w; s.maxt = kLargest; s.d = V3(b.x, b.y, b.z); s.eta = b.w;
+        s.tp = V3(c.x, c.y, c.z); s.flags = f2u(c.w); s.res = V3(0.f); s.lp = V3(0.f); s.last_pdf = 1.f;      // (last_pdf, lp: never read)
+        s.lane = r4.z; s.rng_word = r4.w; s.rng_state = ((uint64_t) r4.y << 32) | r4.x;
+        return;
+    }
     const float4 a = w.a, b = w.b, c = w.c, d = w.d;
     s.o = V3(a.x, a.y, a.z); s.maxt = a.w; s.d = V3(b.x, b.y, b.z); s.eta = b.w;
     s.tp = V3(c.x, c.y, c.z); s.last_pdf = c.w; s.res = V3(d.x, d.y, d.z); s.flags = f2u(d.w);
@@ -72,6 +83,12 @@ template <int MODE = 0, typename QS>
 DEV void load_state(const QS &q, size_t i, PathState &s, bool compact = false) { RawState w; fetch_state<MODE>(q, i, w, compact); unpack_state<MODE>(w, s, compact); }
 template <int MODE = 0, typename QS>
 DEV void store_state(const QS &q, size_t i, const PathState &s, bool compact = false) {
+    if (MODE == 4) {
+        q.o_maxt[i] = make_float4(s.o.x, s.o.y, s.o.z, s.ff_t); q.d_eta[i] = make_float4(s.d.x, s.d.y, s.d.z, s.eta);
+        q.tp_pdf[i] = make_float4(s.tp.x, s.tp.y, s.tp.z, u2f(s.flags));
+        reinterpret_cast<uint4 *>(q.rng)[i] = make_uint4((uint32_t) s.rng_state, (uint32_t) (s.rng_state >> 32), s.lane, s.rng_word);
+        return;
+    }
     q.o_maxt[i] = make_float4(s.o.x, s.o.y, s.o.z, MODE == 1 ? s.si_t : (MODE == 0 ? s.ff_t : s.maxt));
     q.d_eta[i] = make_float4(s.d.x, s.d.y, s.d.z, s.eta);
     if (MODE == 3) {
@@ -403,8 +420,14 @@ struct WaveCount {
 // of a camera lane's first trip), on the lane's own generator: same draws in the same order.  A queued record therefore holds a path
 // that is known to run its next trip, with the throughput already divided by the survival probability, the free-flight distance
 // in the record (ff_t) and, when the distance field proves that distance free of surfaces, PF_NOHIT.
-template <bool HET, typename SMP, typename TR, typename CNT>
-DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const TR &tr, CNT &n_shadow, CNT &n_extra, bool fresh = false, StampClock *clk = nullptr) {
+// CLOSED (64-byte records, MODE 4): the host has proven that only a path's last trip adds radiance (closed_records in device.hip): `result`
+// starts at 0 every trip and leaves in s.res for the film only; in-medium NEE, which the proof makes +0, is run for its draws and shadow-ray
+// counts but not added; last_pdf and the last scatter position are never read.  A trip that breaks the premise (nonzero radiance on a lane that
+// goes on, an emitter hit that needs the MIS weight) adds one to *guard: the host reports an error.  (Checking the in-medium NEE term too was
+// measured at 2.5 % on C3: it keeps the phase function and the emitter value alive through the march.  DESIGN.md section 6c.)
+template <bool HET, bool CLOSED = false, typename SMP, typename TR, typename CNT>
+DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const TR &tr, CNT &n_shadow, CNT &n_extra, bool fresh = false, StampClock *clk = nullptr,
+                           unsigned long long *guard = nullptr) {
     constexpr bool PRE = !HET;
     uint32_t depth = s.flags & PF_DEPTH_MASK;
     bool proven_empty = (s.flags & PF_NOHIT) != 0;
@@ -417,7 +440,8 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
     const uint32_t channel = (s.flags >> PF_CHANNEL_SHIFT) & 3u;
     bool specular_chain = (s.flags & PF_SPECULAR) != 0, valid_ray = (s.flags & PF_VALID) != 0;
     const uint32_t max_depth = (uint32_t) rp.max_depth;
-    V3 throughput = s.tp, result = s.res;
+    V3 throughput = s.tp, result = CLOSED ? V3(0.f) : s.res;
+    bool broken = false;                                                // CLOSED: the premise failed on this trip
     float eta = s.eta;
     Ray ray; ray.o = s.o; ray.d = s.d; ray.maxt = s.maxt;
     auto commit = [&]() {
@@ -535,7 +559,7 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
                 V3 emitted = volpath_sample_emitter<HET>(sc, rng, mei.p, V3(0.f), false, 0, V3(0.f), medium, channel, &ds, tr, n_shadow);
                 float phase_val = phase_eval(M, mei.wi, ds.d);
                 V3 c = throughput * phase_val * emitted * mis_weight(ds.pdf, ds.delta ? 0.f : phase_val);
-                result = result + c;
+                if (!CLOSED) result = result + c;
             }
         }
         (void) rng.next();
@@ -572,11 +596,14 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
         int emitter = si_emitter(sc, si);
         bool active_e = emitter >= 0 && !(depth == 0 && rp.hide_emitters);
         if (active_e) {
-            float emitter_pdf = 1.f;
-            if (!count_direct) emitter_pdf = pdf_emitter_direction<TR::kExt>(sc, s.lp, si, emitter);
-            V3 emitted = emitter_eval(sc, emitter, si);
-            V3 contrib = count_direct ? throughput * emitted : throughput * mis_weight(s.last_pdf, emitter_pdf) * emitted;
-            result = result + contrib;
+            if (CLOSED) { broken = broken || !count_direct; result = result + throughput * emitter_eval(sc, emitter, si); }     // (count_direct: no MIS weight)
+            else {
+                float emitter_pdf = 1.f;
+                if (!count_direct) emitter_pdf = pdf_emitter_direction<TR::kExt>(sc, s.lp, si, emitter);
+                V3 emitted = emitter_eval(sc, emitter, si);
+                V3 contrib = count_direct ? throughput * emitted : throughput * mis_weight(s.last_pdf, emitter_pdf) * emitted;
+                result = result + contrib;
+            }
         }
     }
     active_surface = active_surface && si.valid;
@@ -634,6 +661,9 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
     }
     commit();
     s.flags |= nohit; s.ff_t = cache_t;
+#ifndef LRT_CLOSED_NO_GUARD                                             // (make dev DEVFLAGS=-DLRT_CLOSED_NO_GUARD: without the check, to measure its cost)
+    if (CLOSED && (broken || (active && !(result.x == 0.f && result.y == 0.f && result.z == 0.f)))) atomicAdd(guard, 1ull);     // (never taken when the host's proof holds)
+#endif
     if (HET && act_null_scatter && active) { s.flags |= PF_HAVE_SI; s.hit = make_float4(hkeep.t, hkeep.u, hkeep.v, u2f(hkeep.prim)); }
     return active;
 }
@@ -817,7 +847,8 @@ k_render(ScenePtr scp, LaunchPtr lp) {
     const uint32_t tid = threadIdx.x, lane_in_wave = tid & 63u;
     constexpr bool READLANE = INTEGRATOR != LRT_INTEGRATOR_PATH && INTEGRATOR != LRT_INTEGRATOR_BIOVOLPATH06;
     constexpr bool LONGQ = INTEGRATOR == LRT_INTEGRATOR_BIOVOLPATH;          // fourth queue region (retire_and_compact_wave)
-    constexpr int MODE = (INTEGRATOR == LRT_INTEGRATOR_BIOVOLPATH || INTEGRATOR == LRT_INTEGRATOR_BIOVOLPATH06) ? 1 : (INTEGRATOR == LRT_INTEGRATOR_VOLPATH_HET ? 2 : ((INTEGRATOR == LRT_INTEGRATOR_VOLPATHMIS || INTEGRATOR == LRT_INTEGRATOR_VOLPATHMIS_PLAIN) ? 3 : 0));
+    constexpr bool CLOSED = INTEGRATOR == LRT_INTEGRATOR_VOLPATH_CLOSED;   // 64-byte records (MODE 4; the host launches these instances with COMPACT set)
+    constexpr int MODE = (INTEGRATOR == LRT_INTEGRATOR_BIOVOLPATH || INTEGRATOR == LRT_INTEGRATOR_BIOVOLPATH06) ? 1 : (INTEGRATOR == LRT_INTEGRATOR_VOLPATH_HET ? 2 : ((INTEGRATOR == LRT_INTEGRATOR_VOLPATHMIS || INTEGRATOR == LRT_INTEGRATOR_VOLPATHMIS_PLAIN) ? 3 : (CLOSED ? 4 : 0)));
     if (tid < 8) s_prof[tid] = 0;
     const unsigned long long t_wg_start = (rp.profile & 1u) ? wall_clock64() : 0ull;
     unsigned long long t_loop_start = 0ull, t_barrier = 0ull;
@@ -842,7 +873,7 @@ k_render(ScenePtr scp, LaunchPtr lp) {
     // Counters: per-lane registers, summed over the wave at the end.  The homogeneous-media volpath kernels keep none in vector registers:
     // trips and loaded records are per-wave sums of tile populations (scalar registers), shadow-ray queries and trips retired by the
     // look-ahead per-workgroup sums in LDS (WaveCount).
-    constexpr bool VP_LDS_COUNT = INTEGRATOR == LRT_INTEGRATOR_VOLPATH;
+    constexpr bool VP_LDS_COUNT = INTEGRATOR == LRT_INTEGRATOR_VOLPATH || CLOSED;
     __shared__ unsigned long long s_cnt[2];
     if (VP_LDS_COUNT && tid < 2) s_cnt[tid] = 0;
     WaveCount wc_shadow{ &s_cnt[0] }, wc_extra{ &s_cnt[1] };
@@ -911,10 +942,12 @@ k_render(ScenePtr scp, LaunchPtr lp) {
                 else {
                     const bool fresh_tile = t >= ta + tcl + tb;
 #ifdef LRT_STAMP
-                    alive = LDS_BVH ? volpath_iteration<false>(sc, rp, s, rng, tr_lds, wc_shadow, wc_extra, fresh_tile, &clk) : volpath_iteration<false>(sc, rp, s, rng, tr_glb, wc_shadow, wc_extra, fresh_tile, &clk);
+                    StampClock *const pclk = &clk;
 #else
-                    alive = LDS_BVH ? volpath_iteration<false>(sc, rp, s, rng, tr_lds, wc_shadow, wc_extra, fresh_tile) : volpath_iteration<false>(sc, rp, s, rng, tr_glb, wc_shadow, wc_extra, fresh_tile);
+                    StampClock *const pclk = nullptr;
 #endif
+                    unsigned long long *const guard = CLOSED ? &A.cnt->n_closed_guard : nullptr;
+                    alive = LDS_BVH ? volpath_iteration<false, CLOSED>(sc, rp, s, rng, tr_lds, wc_shadow, wc_extra, fresh_tile, pclk, guard) : volpath_iteration<false, CLOSED>(sc, rp, s, rng, tr_glb, wc_shadow, wc_extra, fresh_tile, pclk, guard);
                 }
                 s.rng_state = rng.state;
                 if (!VP_LDS_COUNT) n_trips += 1;
