@@ -254,7 +254,7 @@ typedef struct {
 typedef struct lrt_scene lrt_scene;
 
 LRT_API const char *lrt_last_error(void);
-LRT_API int         lrt_version(void);   /* 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
+LRT_API int         lrt_version(void);   /* 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
 
 LRT_API lrt_status lrt_scene_load_xml(const char *path, const char *const *defines,
                                       int n_defines, lrt_scene **out);
@@ -436,6 +436,48 @@ LRT_API lrt_status lrt_vae_scatter(lrt_vae_model *model, uint32_t n, const float
                                    const float *poly_coeffs, const float albedo[3], float g, float ior,
                                    const float sigma_t[3], float fit_scale, uint32_t seed,
                                    float *out_pos, float *out_absorption, int device);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Guided denoiser [v109]: the place of mi.OptixDenoiser (include/mitsuba/render/optixdenoiser.h) in the reference's workflow
+ * (Denoise.py; --imode optix, src/mitsuba/realtime.hpp:501-508).  OptiX's network is closed and NVIDIA-only; behind the same
+ * interface runs the edge-avoiding A-Trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch, HPG 2010) with albedo demodulation,
+ * specified operation by operation in DESIGN.md section 9.
+ * A field of lrt_denoise_params that is 0 takes its default; a negative or non-finite one is LRT_ERR_INVALID, and so is
+ * `iterations` outside 1 .. LRT_DENOISE_MAX_ITERATIONS.                                                                   */
+#define LRT_DENOISE_MAX_ITERATIONS    8
+#define LRT_DENOISE_ITERATIONS        5
+#define LRT_DENOISE_SIGMA_COLOR       0.3f
+#define LRT_DENOISE_SIGMA_NORMAL      0.1f
+#define LRT_DENOISE_SIGMA_ALBEDO      0.05f
+#define LRT_DENOISE_EPS_A             0.5f      /* defaults: scripts/study/denoise_study.py, DESIGN.md section 9.3 */
+#define LRT_DENOISE_MAX_SIZE          16384    /* width and height */
+typedef struct {
+    int32_t iterations;       /* passes N, step 2^k in pass k                          */
+    float   sigma_color;      /* colour tolerance of pass 0; halves every pass         */
+    float   sigma_normal;
+    float   sigma_albedo;
+    float   eps_a;            /* floor of the demodulation divisor max(albedo, eps_a)  */
+} lrt_denoise_params;
+typedef struct lrt_denoiser lrt_denoiser;
+/* Allocates the workspace (packed planes, ping-pong colour, staging) for width x height on `device` and a non-blocking stream;
+ * params may be NULL (all defaults).  The arguments are checked before the device is touched. */
+LRT_API lrt_status lrt_denoiser_create(int width, int height, int use_albedo, int use_normals, int denoise_alpha,
+                                       const lrt_denoise_params *params, int device, lrt_denoiser **out);
+/* noisy / out: height * width * channels floats, channels 3 or 4 (R,G,B[,A]); albedo / normals: height * width * 3 floats,
+ * required exactly when the denoiser was created with that guide (NULL otherwise: LRT_ERR_INVALID either way round).  Alpha is
+ * filtered when the denoiser was created with denoise_alpha and channels is 4, copied through otherwise.  With device_buffers
+ * all four pointers are device memory on the denoiser's device (as lrt_render_opts.output_on_device): the caller has finished
+ * writing the inputs, and the call returns after the denoiser's stream has finished with all of them.  out must not alias an input. */
+LRT_API lrt_status lrt_denoise(lrt_denoiser *denoiser, const float *noisy, int channels, const float *albedo, const float *normals,
+                               float *out, int device_buffers);
+LRT_API void       lrt_denoiser_free(lrt_denoiser *denoiser);
+/* The parameters a denoiser runs with (defaults resolved) and its size. */
+LRT_API lrt_status lrt_denoiser_get(const lrt_denoiser *denoiser, int *width, int *height, lrt_denoise_params *params);
+/* lrt_image_read that also reports the file's channel names (EXR: EVERY channel of the file, R,G,B[,A] or Y[,A]
+ * first when the file has them, the others after them in file order, e.g. "albedo.R"; PNG: no names, the data of lrt_image_read): *names is one string of the names in data order, separated by '\n', released with lrt_image_free_names; empty
+ * when the file has none. */
+LRT_API lrt_status lrt_image_read_named(const char *path, int *width, int *height, int *channels, float **data, char **names);
+LRT_API void       lrt_image_free_names(char *names);
 
 #ifdef __cplusplus
 }

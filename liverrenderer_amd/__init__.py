@@ -14,7 +14,8 @@ from . import _lib
 from ._lib import make_opts
 
 __all__ = ["set_variant", "variant", "variants", "load_file", "load_string", "load_dict", "cornell_box", "render",
-           "traverse", "Scene", "ScalarTransform4f", "render_stats", "write_volume_grid", "Bitmap", "Struct", "util", "read_image", "write_exr", "write_png"]
+           "traverse", "Scene", "ScalarTransform4f", "render_stats", "write_volume_grid", "Bitmap", "Struct", "util", "read_image", "write_exr", "write_png",
+           "Denoiser", "OptixDenoiser", "denoise"]
 
 _VARIANT = "hip_ad_rgb"
 
@@ -559,6 +560,18 @@ def read_image(path):
         L.lrt_image_free(data)
 
 
+def _read_image_named(path):
+    """lrt_image_read_named: (array, channel names or None).  An EXR gives every channel of the file."""
+    L = _lib.lib()
+    w, h, c = C.c_int(), C.c_int(), C.c_int(); data = C.POINTER(C.c_float)(); names = C.c_void_p()
+    _lib.check(L.lrt_image_read_named(os.fspath(path).encode(), C.byref(w), C.byref(h), C.byref(c), C.byref(data), C.byref(names)))
+    try:
+        joined = C.string_at(names.value).decode() if names.value else ""
+        return np.ctypeslib.as_array(data, (h.value, w.value, c.value)).copy(), (joined.split("\n") if joined else None)
+    finally:
+        L.lrt_image_free(data); L.lrt_image_free_names(names)
+
+
 def write_png(path, image):
     """8-bit sRGB PNG of a linear float image (LiverRenderer.py:383-385: Bitmap.convert(RGBA, UInt8, srgb_gamma=True))."""
     img = np.ascontiguousarray(image, dtype=np.float32)
@@ -595,11 +608,50 @@ class Bitmap:
     class PixelFormat:
         Y, YA, RGB, RGBA = "y", "ya", "rgb", "rgba"
 
-    def __init__(self, src):
-        self.data = read_image(src) if isinstance(src, (str, os.PathLike)) else np.asarray(src, dtype=np.float32)
+    def __init__(self, src, pixel_format=None, component_format=None, srgb_gamma=None, channel_names=None):
+        """mi.Bitmap(path) | mi.Bitmap(array, channel_names=[...]) | mi.Bitmap(bitmap, pixel_format, component_format, srgb_gamma)
+        (the converting constructor Denoise.py uses).  `channel_names` (one per channel, e.g. scene.aov_channel_names()) makes
+        the bitmap a multi-channel one; a file's own names are kept (EXR: every channel of the file, R,G,B[,A] first)."""
+        if isinstance(src, Bitmap):
+            b = src.convert(pixel_format, component_format, srgb_gamma) if (pixel_format or component_format or srgb_gamma is not None) else src
+            self.data, self.component_format, self.srgb_gamma, self.channel_names = b.data, b.component_format, b.srgb_gamma, b.channel_names
+            return
+        names = None
+        if isinstance(src, (str, os.PathLike)):
+            self.data, names = _read_image_named(src)
+        else:
+            self.data = np.asarray(src, dtype=np.float32)
         if self.data.ndim == 2:
             self.data = self.data[..., None]
+        if channel_names is not None:
+            names = [str(n) for n in channel_names]
+            if len(names) != self.data.shape[2]:
+                raise ValueError(f"Bitmap: {len(names)} channel names for an image of {self.data.shape[2]} channels")
+        self.channel_names = names
         self.component_format, self.srgb_gamma = Struct.Type.Float32, False
+
+    def select(self, prefix="<root>"):
+        """The H x W x (3|4) image a channel name selects, as OptixDenoiser's bitmap form reads its inputs: a prefix selects
+        <prefix>.R/.G/.B or <prefix>.X/.Y/.Z; "<root>" selects R, G, B[, A], or the first three or four channels of a bitmap
+        without names (the first three when it has five or more)."""
+        names, d = self.channel_names, self.data
+        if prefix == "<root>":
+            if not names:
+                n = d.shape[2] if d.shape[2] in (3, 4) else 3
+                if d.shape[2] < 3:
+                    raise RuntimeError(f"Bitmap.select: \"<root>\" needs at least 3 channels, the bitmap has {d.shape[2]}")
+                return np.ascontiguousarray(d[..., :n])
+            want = ["R", "G", "B"] + (["A"] if "A" in names else [])
+        else:
+            if not names:
+                raise RuntimeError(f"Bitmap.select: channel \"{prefix}\" requested from a bitmap without channel names")
+            want = next(([f"{prefix}.{c}" for c in sfx] for sfx in ("RGB", "XYZ") if all(f"{prefix}.{c}" in names for c in sfx)), None)
+            if want is None:
+                raise RuntimeError(f"Bitmap.select: no channels \"{prefix}.R/.G/.B\" or \"{prefix}.X/.Y/.Z\" among {names}")
+        missing = [n for n in want if n not in names]
+        if missing:
+            raise RuntimeError(f"Bitmap.select: no channel {missing} among {names}")
+        return np.ascontiguousarray(d[..., [names.index(n) for n in want]])
 
     def size(self):
         return (self.data.shape[1], self.data.shape[0])
@@ -618,6 +670,7 @@ class Bitmap:
             lum = (0.212671 * rgb[..., :1] + 0.715160 * rgb[..., 1:2] + 0.072169 * rgb[..., 2:3])
             d = {1: lum, 2: np.concatenate([lum, alpha], 2), 3: rgb, 4: np.concatenate([rgb, alpha], 2)}[n]
         out.data = np.ascontiguousarray(d, dtype=np.float32)
+        out.channel_names = self.channel_names if n == self.data.shape[2] else None
         out.component_format = component_format or self.component_format
         out.srgb_gamma = self.srgb_gamma if srgb_gamma is None else bool(srgb_gamma)
         return out
@@ -637,8 +690,162 @@ class util:
         if os.fspath(path).lower().endswith(".png"):
             write_png(path, data)
         elif os.fspath(path).lower().endswith(".exr"):
-            write_exr(path, data)
+            names = image.channel_names if isinstance(image, Bitmap) else None
+            plain = names is None or names in (["Y"], ["R", "G", "B"], ["R", "G", "B", "A"])
+            write_exr(path, data, None if plain else names)
         else:
             raise RuntimeError(f"write_bitmap: unsupported file format \"{path}\" (supported: .png, .exr)")
 
     cornell_box = staticmethod(lambda: cornell_box())
+
+
+# ---- mi.OptixDenoiser (include/mitsuba/render/optixdenoiser.h): the denoising step of Denoise.py and of --imode optix.  OptiX's
+# network is closed and NVIDIA-only; behind the same interface runs the guided A-Trous wavelet filter of DESIGN.md section 9,
+# in the HIP kernels of csrc/kernels_denoise.h.
+def _is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+class Denoiser:
+    """mi.Denoiser(input_size, albedo=False, normals=False, temporal=False, denoise_alpha=False, **params); mi.OptixDenoiser is
+    the same class (argument order of optixdenoiser.h:57-59).  input_size is (width, height), e.g. Bitmap.size().  `params`:
+    iterations (1 .. 8), sigma_color, sigma_normal, sigma_albedo, eps_a (all positive; left out: the library's defaults) and
+    device.  The workspace and a stream of its own are allocated here and live as long as the object."""
+
+    PARAMS = ("iterations", "sigma_color", "sigma_normal", "sigma_albedo", "eps_a")
+
+    def __init__(self, input_size, albedo=False, normals=False, temporal=False, denoise_alpha=False, device=0, **params):
+        self._h = None
+        if temporal:
+            raise RuntimeError("Denoiser: temporal denoising is unsupported (it needs an optical flow, which no AOV of this back-end produces)")
+        unknown = sorted(set(params) - set(self.PARAMS))
+        if unknown:
+            raise TypeError(f"Denoiser: unknown parameter(s) {unknown} (known: {list(self.PARAMS)})")
+        size = tuple(int(v) for v in input_size)
+        if len(size) != 2:
+            raise ValueError("Denoiser: input_size is (width, height)")
+        prm = _lib.DenoiseParams()
+        for k, v in params.items():
+            if v is None:
+                continue
+            if k == "iterations":
+                if int(v) != v or not 1 <= int(v) <= 8:
+                    raise ValueError(f"Denoiser: iterations {v!r} outside 1 .. 8")
+                prm.iterations = int(v)
+            else:
+                if not (float(v) > 0.0 and math.isfinite(float(v))):      # 0 would select the default in lrt_denoise_params
+                    raise ValueError(f"Denoiser: {k} must be positive and finite, got {v!r}")
+                setattr(prm, k, float(v))
+        self._lib = _lib.lib()
+        h = C.c_void_p()
+        _lib.check(self._lib.lrt_denoiser_create(size[0], size[1], int(bool(albedo)), int(bool(normals)), int(bool(denoise_alpha)),
+                                                 C.byref(prm), int(device), C.byref(h)))
+        self._h = h.value
+        self.input_size, self.albedo, self.normals, self.denoise_alpha, self.device = size, bool(albedo), bool(normals), bool(denoise_alpha), int(device)
+        got = _lib.DenoiseParams()
+        _lib.check(self._lib.lrt_denoiser_get(self._h, None, None, C.byref(got)))
+        self.params = {k: getattr(got, k) for k in self.PARAMS}
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.lrt_denoiser_free(self._h); self._h = None
+        except Exception:
+            pass
+
+    def __repr__(self):
+        return f"Denoiser[input_size={self.input_size}, albedo={self.albedo}, normals={self.normals}, denoise_alpha={self.denoise_alpha}, params={self.params}]"
+
+    def __call__(self, noisy, albedo=None, normals=None, to_sensor=None, flow=None, previous_denoised=None, noisy_ch="<root>",
+                 albedo_ch=None, normals_ch=None, flow_ch="", previous_denoised_ch=""):
+        """Array form (optixdenoiser.h:112-117): denoiser(noisy, albedo=None, normals=None, to_sensor=None, flow=None,
+        previous_denoised=None) with H x W x (3|4) `noisy` and H x W x 3 guides, float32.  numpy arrays in: a numpy array out.
+        torch tensors on the GPU in: a tensor on the same device out, without a host copy (the current torch stream is
+        synchronised first: the library works on a stream of its own).
+        Bitmap form (optixdenoiser.h:173-179): denoiser(bitmap, albedo_ch="", normals_ch="", to_sensor=None, flow_ch="",
+        previous_denoised_ch="", noisy_ch="<root>") reads its inputs from the channels of one multi-channel Bitmap
+        (Bitmap.select) and returns a Bitmap.
+        `to_sensor` is accepted and ignored: the filter uses only differences of normals, whose lengths a rotation does not
+        change.  `flow` / `previous_denoised` belong to temporal denoising, which is unsupported."""
+        if isinstance(noisy, Bitmap):
+            a_ch = albedo_ch if albedo_ch is not None else (albedo if isinstance(albedo, str) else "")
+            n_ch = normals_ch if normals_ch is not None else (normals if isinstance(normals, str) else "")
+            if (albedo is not None and not isinstance(albedo, str)) or (normals is not None and not isinstance(normals, str)):
+                raise TypeError("Denoiser: with a Bitmap the guides are channel names of that bitmap (albedo_ch, normals_ch)")
+            if flow_ch or previous_denoised_ch or isinstance(flow, str) and flow or isinstance(previous_denoised, str) and previous_denoised:
+                raise RuntimeError("Denoiser: temporal denoising is unsupported (flow_ch / previous_denoised_ch)")
+            if self.albedo and not a_ch:
+                raise RuntimeError("Denoiser: the denoiser was created with the albedo guide, but no albedo_ch was given")
+            if self.normals and not n_ch:
+                raise RuntimeError("Denoiser: the denoiser was created with the normals guide, but no normals_ch was given")
+            out = self(noisy.select(noisy_ch), noisy.select(a_ch) if a_ch else None, noisy.select(n_ch) if n_ch else None)
+            return Bitmap(out)
+        if albedo_ch is not None or normals_ch is not None:
+            raise TypeError("Denoiser: albedo_ch / normals_ch go with a Bitmap input")
+        if flow is not None or previous_denoised is not None:
+            raise RuntimeError("Denoiser: temporal denoising is unsupported (flow / previous_denoised)")
+        w, h = self.input_size
+        if _is_torch(noisy):
+            return self._call_torch(noisy, albedo, normals)
+
+        def arr(x, name, channels):
+            a = np.ascontiguousarray(x, dtype=np.float32)
+            if a.ndim != 3 or a.shape[0] != h or a.shape[1] != w or a.shape[2] not in channels:
+                raise RuntimeError(f"Denoiser: {name} has shape {tuple(a.shape)}, expected ({h}, {w}, {' | '.join(map(str, channels))})")
+            return a
+        n = arr(noisy, "noisy", (3, 4))
+        a = None if albedo is None else arr(albedo, "albedo", (3,))
+        nr = None if normals is None else arr(normals, "normals", (3,))
+        out = np.empty_like(n)
+        _lib.check(self._lib.lrt_denoise(self._h, n.ctypes.data, n.shape[2], None if a is None else a.ctypes.data,
+                                         None if nr is None else nr.ctypes.data, out.ctypes.data, 0))
+        return out
+
+    def _call_torch(self, noisy, albedo, normals):
+        import torch
+        w, h = self.input_size
+
+        def ten(x, name, channels):
+            if not _is_torch(x):
+                raise TypeError(f"Denoiser: {name} must be a torch tensor when noisy is one")
+            if not x.is_cuda or x.device != noisy.device or x.dtype != torch.float32:
+                raise RuntimeError(f"Denoiser: {name} must be a float32 tensor on {noisy.device} (got {x.dtype} on {x.device})")
+            if x.dim() != 3 or x.shape[0] != h or x.shape[1] != w or x.shape[2] not in channels:
+                raise RuntimeError(f"Denoiser: {name} has shape {tuple(x.shape)}, expected ({h}, {w}, {' | '.join(map(str, channels))})")
+            return x.contiguous()
+        n = ten(noisy, "noisy", (3, 4))
+        if (n.device.index or 0) != self.device:
+            raise RuntimeError(f"Denoiser: the tensors live on {n.device}, the denoiser on device {self.device}")
+        a = None if albedo is None else ten(albedo, "albedo", (3,))
+        nr = None if normals is None else ten(normals, "normals", (3,))
+        out = torch.empty_like(n)
+        torch.cuda.current_stream(n.device).synchronize()
+        _lib.check(self._lib.lrt_denoise(self._h, n.data_ptr(), n.shape[2], None if a is None else a.data_ptr(),
+                                         None if nr is None else nr.data_ptr(), out.data_ptr(), 1))
+        return out
+
+
+OptixDenoiser = Denoiser
+
+
+def denoise(scene_image, scene, **params):
+    """Denoise what mi.render returns on an `aov` scene: the first nested integrator's image is the noisy input, the first
+    `albedo` AOV and the first `sh_normal` AOV (by scene.aov_channel_names()) are the guides, whichever of them the scene has.
+    Returns the denoised H x W x (3|4) image.  `params` as for Denoiser."""
+    a = scene.aov_desc()
+    if a is None:
+        raise RuntimeError("denoise(): the scene has no aov integrator (render it with <integrator type=\"aov\"> to get the guides)")
+    img = np.asarray(scene_image, dtype=np.float32)
+    names = scene.aov_channel_names()
+    if img.ndim != 3 or img.shape[2] != len(names):
+        raise RuntimeError(f"denoise(): the image has shape {tuple(img.shape)}, the scene renders {len(names)} channels")
+    bmp = Bitmap(img, channel_names=names)
+    inner = a.integrator_names[0].value.decode()
+    rgba = [f"{inner}.{c}" for c in "RGBA" if f"{inner}.{c}" in names]
+    noisy = np.ascontiguousarray(img[..., [names.index(n) for n in rgba]])
+    guide = {}
+    for key, typ in (("albedo", "albedo"), ("normals", "sh_normal")):
+        k = next((i for i in range(a.n_aovs) if a.aov_types[i] == _lib.AOV_TYPES[typ]), None)
+        guide[key] = None if k is None else bmp.select(a.aov_names[k].value.decode())
+    dn = Denoiser((img.shape[1], img.shape[0]), albedo=guide["albedo"] is not None, normals=guide["normals"] is not None, **params)
+    return dn(noisy, guide["albedo"], guide["normals"])

@@ -108,6 +108,11 @@ class ParamGrads(C.Structure):
     _fields_ = [("d_sigma_t", C.c_float * 3), ("d_albedo", C.c_float * 3), ("d_g", C.c_float)]
 
 
+class DenoiseParams(C.Structure):
+    """lrt_denoise_params: a field left 0 takes its default (include/liverrt.h)."""
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float), ("eps_a", C.c_float)]
+
+
 class RaysSoA(C.Structure):
     _fields_ = [(n, C.POINTER(C.c_float)) for n in ("ox", "oy", "oz", "dx", "dy", "dz", "tmax")]
 
@@ -202,6 +207,16 @@ def lib():
     L.lrt_aov_channel_name.restype = C.c_char_p
     L.lrt_render_aov.argtypes = [C.c_void_p, P(RenderOpts), C.c_void_p, C.c_void_p]
     L.lrt_render_aov_samples.argtypes = [C.c_void_p, P(RenderOpts), C.c_uint64, C.c_uint32, C.c_void_p]
+    L.lrt_denoiser_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(DenoiseParams), C.c_int, P(C.c_void_p)]
+    L.lrt_denoise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.lrt_denoiser_free.argtypes = [C.c_void_p]
+    L.lrt_denoiser_free.restype = None
+    L.lrt_denoiser_get.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int), P(DenoiseParams)]
+    L.lrt_image_read_named.argtypes = [C.c_char_p, P(C.c_int), P(C.c_int), P(C.c_int), P(P(C.c_float)), P(C.c_void_p)]
+    L.lrt_image_free_names.argtypes = [C.c_void_p]
+    L.lrt_image_free_names.restype = None
+    for name in ("lrt_denoiser_create", "lrt_denoise", "lrt_denoiser_get", "lrt_image_read_named"):
+        getattr(L, name).restype = C.c_int
     for name in ("lrt_image_read", "lrt_image_write_exr", "lrt_image_write_png", "lrt_scene_load_xml", "lrt_scene_load_xml_string", "lrt_scene_from_desc", "lrt_render", "lrt_render_multi", "lrt_render_backward_multi", "lrt_math_eval", "lrt_render_stats_get",
                  "lrt_film_develop", "lrt_render_samples", "lrt_render_backward", "lrt_trace", "lrt_emitter_probe", "lrt_param_set", "lrt_param_get",
                  "lrt_image_write_exr_channels", "lrt_scene_aov_get", "lrt_render_aov", "lrt_render_aov_samples"):
@@ -215,7 +230,8 @@ EXPORTED_SYMBOLS = ["lrt_last_error", "lrt_version", "lrt_scene_load_xml", "lrt_
                     "lrt_render_samples", "lrt_render_backward", "lrt_trace", "lrt_emitter_probe", "lrt_param_set", "lrt_param_get",
                     "lrt_image_read", "lrt_image_free", "lrt_image_write_exr", "lrt_image_write_png",
                     "lrt_vae_model_create", "lrt_vae_model_free", "lrt_vae_scatter",
-                    "lrt_scene_aov_get", "lrt_aov_channel_name", "lrt_render_aov", "lrt_render_aov_samples", "lrt_image_write_exr_channels"]
+                    "lrt_scene_aov_get", "lrt_aov_channel_name", "lrt_render_aov", "lrt_render_aov_samples", "lrt_image_write_exr_channels",
+                    "lrt_denoiser_create", "lrt_denoise", "lrt_denoiser_free", "lrt_denoiser_get", "lrt_image_read_named", "lrt_image_free_names"]
 
 
 def check(status):

@@ -28,7 +28,7 @@ static lrt_status fail(lrt_status st, const std::string &msg) { g_error = msg; r
 extern "C" {
 
 const char *lrt_last_error(void) { return g_error.c_str(); }
-int lrt_version(void) { return 108; }    // 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
+int lrt_version(void) { return 109; }    // 1.9: the guided denoiser (lrt_denoiser_create / lrt_denoise / lrt_denoiser_free), lrt_image_read_named; 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
 
 static std::vector<std::pair<std::string, std::string>> parse_defines(const char *const *defines, int n) {
     std::vector<std::pair<std::string, std::string>> r;
@@ -425,5 +425,87 @@ lrt_status lrt_image_write_png(const char *path, int width, int height, int chan
         return LRT_OK;
     LRT_CATCH
 }
+
+// ---- guided denoiser (device.hip: denoiser_create / denoiser_run; kernels_denoise.h)
+struct lrt_denoiser { Denoiser *dev = nullptr; int width = 0, height = 0; bool albedo = false, normals = false, alpha = false; lrt_denoise_params params{}; };
+
+lrt_status lrt_denoiser_create(int width, int height, int use_albedo, int use_normals, int denoise_alpha, const lrt_denoise_params *params, int device, lrt_denoiser **out) {
+    if (!out) return fail(LRT_ERR_INVALID, "lrt_denoiser_create: null argument");
+    *out = nullptr;
+    if (width < 1 || height < 1 || width > LRT_DENOISE_MAX_SIZE || height > LRT_DENOISE_MAX_SIZE)
+        return fail(LRT_ERR_INVALID, "lrt_denoiser_create: size " + std::to_string(width) + " x " + std::to_string(height) + " outside 1 .. " + std::to_string(LRT_DENOISE_MAX_SIZE));
+    lrt_denoise_params P = params ? *params : lrt_denoise_params{};
+    if (P.iterations == 0) P.iterations = LRT_DENOISE_ITERATIONS;
+    if (P.iterations < 1 || P.iterations > LRT_DENOISE_MAX_ITERATIONS)
+        return fail(LRT_ERR_INVALID, "lrt_denoiser_create: iterations " + std::to_string(P.iterations) + " outside 1 .. " + std::to_string(LRT_DENOISE_MAX_ITERATIONS));
+    struct { const char *name; float *v; float def; } fields[] = { { "sigma_color", &P.sigma_color, LRT_DENOISE_SIGMA_COLOR }, { "sigma_normal", &P.sigma_normal, LRT_DENOISE_SIGMA_NORMAL },
+                                                                  { "sigma_albedo", &P.sigma_albedo, LRT_DENOISE_SIGMA_ALBEDO }, { "eps_a", &P.eps_a, LRT_DENOISE_EPS_A } };
+    for (auto &f : fields) {
+        if (*f.v == 0.f) *f.v = f.def;
+        if (!(*f.v > 0.f) || !std::isfinite(*f.v)) return fail(LRT_ERR_INVALID, std::string("lrt_denoiser_create: ") + f.name + " must be positive and finite (0 selects the default)");
+    }
+    LRT_TRY
+        lrt_denoiser *d = new lrt_denoiser();
+        d->width = width; d->height = height; d->albedo = use_albedo != 0; d->normals = use_normals != 0; d->alpha = denoise_alpha != 0; d->params = P;
+        try { d->dev = denoiser_create(width, height, d->albedo, d->normals, d->alpha, P, device); } catch (...) { delete d; throw; }
+        *out = d;
+        return LRT_OK;
+    LRT_CATCH
+}
+
+lrt_status lrt_denoise(lrt_denoiser *denoiser, const float *noisy, int channels, const float *albedo, const float *normals, float *out, int device_buffers) {
+    if (!denoiser || !noisy || !out) return fail(LRT_ERR_INVALID, "lrt_denoise: null argument");
+    if (channels != 3 && channels != 4) return fail(LRT_ERR_INVALID, "lrt_denoise: " + std::to_string(channels) + " channels (expected 3 or 4)");
+    if (denoiser->albedo && !albedo) return fail(LRT_ERR_INVALID, "lrt_denoise: the denoiser was created with the albedo guide, but no albedo was given");
+    if (!denoiser->albedo && albedo) return fail(LRT_ERR_INVALID, "lrt_denoise: an albedo was given, but the denoiser was created without the albedo guide");
+    if (denoiser->normals && !normals) return fail(LRT_ERR_INVALID, "lrt_denoise: the denoiser was created with the normals guide, but no normals were given");
+    if (!denoiser->normals && normals) return fail(LRT_ERR_INVALID, "lrt_denoise: normals were given, but the denoiser was created without the normals guide");
+    if (out == noisy || out == albedo || out == normals) return fail(LRT_ERR_INVALID, "lrt_denoise: out must not alias an input");
+    LRT_TRY
+        denoiser_run(denoiser->dev, noisy, channels, albedo, normals, out, device_buffers);
+        return LRT_OK;
+    LRT_CATCH
+}
+
+void lrt_denoiser_free(lrt_denoiser *denoiser) { if (denoiser) { denoiser_destroy(denoiser->dev); delete denoiser; } }
+
+lrt_status lrt_denoiser_get(const lrt_denoiser *denoiser, int *width, int *height, lrt_denoise_params *params) {
+    if (!denoiser) return fail(LRT_ERR_INVALID, "lrt_denoiser_get: null argument");
+    if (width) *width = denoiser->width;
+    if (height) *height = denoiser->height;
+    if (params) *params = denoiser->params;
+    return LRT_OK;
+}
+
+lrt_status lrt_image_read_named(const char *path, int *width, int *height, int *channels, float **data, char **names) {
+    if (!path || !width || !height || !channels || !data || !names) return fail(LRT_ERR_INVALID, "lrt_image_read_named: null argument");
+    *data = nullptr; *names = nullptr;
+    LRT_TRY
+        std::string ps = path, ext; size_t dot = ps.rfind('.'); if (dot != std::string::npos) ext = ps.substr(dot + 1);
+        for (auto &c : ext) c = (char) tolower(c);
+        Image im; std::string joined;
+        if (ext == "exr") {
+            Image e = read_exr(ps);
+            auto idx = [&](const char *n) { for (size_t k = 0; k < e.channel_names.size(); ++k) if (e.channel_names[k] == n) return (int) k; return -1; };
+            int r = idx("R"), g = idx("G"), b = idx("B"), a = idx("A"), yc = idx("Y");
+            std::vector<int> map;
+            if (r >= 0 && g >= 0 && b >= 0) { map = { r, g, b }; if (a >= 0) map.push_back(a); }
+            else if (yc >= 0) { map = { yc }; if (a >= 0) map.push_back(a); }
+            for (int k = 0; k < e.channels; ++k) { bool used = false; for (int m : map) used = used || m == k; if (!used) map.push_back(k); }
+            im.width = e.width; im.height = e.height; im.channels = e.channels; im.data.resize(e.data.size());
+            for (size_t p = 0; p < (size_t) e.width * e.height; ++p)
+                for (size_t c = 0; c < map.size(); ++c) im.data[p * map.size() + c] = e.data[p * e.channels + map[c]];
+            for (size_t c = 0; c < map.size(); ++c) { if (c) joined += '\n'; joined += e.channel_names[map[c]]; }
+        } else im = read_image_rgb(ps);
+        float *p = (float *) malloc(std::max<size_t>(im.data.size(), 1) * sizeof(float));
+        char *nm = (char *) malloc(joined.size() + 1);
+        if (!p || !nm) { free(p); free(nm); throw std::runtime_error("out of memory"); }
+        memcpy(p, im.data.data(), im.data.size() * sizeof(float)); memcpy(nm, joined.c_str(), joined.size() + 1);
+        *width = im.width; *height = im.height; *channels = im.channels; *data = p; *names = nm;
+        return LRT_OK;
+    LRT_CATCH
+}
+
+void lrt_image_free_names(char *names) { free(names); }
 
 } // extern "C"

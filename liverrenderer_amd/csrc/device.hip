@@ -6,6 +6,7 @@
 #include "kernels_prb.h"
 #include "kernels_vae.h"
 #include "kernels_aov.h"
+#include "kernels_denoise.h"
 #include <functional>
 #include "bvh.h"
 #include <cmath>
@@ -1512,6 +1513,83 @@ void device_math_eval(int fn, const float *x, const float *y, uint32_t n, float 
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpy(out, d1.p, (size_t) n * 4, hipMemcpyDeviceToHost));
     if (out2) HIP_CHECK(hipMemcpy(out2, d2.p, (size_t) n * 4, hipMemcpyDeviceToHost));
+}
+
+// ---- guided denoiser (kernels_denoise.h)
+struct Denoiser {
+    int device = 0, w = 0, h = 0;
+    bool alb = false, nrm = false, alpha = false;
+    lrt_denoise_params prm{};
+    hipStream_t stream = nullptr;
+    float4 *colour[2] = { nullptr, nullptr }, *g_normal = nullptr, *g_albedo = nullptr;     // packed planes, ping-pong colour
+    float *s_noisy = nullptr, *s_albedo = nullptr, *s_normals = nullptr, *s_out = nullptr;  // staging for host pointers
+    ~Denoiser() {
+        (void) hipSetDevice(device);
+        if (stream) (void) hipStreamSynchronize(stream);
+        for (void *p : { (void *) colour[0], (void *) colour[1], (void *) g_normal, (void *) g_albedo, (void *) s_noisy, (void *) s_albedo, (void *) s_normals, (void *) s_out })
+            if (p) (void) hipFree(p);
+        if (stream) (void) hipStreamDestroy(stream);
+    }
+};
+
+Denoiser *denoiser_create(int width, int height, bool use_albedo, bool use_normals, bool denoise_alpha, const lrt_denoise_params &params, int device) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) throw std::runtime_error("no HIP device available: the hip_ad_rgb back-end has no CPU fallback");
+    if (device < 0 || device >= count) throw std::runtime_error("invalid HIP device ordinal " + std::to_string(device));
+    HIP_CHECK(hipSetDevice(device));
+    Denoiser *D = new Denoiser();
+    try {
+        D->device = device; D->w = width; D->h = height; D->alb = use_albedo; D->nrm = use_normals; D->alpha = denoise_alpha; D->prm = params;
+        HIP_CHECK(hipStreamCreateWithFlags(&D->stream, hipStreamNonBlocking));
+        size_t np = (size_t) width * height;
+        for (int k = 0; k < 2; ++k) HIP_CHECK(hipMalloc((void **) &D->colour[k], np * 16));
+        if (use_normals) { HIP_CHECK(hipMalloc((void **) &D->g_normal, np * 16)); HIP_CHECK(hipMalloc((void **) &D->s_normals, np * 12)); }
+        if (use_albedo)  { HIP_CHECK(hipMalloc((void **) &D->g_albedo, np * 16)); HIP_CHECK(hipMalloc((void **) &D->s_albedo, np * 12)); }
+        HIP_CHECK(hipMalloc((void **) &D->s_noisy, np * 16)); HIP_CHECK(hipMalloc((void **) &D->s_out, np * 16));
+    } catch (...) { delete D; throw; }
+    return D;
+}
+
+void denoiser_destroy(Denoiser *d) { delete d; }
+
+template <bool ALB, bool NRM, bool ALPHA>
+static void denoise_launch(Denoiser *D, const float *noisy, int channels, const float *albedo, const float *normals, float *out) {
+    hipStream_t st = D->stream;
+    uint32_t np = (uint32_t) ((size_t) D->w * D->h);
+    const lrt_denoise_params &P = D->prm;
+    k_denoise_pack<ALB, NRM, ALPHA><<<(np + 255) / 256, 256, 0, st>>>(noisy, channels, albedo, normals, P.eps_a, np, D->colour[0], D->g_normal, D->g_albedo);
+    HIP_CHECK(hipGetLastError());
+    // the three inverse tolerances, each one float32 operation after another: 4^k / sigma_color^2, 1 / sigma_normal^2, 1 / sigma_albedo^2
+    float sc2 = P.sigma_color * P.sigma_color, in = 1.f / (P.sigma_normal * P.sigma_normal), ia = 1.f / (P.sigma_albedo * P.sigma_albedo);
+    dim3 block(LRT_DN_BX, LRT_DN_BY), grid((D->w + LRT_DN_BX - 1) / LRT_DN_BX, (D->h + LRT_DN_BY - 1) / LRT_DN_BY);
+    for (int k = 0; k < P.iterations; ++k) {
+        float ic = (float) (1u << (2 * k)) / sc2;
+        k_denoise_pass<ALB, NRM, ALPHA><<<grid, block, 0, st>>>(D->colour[k & 1], D->g_normal, D->g_albedo, D->colour[(k + 1) & 1], D->w, D->h, 1 << k, ic, in, ia);
+        HIP_CHECK(hipGetLastError());
+    }
+    k_denoise_unpack<ALB><<<(np + 255) / 256, 256, 0, st>>>(D->colour[P.iterations & 1], D->g_albedo, noisy, channels, P.eps_a, np, out);
+    HIP_CHECK(hipGetLastError());
+}
+
+void denoiser_run(Denoiser *D, const float *noisy, int channels, const float *albedo, const float *normals, float *out, int device_buffers) {
+    HIP_CHECK(hipSetDevice(D->device));
+    hipStream_t st = D->stream;
+    size_t np = (size_t) D->w * D->h;
+    const float *d_noisy = noisy, *d_albedo = albedo, *d_normals = normals; float *d_out = out;
+    if (!device_buffers) {
+        HIP_CHECK(hipMemcpyAsync(D->s_noisy, noisy, np * channels * 4, hipMemcpyHostToDevice, st)); d_noisy = D->s_noisy;
+        if (D->alb) { HIP_CHECK(hipMemcpyAsync(D->s_albedo, albedo, np * 12, hipMemcpyHostToDevice, st)); d_albedo = D->s_albedo; }
+        if (D->nrm) { HIP_CHECK(hipMemcpyAsync(D->s_normals, normals, np * 12, hipMemcpyHostToDevice, st)); d_normals = D->s_normals; }
+        d_out = D->s_out;
+    }
+    bool alpha = D->alpha && channels == 4;
+    #define LRT_DN_CASE(A, N, AL) if (D->alb == A && D->nrm == N && alpha == AL) denoise_launch<A, N, AL>(D, d_noisy, channels, d_albedo, d_normals, d_out);
+    LRT_DN_CASE(false, false, false) LRT_DN_CASE(false, false, true) LRT_DN_CASE(false, true, false) LRT_DN_CASE(false, true, true)
+    LRT_DN_CASE(true, false, false)  LRT_DN_CASE(true, false, true)  LRT_DN_CASE(true, true, false)  LRT_DN_CASE(true, true, true)
+    #undef LRT_DN_CASE
+    if (!device_buffers) HIP_CHECK(hipMemcpyAsync(out, D->s_out, np * channels * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
 }
 
 } // namespace lrt

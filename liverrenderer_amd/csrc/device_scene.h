@@ -22,6 +22,11 @@ void device_vae_scatter(const float *blob, uint32_t n, const float *in_pos, cons
                         const float sigma_t[3], float fit_scale, uint32_t seed, float *out_pos, float *out_absorption, int device);
 void device_render_backward(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, const float *grad_image, lrt_param_grads *out, lrt_render_stats &stats);
 void device_math_eval(int fn, const float *x, const float *y, uint32_t n, float *out, float *out2, int device);   // test hook: dmath.h on the device
+// guided denoiser (kernels_denoise.h): the workspace and a non-blocking stream belong to the object; `params` arrives resolved (no zeros)
+struct Denoiser;
+Denoiser *denoiser_create(int width, int height, bool use_albedo, bool use_normals, bool denoise_alpha, const lrt_denoise_params &params, int device);
+void denoiser_destroy(Denoiser *d);
+void denoiser_run(Denoiser *d, const float *noisy, int channels, const float *albedo, const float *normals, float *out, int device_buffers);
 // one process, several devices: tiles over the devices, one RCCL all-reduce of the film / of the 7 gradient doubles (device.hip)
 struct MultiContext;
 void multi_context_destroy(MultiContext *m);
