@@ -254,7 +254,7 @@ typedef struct {
 typedef struct lrt_scene lrt_scene;
 
 LRT_API const char *lrt_last_error(void);
-LRT_API int         lrt_version(void);   /* 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
+LRT_API int         lrt_version(void);   /* 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
 
 LRT_API lrt_status lrt_scene_load_xml(const char *path, const char *const *defines,
                                       int n_defines, lrt_scene **out);
@@ -271,7 +271,8 @@ LRT_API void       lrt_scene_free(lrt_scene *scene);
  * Film::prepare / SamplingIntegrator::render do before a render); with opts->output_on_device the two pointers are device
  * memory and the call returns after the library's stream has finished with them.  A tile shard (tile_count > 1) fills only
  * its own tiles' samples into the full-size film: shard films add up to the unsharded film.
- * On a scene loaded with an `aov` integrator this renders the description's integrator (the first nested one): see lrt_render_aov.  */
+ * On a scene loaded with an `aov` integrator this renders the description's integrator (the first nested one): see lrt_render_aov;
+ * on one loaded with a `moment` integrator [v110] the nested integrator alone: see lrt_render_moment.  */
 LRT_API lrt_status lrt_render(lrt_scene *scene, const lrt_render_opts *opts,
                               float *film_raw, float *image);
 LRT_API lrt_status lrt_render_stats_get(const lrt_scene *scene, lrt_render_stats *out);
@@ -404,6 +405,39 @@ LRT_API lrt_status lrt_render_aov_samples(lrt_scene *scene, const lrt_render_opt
  * permuted to match).  data: h * w * n_channels floats in the order of `names`. */
 LRT_API lrt_status lrt_image_write_exr_channels(const char *path, int width, int height, int n_channels,
                                                 const char *const *names, const float *data);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * The `moment` integrator [v110] (src/integrators/moment.cpp, *_rgb variants): beside the nested integrator's image, per pixel,
+ * the first and second moments of its samples in CIE XYZ - what a variance image and the Z-test of
+ * src/render/tests/test_renders.py:159-228 are computed from.  As with `aov`, the scene description stays an ordinary one:
+ * lrt_scene_desc.integrator holds the nested integrator, so lrt_render on a moment scene renders that integrator alone.
+ * Per camera sample with radiance L (path.cpp:342-345 zeroes an invalid sample first), DESIGN.md section 10.1:
+ *   X = fmaf(m02, B, fmaf(m01, G, m00 * R)), Y and Z with rows 1 and 2 of srgb_to_xyz (include/mitsuba/core/spectrum.h:396-402),
+ *   m2_X = X * X, ... - all in float32, and all channels go through the reconstruction filter with the sample's weight.
+ * Raw film:        R, G, B, [A], W, X, Y, Z, m2_X, m2_Y, m2_Z     (n_raw_channels: 10, 11 with alpha; hdrfilm.cpp:245-258)
+ * Developed image: R, G, B, [A],    X, Y, Z, m2_X, m2_Y, m2_Z     (n_channels: 9 or 10), each divided by W (by 1 where W = 0).
+ * One nested integrator (path, volpath, volpathmis, biovolpath, biovolpath06); two or more, a nested aov / moment / prbvolpath:
+ * LRT_ERR_UNSUPPORTED at load time; none: LRT_ERR_INVALID, as in the reference.                                            */
+typedef struct {
+    lrt_integrator_desc integrator;          /* the nested integrator (= lrt_scene_desc.integrator)                            */
+    char    name[LRT_AOV_NAME_LEN];          /* its property name: the XML `name`, the dict key, "_arg_0" for an unnamed child  */
+    int32_t n_channels;                      /* developed channels                                                             */
+    int32_t n_raw_channels;                  /* film channels (with W)                                                         */
+} lrt_moment_desc;
+/* LRT_ERR_INVALID when the scene has no moment integrator. */
+LRT_API lrt_status lrt_scene_moment_get(const lrt_scene *scene, lrt_moment_desc *out);
+/* Name of developed channel c (0 <= c < n_channels): "R", "G", "B", ["A"], "<name>.X", ".Y", ".Z", "m2_<name>.X", ".Y", ".Z";
+ * NULL when the scene has no moment integrator or c is out of range.  The string lives as long as the scene. */
+LRT_API const char *lrt_moment_channel_name(const lrt_scene *scene, int c);
+/* film_raw: crop_h * crop_w * n_raw_channels floats; image: crop_h * crop_w * n_channels floats; either may be NULL.  Passes
+ * (samples_per_pass), crop windows, output_on_device, tile_rank / tile_count (the film is linear in the samples: shard films add
+ * up) and the statistics are those of lrt_render.  opts->integrator / max_depth / rr_depth / hide_emitters must be "use the
+ * scene's" (LRT_ERR_INVALID otherwise).  lrt_render_multi, lrt_render_backward and lrt_render_backward_multi on a moment scene
+ * are LRT_ERR_UNSUPPORTED. */
+LRT_API lrt_status lrt_render_moment(lrt_scene *scene, const lrt_render_opts *opts, float *film_raw, float *image);
+/* Test hook: X, Y, Z, m2_X, m2_Y, m2_Z of lanes [lane_begin, lane_begin + n) before film accumulation (first pass only, as
+ * lrt_render_samples), through the device function the film kernel uses: out is n * 6 floats. */
+LRT_API lrt_status lrt_render_moment_samples(lrt_scene *scene, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Learned subsurface model, network stage only: the shape-adaptive scatter network of

@@ -15,7 +15,7 @@ from ._lib import make_opts
 
 __all__ = ["set_variant", "variant", "variants", "load_file", "load_string", "load_dict", "cornell_box", "render",
            "traverse", "Scene", "ScalarTransform4f", "render_stats", "write_volume_grid", "Bitmap", "Struct", "util", "read_image", "write_exr", "write_png",
-           "Denoiser", "OptixDenoiser", "denoise"]
+           "Denoiser", "OptixDenoiser", "denoise", "moment_variance", "z_test"]
 
 _VARIANT = "hip_ad_rgb"
 
@@ -114,7 +114,7 @@ def cornell_box():
 
 # ------------------------------------------------------------- dict -> XML
 _TAGS = {
-    "scene": "scene", "path": "integrator", "volpath": "integrator", "prbvolpath": "integrator", "aov": "integrator",
+    "scene": "scene", "path": "integrator", "volpath": "integrator", "prbvolpath": "integrator", "aov": "integrator", "moment": "integrator",
     "biovolpath": "integrator", "biovolpath06": "integrator", "volpathmis": "integrator",
     "perspective": "sensor", "independent": "sampler", "ldsampler": "sampler", "hdrfilm": "film",
     "box": "rfilter", "gaussian": "rfilter", "tent": "rfilter",
@@ -159,7 +159,7 @@ def _dict_to_xml(name, d, out, indent, top_ids, parent=None):
                 and not (tag == "emitter" and name == "emitter"):
             attrs += f' name="{_esc(name)}"'
         elif tag == "integrator" and parent == "integrator":
-            attrs += f' name="{_esc(name)}"'            # a nested integrator of `aov`: the key names its image (aov.cpp:115-125)
+            attrs += f' name="{_esc(name)}"'            # a nested integrator of `aov` / `moment`: the key names its channels (aov.cpp:115-125, moment.cpp:52-60)
     out.append(f"{indent}<{tag}{attrs}>")
     sub = indent + "    "
     for k, v in d.items():
@@ -282,14 +282,57 @@ class Scene:
         _lib.check(self._lib.lrt_render_aov(self._h, C.byref(o), raw.ctypes.data if return_raw else None, img.ctypes.data))
         return (img, raw) if return_raw else img
 
+    # -- the moment integrator ---------------------------------------------
+    def moment_desc(self):
+        """lrt_moment_desc of a scene loaded with a `moment` integrator, None for any other scene."""
+        m = _lib.MomentDesc()
+        return m if self._lib.lrt_scene_moment_get(self._h, C.byref(m)) == _lib.OK else None
+
+    def is_moment(self):
+        return self.moment_desc() is not None
+
+    def moment_channel_names(self):
+        """Names of the channels render() returns on a moment scene: R, G, B, [A], <name>.X/.Y/.Z, m2_<name>.X/.Y/.Z."""
+        m = self.moment_desc()
+        if m is None:
+            raise RuntimeError("moment_channel_names(): the scene has no moment integrator")
+        return [self._lib.lrt_moment_channel_name(self._h, c).decode() for c in range(m.n_channels)]
+
+    def render_moment_samples(self, lane_begin, n, **kw):
+        """lrt_render_moment_samples (test hook): X, Y, Z, m2_X, m2_Y, m2_Z of lanes [lane_begin, lane_begin + n) before film
+        accumulation (first pass): (n, 6) float32."""
+        if not self.is_moment():
+            raise RuntimeError("render_moment_samples(): the scene has no moment integrator")
+        out = np.empty((n, 6), dtype=np.float32)
+        o = make_opts(None, None, None, None, kw.get("spp", 0), kw.get("seed", 0), 0, 1, kw.get("device", 0))
+        _lib.check(self._lib.lrt_render_moment_samples(self._h, C.byref(o), int(lane_begin), int(n), out.ctypes.data))
+        return out
+
+    def _render_moment(self, m, spp, seed, integrator, max_depth, rr_depth, hide_emitters, tile_rank, tile_count, device, return_raw):
+        f = self.desc.film
+        img = np.empty((f.crop_height, f.crop_width, m.n_channels), dtype=np.float32)
+        raw = np.empty((f.crop_height, f.crop_width, m.n_raw_channels), dtype=np.float32) if return_raw else None
+        o = make_opts(integrator, max_depth, rr_depth, hide_emitters, spp, seed, tile_rank, tile_count, device)
+        _lib.check(self._lib.lrt_render_moment(self._h, C.byref(o), raw.ctypes.data if return_raw else None, img.ctypes.data))
+        return (img, raw) if return_raw else img
+
+    def render_moment_to_device(self, film_ptr, image_ptr=None, **kw):
+        """lrt_render_moment into caller-provided DEVICE buffers (n_raw_channels / n_channels floats per pixel)."""
+        o = make_opts(None, None, None, None, kw.get("spp", 0), kw.get("seed", 0), kw.get("tile_rank", 0), kw.get("tile_count", 1), kw.get("device", 0), True)
+        _lib.check(self._lib.lrt_render_moment(self._h, C.byref(o), C.c_void_p(film_ptr) if film_ptr else None, C.c_void_p(image_ptr) if image_ptr else None))
+
     # -- rendering ---------------------------------------------------------
     def render(self, spp=0, seed=0, integrator=None, max_depth=None, rr_depth=None, hide_emitters=None,
                tile_rank=0, tile_count=1, device=0, return_raw=False):
         """Developed H x W x (3|4) image; on a scene with an `aov` integrator H x W x n_channels (aov_channel_names()), and with
-        return_raw the AOV pass's film (AOV channels, then W) as the second value."""
+        return_raw the AOV pass's film (AOV channels, then W) as the second value; on a scene with a `moment` integrator
+        H x W x n_channels (moment_channel_names()), and with return_raw the moment film (R,G,B,[A],W,X,Y,Z,m2X,m2Y,m2Z)."""
         a = self.aov_desc()
         if a is not None:
             return self._render_aov(a, spp, seed, integrator, max_depth, rr_depth, hide_emitters, tile_rank, tile_count, device, return_raw)
+        m = self.moment_desc()
+        if m is not None:
+            return self._render_moment(m, spp, seed, integrator, max_depth, rr_depth, hide_emitters, tile_rank, tile_count, device, return_raw)
         h, w, c = self.film_shape()
         img = np.empty((h, w, c), dtype=np.float32)
         raw = np.empty((h, w, self.raw_channels()), dtype=np.float32) if return_raw else None
@@ -491,7 +534,8 @@ def load_dict(d, base_dir="."):
 
 def render(scene, spp=0, seed=0, integrator=None, **kw):
     """mi.render(scene, spp=..., seed=...): developed H x W x (3|4) float32 image (an aov scene: H x W x n_channels, the inner
-    images then the AOVs, channel names from scene.aov_channel_names())."""
+    images then the AOVs, channel names from scene.aov_channel_names(); a moment scene: R,G,B,[A] then the XYZ means and second
+    moments, scene.moment_channel_names())."""
     return scene.render(spp=spp, seed=seed, integrator=integrator, **kw)
 
 
@@ -849,3 +893,54 @@ def denoise(scene_image, scene, **params):
         guide[key] = None if k is None else bmp.select(a.aov_names[k].value.decode())
     dn = Denoiser((img.shape[1], img.shape[0]), albedo=guide["albedo"] is not None, normals=guide["normals"] is not None, **params)
     return dn(noisy, guide["albedo"], guide["normals"])
+
+
+# ---- error bars from a moment render (src/integrators/moment.cpp; src/render/tests/test_renders.py:159-228)
+def moment_variance(image, scene, spp):
+    """(variance, mean): from what mi.render returns on a `moment` scene, the per-pixel variance OF THE MEAN of X, Y, Z over the
+    pixel's `spp` samples, (m2 - m1 * m1) / (spp - 1) in float64 clamped at 0, and the XYZ means m1; both H x W x 3.
+    Exact for the box filter only: with a wider reconstruction filter the samples that reach a pixel carry unequal weights, and
+    the developed channels are weighted means."""
+    m = scene.moment_desc()
+    if m is None:
+        raise RuntimeError("moment_variance(): the scene has no moment integrator")
+    img = np.asarray(image, dtype=np.float64)
+    if img.ndim != 3 or img.shape[2] != m.n_channels:
+        raise RuntimeError(f"moment_variance(): the image has shape {tuple(img.shape)}, the scene renders {m.n_channels} channels")
+    if int(spp) < 2:
+        raise ValueError("moment_variance(): a variance needs spp >= 2")
+    o = m.n_channels - 6
+    m1, m2 = img[..., o:o + 3], img[..., o + 3:o + 6]
+    return np.maximum((m2 - m1 * m1) / (int(spp) - 1), 0.0), m1.copy()
+
+
+def z_test(mean_a, var_a, mean_b, var_b, alpha=0.01):
+    """(p_values, pass_fraction) of the per-pixel two-sided Z-test of test_renders.py:159-176 on the difference of two estimates
+    with known variances OF THE MEAN: z = |a - b| / sqrt(var_a + var_b), p = erfc(z / sqrt(2)); a pixel passes when
+    p > 1 - (1 - alpha)^(1 / N), the Sidak correction over the N = H * W pixels.  A pixel whose two variances are both 0 has no
+    error bar: it passes (p = 1) when the two means are equal and fails (p = 0) otherwise; it counts in the denominator.
+    The reference accepts when at least 99.75 % of the pixels pass (test_renders.py:228)."""
+    a, b = np.asarray(mean_a, dtype=np.float64), np.asarray(mean_b, dtype=np.float64)
+    va, vb = np.asarray(var_a, dtype=np.float64), np.asarray(var_b, dtype=np.float64)
+    if not (a.shape == b.shape == va.shape == vb.shape):
+        raise ValueError(f"z_test(): shapes differ: {a.shape}, {va.shape}, {b.shape}, {vb.shape}")
+    if a.size == 0 or not 0.0 < alpha < 1.0:
+        raise ValueError("z_test(): empty input, or alpha outside (0, 1)")
+    if (va < 0).any() or (vb < 0).any():
+        raise ValueError("z_test(): negative variance")
+    n_pixels = a.shape[0] * a.shape[1] if a.ndim >= 2 else a.size
+    d, var = np.abs(a - b), va + vb
+    p = np.where(d == 0.0, 1.0, 0.0)                       # no error bar: equal or not
+    bar = var != 0.0
+    with np.errstate(invalid="ignore"):
+        z = d[bar] / np.sqrt(var[bar])                     # NaN (a non-finite mean or variance) fails: p = 0
+    ok = z == z
+    pz = np.zeros(z.shape, dtype=np.float64)
+    pz[ok] = _erfc(z[ok] / math.sqrt(2.0)).astype(np.float64) if ok.any() else 0.0
+    p[bar] = pz
+    level = 1.0 - (1.0 - alpha) ** (1.0 / n_pixels)
+    # with H x W x 3 input the fraction is over all H * W * 3 values while the correction counts pixels, as test_renders.py:224-228
+    return p, float(np.count_nonzero(p > level)) / p.size
+
+
+_erfc = np.frompyfunc(math.erfc, 1, 1)                     # scipy may be absent; one C-level loop over the pixels that have an error bar

@@ -92,6 +92,11 @@ class AovDesc(C.Structure):
                 ("n_aov_channels", C.c_int32), ("n_channels", C.c_int32)]
 
 
+class MomentDesc(C.Structure):
+    """lrt_moment_desc: the moment integrator's nested integrator, its name and the channel counts (include/liverrt.h)."""
+    _fields_ = [("integrator", IntegratorDesc), ("name", C.c_char * AOV_NAME_LEN), ("n_channels", C.c_int32), ("n_raw_channels", C.c_int32)]
+
+
 class RenderOpts(C.Structure):
     _fields_ = [("integrator", C.c_int32), ("max_depth", C.c_int32), ("rr_depth", C.c_int32), ("hide_emitters", C.c_int32),
                 ("spp", C.c_uint32), ("seed", C.c_uint32), ("tile_rank", C.c_uint32), ("tile_count", C.c_uint32),
@@ -207,6 +212,11 @@ def lib():
     L.lrt_aov_channel_name.restype = C.c_char_p
     L.lrt_render_aov.argtypes = [C.c_void_p, P(RenderOpts), C.c_void_p, C.c_void_p]
     L.lrt_render_aov_samples.argtypes = [C.c_void_p, P(RenderOpts), C.c_uint64, C.c_uint32, C.c_void_p]
+    L.lrt_scene_moment_get.argtypes = [C.c_void_p, P(MomentDesc)]
+    L.lrt_moment_channel_name.argtypes = [C.c_void_p, C.c_int]
+    L.lrt_moment_channel_name.restype = C.c_char_p
+    L.lrt_render_moment.argtypes = [C.c_void_p, P(RenderOpts), C.c_void_p, C.c_void_p]
+    L.lrt_render_moment_samples.argtypes = [C.c_void_p, P(RenderOpts), C.c_uint64, C.c_uint32, C.c_void_p]
     L.lrt_denoiser_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(DenoiseParams), C.c_int, P(C.c_void_p)]
     L.lrt_denoise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.lrt_denoiser_free.argtypes = [C.c_void_p]
@@ -215,7 +225,7 @@ def lib():
     L.lrt_image_read_named.argtypes = [C.c_char_p, P(C.c_int), P(C.c_int), P(C.c_int), P(P(C.c_float)), P(C.c_void_p)]
     L.lrt_image_free_names.argtypes = [C.c_void_p]
     L.lrt_image_free_names.restype = None
-    for name in ("lrt_denoiser_create", "lrt_denoise", "lrt_denoiser_get", "lrt_image_read_named"):
+    for name in ("lrt_denoiser_create", "lrt_denoise", "lrt_denoiser_get", "lrt_image_read_named", "lrt_scene_moment_get", "lrt_render_moment", "lrt_render_moment_samples"):
         getattr(L, name).restype = C.c_int
     for name in ("lrt_image_read", "lrt_image_write_exr", "lrt_image_write_png", "lrt_scene_load_xml", "lrt_scene_load_xml_string", "lrt_scene_from_desc", "lrt_render", "lrt_render_multi", "lrt_render_backward_multi", "lrt_math_eval", "lrt_render_stats_get",
                  "lrt_film_develop", "lrt_render_samples", "lrt_render_backward", "lrt_trace", "lrt_emitter_probe", "lrt_param_set", "lrt_param_get",
@@ -231,7 +241,8 @@ EXPORTED_SYMBOLS = ["lrt_last_error", "lrt_version", "lrt_scene_load_xml", "lrt_
                     "lrt_image_read", "lrt_image_free", "lrt_image_write_exr", "lrt_image_write_png",
                     "lrt_vae_model_create", "lrt_vae_model_free", "lrt_vae_scatter",
                     "lrt_scene_aov_get", "lrt_aov_channel_name", "lrt_render_aov", "lrt_render_aov_samples", "lrt_image_write_exr_channels",
-                    "lrt_denoiser_create", "lrt_denoise", "lrt_denoiser_free", "lrt_denoiser_get", "lrt_image_read_named", "lrt_image_free_names"]
+                    "lrt_denoiser_create", "lrt_denoise", "lrt_denoiser_free", "lrt_denoiser_get", "lrt_image_read_named", "lrt_image_free_names",
+                    "lrt_scene_moment_get", "lrt_moment_channel_name", "lrt_render_moment", "lrt_render_moment_samples"]
 
 
 def check(status):

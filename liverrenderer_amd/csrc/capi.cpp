@@ -28,7 +28,7 @@ static lrt_status fail(lrt_status st, const std::string &msg) { g_error = msg; r
 extern "C" {
 
 const char *lrt_last_error(void) { return g_error.c_str(); }
-int lrt_version(void) { return 109; }    // 1.9: the guided denoiser (lrt_denoiser_create / lrt_denoise / lrt_denoiser_free), lrt_image_read_named; 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
+int lrt_version(void) { return 110; }    // 1.10: the moment integrator (lrt_render_moment, lrt_render_moment_samples, lrt_scene_moment_get, lrt_moment_channel_name); 1.9: the guided denoiser (lrt_denoiser_create / lrt_denoise / lrt_denoiser_free), lrt_image_read_named; 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
 
 static std::vector<std::pair<std::string, std::string>> parse_defines(const char *const *defines, int n) {
     std::vector<std::pair<std::string, std::string>> r;
@@ -189,6 +189,7 @@ lrt_status lrt_render_multi(lrt_scene *scene, const lrt_render_opts *opts, int n
     if (!scene) return fail(LRT_ERR_INVALID, "lrt_render_multi: null scene");
     LRT_TRY
         if (scene->st.has_aov) return fail(LRT_ERR_UNSUPPORTED, "lrt_render_multi: an aov scene renders on one device (lrt_render_aov)");
+        if (scene->st.has_moment) return fail(LRT_ERR_UNSUPPORTED, "lrt_render_multi: a moment scene renders on one device (lrt_render_moment; shard it with tile_rank / tile_count)");
         if (opts && (opts->tile_count > 1 || opts->tile_rank != 0)) throw std::invalid_argument("lrt_render_multi shards the image itself: tile_rank / tile_count must be 0 / 1 (or 0 / 0)");
         ensure_devices(scene, n_devices, device_ids);
         device_render_multi(scene->multi, scene->multi_ctx, scene->st.desc, opts, film_raw, image, scene->stats);
@@ -200,6 +201,7 @@ lrt_status lrt_render_backward_multi(lrt_scene *scene, const lrt_render_opts *op
     if (!scene || !grad_image || !out) return fail(LRT_ERR_INVALID, "lrt_render_backward_multi: null argument");
     LRT_TRY
         if (scene->st.has_aov) return fail(LRT_ERR_UNSUPPORTED, "lrt_render_backward_multi: the aov integrator has no adjoint here");
+        if (scene->st.has_moment) return fail(LRT_ERR_UNSUPPORTED, "lrt_render_backward_multi: the moment integrator has no adjoint here");
         if (opts && (opts->tile_count > 1 || opts->tile_rank != 0)) throw std::invalid_argument("lrt_render_backward_multi shards the image itself: tile_rank / tile_count must be 0 / 1 (or 0 / 0)");
         ensure_devices(scene, n_devices, device_ids);
         device_render_backward_multi(scene->multi, scene->multi_ctx, scene->st.desc, opts, grad_image, out, scene->stats);
@@ -241,6 +243,7 @@ lrt_status lrt_render_samples(lrt_scene *scene, const lrt_render_opts *opts, uin
 lrt_status lrt_render_backward(lrt_scene *scene, const lrt_render_opts *opts, const float *grad_image, lrt_param_grads *out) {
     if (!scene || !grad_image || !out) return fail(LRT_ERR_INVALID, "lrt_render_backward: null argument");
     if (scene->st.has_aov) return fail(LRT_ERR_UNSUPPORTED, "lrt_render_backward: the aov integrator has no adjoint here");
+    if (scene->st.has_moment) return fail(LRT_ERR_UNSUPPORTED, "lrt_render_backward: the moment integrator has no adjoint here");
     LRT_TRY
         ensure_device(scene, opts ? opts->device : 0);
         device_render_backward(scene->dev, scene->st.desc, opts, grad_image, out, scene->stats);
@@ -287,6 +290,48 @@ lrt_status lrt_render_aov_samples(lrt_scene *scene, const lrt_render_opts *opts,
     LRT_TRY
         ensure_device(scene, opts ? opts->device : 0);
         device_render_aov_samples(scene->dev, scene->st.desc, scene->st.aov, opts, lane_begin, n, out, scene->stats);
+        return LRT_OK;
+    LRT_CATCH
+}
+
+// ---- the moment integrator
+lrt_status lrt_scene_moment_get(const lrt_scene *scene, lrt_moment_desc *out) {
+    if (!scene || !out) return fail(LRT_ERR_INVALID, "lrt_scene_moment_get: null argument");
+    if (!scene->st.has_moment) return fail(LRT_ERR_INVALID, "lrt_scene_moment_get: the scene has no moment integrator");
+    *out = scene->st.moment; return LRT_OK;
+}
+
+const char *lrt_moment_channel_name(const lrt_scene *scene, int c) {
+    if (!scene || !scene->st.has_moment || c < 0 || c >= (int) scene->st.moment_channel_names.size()) return nullptr;
+    return scene->st.moment_channel_names[(size_t) c].c_str();
+}
+
+// the nested integrator comes from the scene, as for aov
+static lrt_status check_moment_call(const lrt_scene *scene, const lrt_render_opts *opts, const char *fn) {
+    if (!scene->st.has_moment) return fail(LRT_ERR_INVALID, std::string(fn) + ": the scene has no moment integrator");
+    if (opts && (opts->integrator != -1 || opts->max_depth != -2 || opts->rr_depth != -1 || opts->hide_emitters != -1))
+        return fail(LRT_ERR_INVALID, std::string(fn) + ": integrator, max_depth, rr_depth and hide_emitters come from the scene's nested integrator (leave them at -1 / -2 / -1 / -1)");
+    return LRT_OK;
+}
+
+lrt_status lrt_render_moment(lrt_scene *scene, const lrt_render_opts *opts, float *film_raw, float *image) {
+    if (!scene) return fail(LRT_ERR_INVALID, "lrt_render_moment: null scene");
+    lrt_status st = check_moment_call(scene, opts, "lrt_render_moment");
+    if (st != LRT_OK) return st;
+    LRT_TRY
+        ensure_device(scene, opts ? opts->device : 0);
+        device_render_moment(scene->dev, scene->st.desc, opts, film_raw, image, scene->stats);
+        return LRT_OK;
+    LRT_CATCH
+}
+
+lrt_status lrt_render_moment_samples(lrt_scene *scene, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out) {
+    if (!scene || !out) return fail(LRT_ERR_INVALID, "lrt_render_moment_samples: null argument");
+    lrt_status st = check_moment_call(scene, opts, "lrt_render_moment_samples");
+    if (st != LRT_OK) return st;
+    LRT_TRY
+        ensure_device(scene, opts ? opts->device : 0);
+        device_render_moment_samples(scene->dev, scene->st.desc, opts, lane_begin, n, out, scene->stats);
         return LRT_OK;
     LRT_CATCH
 }

@@ -7,6 +7,7 @@
 #include "kernels_vae.h"
 #include "kernels_aov.h"
 #include "kernels_denoise.h"
+#include "kernels_moment.h"
 #include <functional>
 #include "bvh.h"
 #include <cmath>
@@ -924,20 +925,32 @@ static void run_wavefront(DeviceScene *D, const lrt_scene_desc &d, const Resolve
 
 // after_pass (the aov integrator with one nested integrator): called after each pass's colour work, while D->cur_pass_in still
 // holds the sampler states at the start of that pass
+// moment (the moment integrator, kernels_moment.h): the film has the moment channels, every filter takes the lane-buffer route and
+// k_moment_splat / k_moment_develop stand in for k_splat_lanes / k_develop
 static void render_passes(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, float *film_raw, float *image, lrt_render_stats &stats,
-                          const std::function<void(const ResolvedOpts &)> &after_pass);
+                          const std::function<void(const ResolvedOpts &)> &after_pass, bool moment = false);
 
 void device_render(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, float *film_raw, float *image, lrt_render_stats &stats) {
     render_passes(D, d, opts, film_raw, image, stats, nullptr);
 }
 
+// the instance of k_moment_splat<WIDE, ALPHA> for a reconstruction filter and a film
+static void launch_moment_splat(DeviceScene *D, bool wide, bool alpha, uint32_t grid, LaunchPtr lp) {
+    const ScenePtr sc = (ScenePtr) D->d_sc;
+    if (wide && alpha) k_moment_splat<true, true><<<grid, LRT_BLOCK, 0, D->stream>>>(sc, lp);
+    else if (wide) k_moment_splat<true, false><<<grid, LRT_BLOCK, 0, D->stream>>>(sc, lp);
+    else if (alpha) k_moment_splat<false, true><<<grid, LRT_BLOCK, 0, D->stream>>>(sc, lp);
+    else k_moment_splat<false, false><<<grid, LRT_BLOCK, 0, D->stream>>>(sc, lp);
+}
+
 static void render_passes(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, float *film_raw, float *image, lrt_render_stats &stats,
-                          const std::function<void(const ResolvedOpts &)> &after_pass) {
+                          const std::function<void(const ResolvedOpts &)> &after_pass, bool moment) {
     HIP_CHECK(hipSetDevice(D->device));
     ResolvedOpts O = resolve(d, opts);
     const DFilm &F = D->sc.film;
     bool on_device = opts && opts->output_on_device;
-    size_t np = (size_t) F.width * F.height, film_floats = np * F.channels, image_floats = np * (F.has_alpha ? 4 : 3);
+    const size_t film_channels = moment ? (F.has_alpha ? 11 : 10) : (size_t) F.channels, image_channels = moment ? film_channels - 1 : (F.has_alpha ? 4 : 3);
+    size_t np = (size_t) F.width * F.height, film_floats = np * film_channels, image_floats = np * image_channels;
     ensure_pixel_list(D, O);
     const uint64_t n_lanes = (uint64_t) D->n_owned_pixels * O.spp;            // this rank's lanes of ONE pass
     float *film = nullptr;
@@ -951,7 +964,7 @@ static void render_passes(DeviceScene *D, const lrt_scene_desc &d, const lrt_ren
         for (int k = 0; k < 2; ++k) { D->release(D->pass_state[k]); HIP_CHECK(hipMalloc((void **) &D->pass_state[k], std::max<uint64_t>(n_lanes, 1) * 8)); D->track(D->pass_state[k]); }
         D->pass_state_lanes = n_lanes;
     }
-    const bool lane_splat = F.rfilter != LRT_RFILTER_BOX && (O.n_passes > 1 || !getenv("LRT_NO_LANE_SPLAT"));
+    const bool lane_splat = moment || (F.rfilter != LRT_RFILTER_BOX && (O.n_passes > 1 || !getenv("LRT_NO_LANE_SPLAT")));
     lrt_render_stats total{};
     for (uint32_t pass = 0; pass < O.n_passes; ++pass) {                       // integrator.cpp:343-353
         O.pass = pass;
@@ -976,7 +989,10 @@ static void render_passes(DeviceScene *D, const lrt_scene_desc &d, const lrt_ren
             run_wavefront(D, d, O, base, n, pixel_list, nullptr, reinterpret_cast<float *>(D->L_buf), st1);
             DRenderParams rp = make_params(d, O, n); rp.pass_in = D->cur_pass_in;
             DLaunch a{}; a.rp = rp; a.L_buf = D->L_buf; a.pixel_list = pixel_list; a.lane_begin = base; a.n = n; a.film = film;
-            k_splat_lanes<false><<<(uint32_t) ((n + LRT_BLOCK - 1) / LRT_BLOCK), LRT_BLOCK, 0, D->stream>>>((ScenePtr) D->d_sc, push_launch(D, a));
+            const uint32_t grid = (uint32_t) ((n + LRT_BLOCK - 1) / LRT_BLOCK);
+            const LaunchPtr lp = push_launch(D, a);
+            if (!moment) k_splat_lanes<false><<<grid, LRT_BLOCK, 0, D->stream>>>((ScenePtr) D->d_sc, lp);
+            else launch_moment_splat(D, F.rfilter != LRT_RFILTER_BOX, F.has_alpha != 0, grid, lp);
             HIP_CHECK(hipGetLastError());
             total.n_samples += st1.n_samples; total.n_iter += st1.n_iter; total.n_shadow += st1.n_shadow; total.n_launches += st1.n_launches;
             total.n_records += st1.n_records; total.kernel_ms += st1.kernel_ms; total.total_ms += st1.total_ms;
@@ -990,12 +1006,39 @@ static void render_passes(DeviceScene *D, const lrt_scene_desc &d, const lrt_ren
     if (image) {
         float *img = image;
         if (!on_device) { if (D->image_floats < image_floats) { D->release(D->image); D->image = nullptr; HIP_CHECK(hipMalloc((void **) &D->image, image_floats * 4)); D->track(D->image); D->image_floats = image_floats; } img = D->image; }
-        k_develop<<<(uint32_t) ((np + 255) / 256), 256, 0, D->stream>>>(F, film, img, (uint32_t) np);
+        if (!moment) k_develop<<<(uint32_t) ((np + 255) / 256), 256, 0, D->stream>>>(F, film, img, (uint32_t) np);
+        else if (F.has_alpha) k_moment_develop<true><<<(uint32_t) ((np + 255) / 256), 256, 0, D->stream>>>(film, img, (uint32_t) np);
+        else k_moment_develop<false><<<(uint32_t) ((np + 255) / 256), 256, 0, D->stream>>>(film, img, (uint32_t) np);
         if (!on_device) HIP_CHECK(hipMemcpyAsync(image, img, image_floats * 4, hipMemcpyDeviceToHost, D->stream));
     }
     if (film_raw && !on_device) HIP_CHECK(hipMemcpyAsync(film_raw, film, film_floats * 4, hipMemcpyDeviceToHost, D->stream));
     HIP_CHECK(hipStreamSynchronize(D->stream));
     HIP_CHECK(hipGetLastError());
+}
+
+// ------------------------------------------------------------------ the moment integrator (kernels_moment.h)
+void device_render_moment(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, float *film_raw, float *image, lrt_render_stats &stats) {
+    render_passes(D, d, opts, film_raw, image, stats, nullptr, true);
+}
+
+// lrt_render_samples' lanes, then moment_values per lane
+void device_render_moment_samples(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out, lrt_render_stats &stats) {
+    HIP_CHECK(hipSetDevice(D->device));
+    ResolvedOpts O = resolve(d, opts);
+    if (lane_begin + n > 0x100000000ull) throw std::runtime_error("lane range exceeds 2^32");
+    if (!n) { stats = lrt_render_stats{}; return; }
+    float *d_buf = nullptr;                          // n float4 of radiance, then n * 6 floats of moments
+    HIP_CHECK(hipMalloc((void **) &d_buf, (size_t) n * (16 + 24)));
+    try {
+        float *d_m = d_buf + (size_t) n * 4;
+        HIP_CHECK(hipMemsetAsync(d_buf, 0, (size_t) n * 16, D->stream));
+        run_wavefront(D, d, O, lane_begin, n, nullptr, nullptr, d_buf, stats);
+        k_moment_lanes<<<(n + 255u) / 256u, 256, 0, D->stream>>>(reinterpret_cast<const float4 *>(d_buf), O.integrator == LRT_INTEGRATOR_PATH ? 1 : 0, n, d_m);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(out, d_m, (size_t) n * 24, hipMemcpyDeviceToHost, D->stream));
+        HIP_CHECK(hipStreamSynchronize(D->stream));
+    } catch (...) { (void) hipFree(d_buf); throw; }
+    HIP_CHECK(hipFree(d_buf));
 }
 
 void device_develop(DeviceScene *D, const float *film_raw, float *image, int on_device) {

@@ -14,6 +14,9 @@ void device_develop(DeviceScene *D, const float *film_raw, float *image, int on_
 // the aov integrator (kernels_aov.h): nested renders, then the first-hit AOV pass; merged image on the device
 void device_render_aov(DeviceScene *D, const lrt_scene_desc &d, const lrt_aov_desc &aov, const lrt_render_opts *opts, float *aov_film_raw, float *image, lrt_render_stats &stats);
 void device_render_aov_samples(DeviceScene *D, const lrt_scene_desc &d, const lrt_aov_desc &aov, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out, lrt_render_stats &stats);
+// the moment integrator (kernels_moment.h): the nested integrator's lanes, then the moment film (R,G,B,[A],W,X,Y,Z,m2X,m2Y,m2Z)
+void device_render_moment(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, float *film_raw, float *image, lrt_render_stats &stats);
+void device_render_moment_samples(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out, lrt_render_stats &stats);
 void device_render_samples(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out, lrt_render_stats &stats);
 void device_trace(DeviceScene *D, const lrt_rays_soa *rays, const lrt_hits_soa *hits, uint32_t n, int any_hit);
 void device_emitter_probe(DeviceScene *D, const float *ref_p, const float *sample, uint32_t n, float *out);   // test hook: emitter sampling of the EXT instances

@@ -27,6 +27,10 @@ struct SceneStorage {
     bool has_aov = false;
     lrt_aov_desc aov{};
     std::vector<std::string> aov_channel_names;
+    // `moment` integrator (loader.cpp): the nested integrator and the developed channel names
+    bool has_moment = false;
+    lrt_moment_desc moment{};
+    std::vector<std::string> moment_channel_names;
     void fix_pointers();                 // re-point desc at the vectors above
     void copy_from(const lrt_scene_desc &d);
 };

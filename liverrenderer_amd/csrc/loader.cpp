@@ -2,7 +2,7 @@
 //
 // Replaces, for the plugins the liver scenes and mi.cornell_box() use, the
 // reference's src/core/parser.cpp + Properties + PluginManager instantiation.
-// Supported plugins: integrator {path, volpath, prbvolpath, biovolpath, biovolpath06, aov}; sensor perspective;
+// Supported plugins: integrator {path, volpath, prbvolpath, biovolpath, biovolpath06, aov, moment}; sensor perspective;
 // sampler {independent, ldsampler}; film hdrfilm; rfilter {box,
 // gaussian, tent}; bsdf {diffuse, dielectric, bumpmap, null}; texture {bitmap,
 // checkerboard}; medium {homogeneous, liver, parenchyma, glissonCapsule} (the
@@ -717,7 +717,7 @@ struct Loader {
         else if (o->type == "biovolpath") I.type = LRT_INTEGRATOR_BIOVOLPATH;
         else if (o->type == "biovolpath06") I.type = LRT_INTEGRATOR_BIOVOLPATH06;
         else if (o->type == "volpathmis") I.type = LRT_INTEGRATOR_VOLPATHMIS;
-        else fail("unsupported integrator \"" + o->type + "\" (supported: path, volpath, volpathmis, prbvolpath, biovolpath, biovolpath06, aov)");
+        else fail("unsupported integrator \"" + o->type + "\" (supported: path, volpath, volpathmis, prbvolpath, biovolpath, biovolpath06, aov, moment)");
         I.max_depth = get_int(*o, "max_depth", -1); I.rr_depth = get_int(*o, "rr_depth", 5); I.hide_emitters = get_bool(*o, "hide_emitters", false);
         if (I.max_depth < 0 && I.max_depth != -1) fail("\"max_depth\" must be set to -1 (infinite) or a value >= 0");
         if (I.rr_depth <= 0) fail("\"rr_depth\" must be set to a value greater than zero!");
@@ -728,6 +728,7 @@ struct Loader {
 
     void make_integrator(const ObjP &o) {
         if (o->type == "aov") { make_aov(o); return; }
+        if (o->type == "moment") { make_moment(o); return; }
         int spass; bool spectral;
         S.desc.integrator = parse_integrator(o, &spass, &spectral);
         S.desc.samples_per_pass = spass > 0 ? (uint32_t) spass : 0u;
@@ -748,6 +749,7 @@ struct Loader {
         for (auto &c : o->children) {
             if (c.second->tag != "integrator") fail("aov: Child objects must be of type 'SamplingIntegrator'!");
             if (c.second->type == "aov") fail("aov: an aov integrator nested in another one is not supported");
+            if (c.second->type == "moment") fail("aov: a nested \"moment\" integrator is not supported");
             if (A.n_integrators == LRT_AOV_MAX_INTEGRATORS) fail("aov: more than " + std::to_string(LRT_AOV_MAX_INTEGRATORS) + " nested integrators");
             int spass; bool spectral;
             lrt_integrator_desc I = parse_integrator(c.second, &spass, &spectral);
@@ -807,6 +809,39 @@ struct Loader {
         S.desc.use_spectral_mis = mis_seen >= 0 ? (uint32_t) mis_seen : 1u;
     }
 
+    // src/integrators/moment.cpp:46-67: the nested integrator(s) are the object children; each contributes <name>.X/.Y/.Z and
+    // m2_<name>.X/.Y/.Z.  An unnamed XML child gets the parser's name "_arg_<k>", k counting the parent's unnamed object children
+    // (src/core/parser.cpp:1023-1025; the counter restarts per parent, :1047).  The description's integrator becomes the nested one.
+    void make_moment(const ObjP &o) {
+        lrt_moment_desc &M = S.moment; M = lrt_moment_desc{};
+        int n = 0, unnamed = 0;
+        for (auto &c : o->children) {
+            if (c.second->tag != "integrator") fail("moment: Child objects must be of type 'SamplingIntegrator'!");
+            const std::string name = c.first.empty() ? "_arg_" + std::to_string(unnamed++) : c.first;
+            if (++n > 1)
+                fail("moment: two or more nested integrators are not supported (the second one continues the first one's sampler stream, which no render here computes)");
+            const std::string &t = c.second->type;
+            if (t == "aov" || t == "moment" || t == "prbvolpath") fail("moment: a nested \"" + t + "\" integrator is not supported");
+            int spass; bool spectral;
+            M.integrator = parse_integrator(c.second, &spass, &spectral);
+            const int spass_m = get_int(*o, "samples_per_pass", -1);
+            if (spass > 0 && spass != spass_m)
+                fail("moment: nested integrator \"" + name + "\" sets samples_per_pass = " + std::to_string(spass) + ", the moment integrator " +
+                     (spass_m > 0 ? std::to_string(spass_m) : std::string("none")) + " (a single scene description cannot express both)");
+            if (name.size() >= LRT_AOV_NAME_LEN) fail("moment: integrator name \"" + name + "\" is longer than " + std::to_string(LRT_AOV_NAME_LEN - 1) + " characters");
+            memcpy(M.name, name.c_str(), name.size() + 1);
+            S.desc.integrator = M.integrator;
+            S.desc.samples_per_pass = spass_m > 0 ? (uint32_t) spass_m : 0u;
+            S.desc.use_spectral_mis = spectral ? 1u : 0u;
+        }
+        if (n == 0) fail("moment: the integrator has no nested integrator (a render would have no result)");
+        S.moment_channel_names = { "R", "G", "B" };
+        if (S.desc.film.has_alpha) S.moment_channel_names.push_back("A");
+        for (const char *pre : { "", "m2_" }) for (const char *suf : { ".X", ".Y", ".Z" }) S.moment_channel_names.push_back(std::string(pre) + M.name + suf);
+        M.n_channels = (int32_t) S.moment_channel_names.size(); M.n_raw_channels = M.n_channels + 1;
+        S.has_moment = true;
+    }
+
     void run(const std::string &text) {
         std::unique_ptr<XmlNode> root = xml_parse(text);
         if (root->tag != "scene") fail("root element must be <scene>");
@@ -823,7 +858,7 @@ struct Loader {
             objs.push_back(o);
         }
         for (auto &o : objs) {
-            if (o->tag == "integrator") { if (o->type != "aov") make_integrator(o); }   // aov: after the sensor (its channel list depends on the film)
+            if (o->tag == "integrator") { if (o->type != "aov" && o->type != "moment") make_integrator(o); }   // aov, moment: after the sensor (their channel lists depend on the film)
             else if (o->tag == "sensor") { if (have_sensor) fail("only one sensor is supported"); make_sensor(o); have_sensor = true; }
             else if (o->tag == "shape") make_shape(o);
             else if (o->tag == "emitter") make_emitter(o);
@@ -833,7 +868,7 @@ struct Loader {
             else fail("unsupported top-level element <" + o->tag + ">");
         }
         if (!have_sensor) fail("the scene has no sensor");
-        for (auto &o : objs) if (o->tag == "integrator" && o->type == "aov") make_integrator(o);
+        for (auto &o : objs) if (o->tag == "integrator" && (o->type == "aov" || o->type == "moment")) make_integrator(o);
         bool ext = false;                       // spheres / point / mesh emitters: prbvolpath's adjoint is built for triangles and rectangle / infinite emitters
         for (auto &sh : S.shapes) ext = ext || sh.kind == LRT_SHAPE_SPHERE;
         for (auto &e : S.emitters) ext = ext || e.type == LRT_EMITTER_POINT || (e.type == LRT_EMITTER_AREA && S.shapes[e.shape].kind == LRT_SHAPE_MESH);
