@@ -254,7 +254,7 @@ typedef struct {
 typedef struct lrt_scene lrt_scene;
 
 LRT_API const char *lrt_last_error(void);
-LRT_API int         lrt_version(void);   /* 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
+LRT_API int         lrt_version(void);   /* 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
 
 LRT_API lrt_status lrt_scene_load_xml(const char *path, const char *const *defines,
                                       int n_defines, lrt_scene **out);
@@ -322,6 +322,11 @@ LRT_API lrt_status lrt_math_eval(int fn, const float *x, const float *y, uint32_
  *   [17..19] emitter_eval at the hit (area.cpp eval: one-sided through the shading frame).  Indices are stored as floats. */
 #define LRT_PROBE_FLOATS 20
 LRT_API lrt_status lrt_emitter_probe(lrt_scene *scene, const float *ref_p, const float *sample, uint32_t n, float *out, int device);
+
+/* Test hook [v111]: the environment emitter at n given world directions dir[3 i ..], as the integrators evaluate it for a ray that
+ * leaves the scene: out[4 i] = Scene::pdf_emitter_direction for the miss (the factor 1 / n_emitters included), out[4 i + 1 .. 3] =
+ * the emitter's eval.  LRT_ERR_* if the scene has no environment emitter. */
+LRT_API lrt_status lrt_envmap_probe(lrt_scene *scene, const float *dir, uint32_t n, float *out, int device);
 
 /* SoA ray queries (layout mirrors RayHit of src/render/scene_native.inl:135-142).
  * Miss: t = +inf, prim = 0xffffffff.  any_hit: only t (0 on hit, +inf on miss). */

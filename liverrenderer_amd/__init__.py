@@ -427,6 +427,15 @@ class Scene:
         return {"p": out[:, 0:3], "n": out[:, 3:6], "d": out[:, 6:9], "dist": out[:, 9], "pdf": out[:, 10], "weight": out[:, 11:14],
                 "emitter": out[:, 14].astype(np.int32), "hit_shape": out[:, 15].astype(np.int32), "hit_pdf": out[:, 16], "hit_le": out[:, 17:20]}
 
+    def envmap_probe(self, directions, device=0):
+        """lrt_envmap_probe (test hook): the environment emitter at world directions (n x 3), as the integrators evaluate it for a
+        ray that leaves the scene.  Returns (pdf (n), radiance (n x 3)): Scene::pdf_emitter_direction of the miss, the emitter's eval."""
+        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        out = np.empty((d.shape[0], 4), dtype=np.float32)
+        FP = C.POINTER(C.c_float)
+        _lib.check(self._lib.lrt_envmap_probe(self._h, d.ctypes.data_as(FP), d.shape[0], out.ctypes.data_as(FP), int(device)))
+        return out[:, 0].copy(), out[:, 1:4].copy()
+
     # -- parameters (mi.traverse) -------------------------------------------
     def param_set(self, key, value):
         v = np.atleast_1d(np.asarray(value, dtype=np.float32))

@@ -199,6 +199,8 @@ def lib():
     L.lrt_render_backward.argtypes = [C.c_void_p, P(RenderOpts), C.c_void_p, P(ParamGrads)]
     L.lrt_trace.argtypes = [C.c_void_p, P(RaysSoA), P(HitsSoA), C.c_uint32, C.c_int]
     L.lrt_emitter_probe.argtypes = [C.c_void_p, P(C.c_float), P(C.c_float), C.c_uint32, P(C.c_float), C.c_int]
+    L.lrt_envmap_probe.argtypes = [C.c_void_p, P(C.c_float), C.c_uint32, P(C.c_float), C.c_int]
+    L.lrt_envmap_probe.restype = C.c_int
     L.lrt_param_set.argtypes = [C.c_void_p, C.c_char_p, P(C.c_float), C.c_int]
     L.lrt_param_get.argtypes = [C.c_void_p, C.c_char_p, P(C.c_float), C.c_int]
     L.lrt_image_read.argtypes = [C.c_char_p, P(C.c_int), P(C.c_int), P(C.c_int), P(P(C.c_float))]
@@ -237,7 +239,7 @@ def lib():
 
 EXPORTED_SYMBOLS = ["lrt_last_error", "lrt_version", "lrt_scene_load_xml", "lrt_scene_load_xml_string", "lrt_scene_from_desc",
                     "lrt_scene_desc_get", "lrt_scene_free", "lrt_render", "lrt_render_multi", "lrt_render_backward_multi", "lrt_math_eval", "lrt_render_stats_get", "lrt_film_develop",
-                    "lrt_render_samples", "lrt_render_backward", "lrt_trace", "lrt_emitter_probe", "lrt_param_set", "lrt_param_get",
+                    "lrt_render_samples", "lrt_render_backward", "lrt_trace", "lrt_emitter_probe", "lrt_envmap_probe", "lrt_param_set", "lrt_param_get",
                     "lrt_image_read", "lrt_image_free", "lrt_image_write_exr", "lrt_image_write_png",
                     "lrt_vae_model_create", "lrt_vae_model_free", "lrt_vae_scatter",
                     "lrt_scene_aov_get", "lrt_aov_channel_name", "lrt_render_aov", "lrt_render_aov_samples", "lrt_image_write_exr_channels",

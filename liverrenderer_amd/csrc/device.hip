@@ -1521,6 +1521,21 @@ void device_emitter_probe(DeviceScene *D, const float *ref_p, const float *sampl
     HIP_CHECK(hipStreamSynchronize(st));
 }
 
+// Test hook (include/liverrt.h lrt_envmap_probe): k_envmap_probe (kernels.h) on the scene's device image
+void device_envmap_probe(DeviceScene *D, const float *dir, uint32_t n, float *out) {
+    HIP_CHECK(hipSetDevice(D->device));
+    if (D->sc.env.emitter < 0) throw std::runtime_error("lrt_envmap_probe: the scene has no environment emitter");
+    if (!n) return;
+    hipStream_t st = D->stream;
+    struct Tmp { float *p = nullptr; ~Tmp() { if (p) (void) hipFree(p); } } dd, dout;
+    HIP_CHECK(hipMalloc((void **) &dd.p, (size_t) n * 3 * 4)); HIP_CHECK(hipMalloc((void **) &dout.p, (size_t) n * 4 * 4));
+    HIP_CHECK(hipMemcpyAsync(dd.p, dir, (size_t) n * 3 * 4, hipMemcpyHostToDevice, st));
+    k_envmap_probe<<<(n + LRT_BLOCK - 1) / LRT_BLOCK, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, dd.p, n, dout.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * 4 * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
 // Test hook (include/liverrt.h lrt_math_eval): the transcendental kernels of csrc/dmath.h evaluated on the device, one lane per value.
 // orc_math.h holds the same polynomials written a second time, so bit-equality of the render lanes says nothing about their accuracy:
 // tests/test_parity_gpu.py bounds the DEVICE values against float64 and checks them bit for bit against the oracle's twins.

@@ -1209,4 +1209,19 @@ k_emitter_probe(ScenePtr scp, const float *__restrict__ ref_p, const float *__re
     o[15] = shape; o[16] = pdf; o[17] = le.x; o[18] = le.y; o[19] = le.z;
 }
 
+// Test hook (lrt_envmap_probe): what the integrators evaluate for a ray that leaves the scene along dir, one direction per lane:
+// pdf_emitter_direction of the environment emitter for a miss, then emitter_eval_env.  The scene must hold an environment emitter.
+__global__ void __launch_bounds__(LRT_BLOCK)
+k_envmap_probe(ScenePtr scp, const float *__restrict__ dir, uint32_t n, float *__restrict__ out) {
+    SceneRef sc = *scp;
+    const uint32_t i = blockIdx.x * LRT_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const V3 d(dir[3 * (size_t) i], dir[3 * (size_t) i + 1], dir[3 * (size_t) i + 2]);
+    SI si{}; si.valid = false; si.wi = -d;
+    const float pdf = pdf_emitter_direction<true>(sc, V3(0.f), si, sc.env.emitter);
+    const V3 le = emitter_eval_env(sc, d);
+    float *o = out + 4 * (size_t) i;
+    o[0] = pdf; o[1] = le.x; o[2] = le.y; o[3] = le.z;
+}
+
 } // namespace lrt

@@ -188,6 +188,28 @@ class OrcScene:
         self._L.orc_envmap_eval(self._h, _fp(d), _fp(rgb))
         return rgb
 
+    def envmap_sample_n(self, samples, ref=(0, 0, 0)):
+        """envmap_sample at n samples (n, 2): directions (n, 3), pdfs (n,), weights (n, 3)"""
+        s = np.ascontiguousarray(samples, np.float32).tolist(); n = len(s)
+        r = np.asarray(ref, np.float32).copy(); d = np.zeros((n, 3), np.float32); pdf = np.zeros(n, np.float32); rgb = np.zeros((n, 3), np.float32)
+        V = C.c_void_p                                            # (the same entry point, taking element addresses)
+        f = C.CFUNCTYPE(None, V, C.c_float, C.c_float, V, V, V, V)(("orc_envmap_sample", self._L))
+        h, pr, pd, pp, pw = self._h, r.ctypes.data, d.ctypes.data, pdf.ctypes.data, rgb.ctypes.data
+        for i in range(n):
+            f(h, s[i][0], s[i][1], pr, pd + 12 * i, pp + 4 * i, pw + 12 * i)
+        return d, pdf, rgb
+
+    def envmap_pdf_eval_n(self, dirs):
+        """envmap_pdf and envmap_eval at n directions (n, 3): pdfs (n,), radiance (n, 3)"""
+        d = np.ascontiguousarray(dirs, np.float32); n = len(d)
+        pdf = np.zeros(n, np.float32); rgb = np.zeros((n, 3), np.float32)
+        V = C.c_void_p
+        fp = C.CFUNCTYPE(C.c_float, V, V)(("orc_envmap_pdf", self._L)); fe = C.CFUNCTYPE(None, V, V, V)(("orc_envmap_eval", self._L))
+        h, pd, pw = self._h, d.ctypes.data, rgb.ctypes.data
+        for i in range(n):
+            pdf[i] = fp(h, pd + 12 * i); fe(h, pd + 12 * i, pw + 12 * i)
+        return pdf, rgb
+
 
 def math_eval(fn, x, y=None):
     x = np.ascontiguousarray(x, np.float32); y = x if y is None else np.ascontiguousarray(y, np.float32)
