@@ -220,7 +220,8 @@ typedef struct {
     int32_t  device;          /* HIP device ordinal                                */
     int32_t  output_on_device;/* film_raw / image are device pointers              */
     int32_t  grad_medium;     /* lrt_render_backward: index (into media[]) of the medium whose sigma_t / albedo / g
-                                 the gradients refer to; -1: the sum over all media (one shared parameter set) */
+                                 the gradients refer to; -1: the sum over all media (one shared parameter set).
+                                 lrt_render_backward_grid [v112]: the index of a heterogeneous medium (-1 is invalid) */
     int32_t  pad;
 } lrt_render_opts;
 
@@ -254,7 +255,7 @@ typedef struct {
 typedef struct lrt_scene lrt_scene;
 
 LRT_API const char *lrt_last_error(void);
-LRT_API int         lrt_version(void);   /* 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
+LRT_API int         lrt_version(void);   /* 112: lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
 
 LRT_API lrt_status lrt_scene_load_xml(const char *path, const char *const *defines,
                                       int n_defines, lrt_scene **out);
@@ -292,6 +293,19 @@ LRT_API lrt_status lrt_render_samples(lrt_scene *scene, const lrt_render_opts *o
  * 404-415); the bio media are rejected (LRT_ERR_UNSUPPORTED): the reference's prbvolpath reads them as homogeneous. */
 LRT_API lrt_status lrt_render_backward(lrt_scene *scene, const lrt_render_opts *opts,
                                        const float *grad_image, lrt_param_grads *out);
+
+/* [v112] lrt_render_backward plus the gradient w.r.t. the sigma_t grid of ONE heterogeneous medium (what dr.backward leaves in
+ * mi.traverse(scene)["<medium>.sigma_t.data"]; src/python/python/ad/integrators/prbvolpath.py on src/media/heterogeneous.cpp).
+ * opts->grad_medium must be the index of a heterogeneous medium; anything else, -1 included, is LRT_ERR_INVALID.
+ * d_grid: res_x * res_y * res_z floats in the layout of grid_data (x fastest); overwritten, not accumulated into; with
+ * opts->output_on_device a device pointer (grad_image too, as in lrt_render_backward).  It is the derivative w.r.t. the raw grid
+ * values, before `scale`: sigma_t(p) = scale * sum_v w_v(p) grid[v] with the trilinear weights of src/volumes/grid.cpp.  The majorant
+ * is detached (parameters_changed).  `out` receives what lrt_render_backward returns for the same arguments.  tile_rank / tile_count
+ * as there: shard gradients add up.  The per-voxel sums are float atomic adds whose order of arrival varies: d_grid may differ in its
+ * last bits from run to run.  Moment and aov scenes are LRT_ERR_UNSUPPORTED, as are the scenes prbvolpath rejects; there is no
+ * multi-device form. */
+LRT_API lrt_status lrt_render_backward_grid(lrt_scene *scene, const lrt_render_opts *opts, const float *grad_image,
+                                            lrt_param_grads *out, float *d_grid);
 
 /* One process, several devices [v104] (SURVEY.md 8e through the C ABI; no reference counterpart: the reference renders on one device):
  * device i of the list (device_ids, or 0 .. n_devices - 1 when NULL) renders the 32x32 tiles t with t % n_devices == i into its own
@@ -340,7 +354,11 @@ LRT_API lrt_status lrt_trace(lrt_scene *scene, const lrt_rays_soa *rays,
  * "<medium id>.phase_function.g" (1; switches the phase to HG when != 0);
  * a `parenchyma` medium also has what src/media/parenchyma.cpp:154-160 traverses:
  * "<id>.sigma_blood.value", "<id>.sigma_bile.value", "<id>.sigma_lipid_water.value" (3 each)
- * and "<id>.sigma_hepatocity" (1).                                           */
+ * and "<id>.sigma_hepatocity" (1).
+ * [v112] a heterogeneous medium also has "<id>.sigma_t.data": the grid values, n = res_x * res_y * res_z floats in the layout
+ * of grid_data (x fastest).  A set needs finite values >= 0 with a maximum above 0 (LRT_ERR_INVALID otherwise, the scene unchanged);
+ * it replaces what lrt_scene_desc_get()->media[i].grid_data points to (the pointer stays), takes grid_max again (the majorant is
+ * scale * grid_max) and has the next render upload the grid.  The resolution is fixed at load time.                  */
 LRT_API lrt_status lrt_param_set(lrt_scene *scene, const char *key, const float *v, int n);
 LRT_API lrt_status lrt_param_get(const lrt_scene *scene, const char *key, float *v, int n);
 

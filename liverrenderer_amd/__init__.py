@@ -386,7 +386,15 @@ class Scene:
     def render_backward(self, grad_image, **kw):
         """PRB adjoint.  `medium`: index of the medium whose sigma_t / albedo / g the gradients refer to; the default -1 sums the adjoint
         over all media into one parameter set (the round-1 meaning; lrt_render_opts.grad_medium in the C ABI, where a zero-initialised
-        struct selects medium 0)."""
+        struct selects medium 0).
+        grid=True (lrt_render_backward_grid): the dict also holds "sigma_t_data", the gradient w.r.t. the sigma_t grid of the
+        heterogeneous medium `medium` (left out: the scene's only heterogeneous medium), float32 of shape (res_z, res_y, res_x) like
+        the array write_volume_grid takes.  out=: a float32 CUDA torch tensor of that shape receives it without a host copy
+        (grad_image may then be a tensor on that device as well) and is returned in the dict."""
+        if kw.get("grid"):
+            return self._render_backward_grid(grad_image, kw)
+        if kw.get("out") is not None:
+            raise TypeError("render_backward: out= goes with grid=True")
         g = np.ascontiguousarray(grad_image, dtype=np.float32)
         o = make_opts(kw.get("integrator"), kw.get("max_depth"), kw.get("rr_depth"), kw.get("hide_emitters"), kw.get("spp", 0),
                       kw.get("seed", 0), kw.get("tile_rank", 0), kw.get("tile_count", 1), kw.get("device", 0), grad_medium=kw.get("medium", -1))
@@ -394,6 +402,56 @@ class Scene:
         _lib.check(self._lib.lrt_render_backward(self._h, C.byref(o), g.ctypes.data, C.byref(out)))
         return {"sigma_t": np.array(out.d_sigma_t[:], dtype=np.float32), "albedo": np.array(out.d_albedo[:], dtype=np.float32),
                 "g": float(out.d_g)}
+
+    def heterogeneous_media(self):
+        """Indices (into desc.media) of the media with a sigma_t grid."""
+        d = self.desc
+        return [i for i in range(d.n_media) if d.media[i].type == _lib.MEDIUM["heterogeneous"]]
+
+    def grid_shape(self, medium):
+        """(res_z, res_y, res_x) of a heterogeneous medium's grid: the shape of the array write_volume_grid takes."""
+        r = self.desc.media[medium].grid_res
+        return (int(r[2]), int(r[1]), int(r[0]))
+
+    def _render_backward_grid(self, grad_image, kw):
+        m = kw.get("medium")
+        if m is None or m < 0:
+            het = self.heterogeneous_media()
+            if len(het) != 1:
+                raise RuntimeError(f"render_backward(grid=True): the scene holds {len(het)} heterogeneous media; name one with medium=")
+            m = het[0]
+        if not 0 <= m < self.desc.n_media or m not in self.heterogeneous_media():
+            shape = None                               # the library reports the cause
+        else:
+            shape = self.grid_shape(m)
+        out_t = kw.get("out")
+        on_device = out_t is not None
+        h, w, c = self.film_shape()
+        if on_device:
+            import torch
+            if not _is_torch(out_t) or not out_t.is_cuda or out_t.dtype != torch.float32 or not out_t.is_contiguous() or (shape is not None and tuple(out_t.shape) != shape):
+                raise RuntimeError(f"render_backward(grid=True): out must be a contiguous float32 CUDA tensor of shape {shape}")
+            dev = out_t.device.index or 0
+            if kw.get("device", dev) != dev:
+                raise RuntimeError(f"render_backward(grid=True): out lives on {out_t.device}, the render was asked for device {kw['device']}")
+            g = grad_image if _is_torch(grad_image) else torch.from_numpy(np.ascontiguousarray(grad_image, dtype=np.float32))
+            g = g.to(device=out_t.device, dtype=torch.float32).contiguous()
+            if g.numel() != h * w * c:
+                raise RuntimeError(f"render_backward: grad_image has {g.numel()} values, the image {h * w * c}")
+            torch.cuda.current_stream(out_t.device).synchronize()     # the library works on a stream of its own
+            g_ptr, d_ptr, res = g.data_ptr(), out_t.data_ptr(), out_t
+        else:
+            g = np.ascontiguousarray(grad_image, dtype=np.float32)
+            if g.size != h * w * c:
+                raise RuntimeError(f"render_backward: grad_image has {g.size} values, the image {h * w * c}")
+            res = np.empty(shape if shape is not None else (1,), dtype=np.float32)
+            g_ptr, d_ptr, dev = g.ctypes.data, res.ctypes.data, kw.get("device", 0)
+        o = make_opts(kw.get("integrator"), kw.get("max_depth"), kw.get("rr_depth"), kw.get("hide_emitters"), kw.get("spp", 0),
+                      kw.get("seed", 0), kw.get("tile_rank", 0), kw.get("tile_count", 1), dev, on_device, grad_medium=m)
+        out = _lib.ParamGrads()
+        _lib.check(self._lib.lrt_render_backward_grid(self._h, C.byref(o), C.c_void_p(g_ptr), C.byref(out), C.c_void_p(d_ptr)))
+        return {"sigma_t": np.array(out.d_sigma_t[:], dtype=np.float32), "albedo": np.array(out.d_albedo[:], dtype=np.float32),
+                "g": float(out.d_g), "sigma_t_data": res}
 
     def stats(self):
         s = _lib.RenderStats()
@@ -438,10 +496,19 @@ class Scene:
 
     # -- parameters (mi.traverse) -------------------------------------------
     def param_set(self, key, value):
-        v = np.atleast_1d(np.asarray(value, dtype=np.float32))
+        """lrt_param_set.  "<id>.sigma_t.data" takes an array of shape (res_z, res_y, res_x) (or its flattening)."""
+        v = np.ascontiguousarray(np.atleast_1d(np.asarray(value, dtype=np.float32))).reshape(-1)
         _lib.check(self._lib.lrt_param_set(self._h, key.encode(), v.ctypes.data_as(C.POINTER(C.c_float)), int(v.size)))
 
     def param_get(self, key, n=3):
+        """lrt_param_get.  "<id>.sigma_t.data" returns the grid as (res_z, res_y, res_x), whatever n says."""
+        if key.endswith(".sigma_t.data"):
+            ids = self.medium_ids(); mid = key[:-len(".sigma_t.data")]
+            if mid in ids and ids.index(mid) in self.heterogeneous_media():
+                shape = self.grid_shape(ids.index(mid))
+                v = np.zeros(shape, dtype=np.float32)
+                _lib.check(self._lib.lrt_param_get(self._h, key.encode(), v.ctypes.data_as(C.POINTER(C.c_float)), int(v.size)))
+                return v
         v = np.zeros(n, dtype=np.float32)
         _lib.check(self._lib.lrt_param_get(self._h, key.encode(), v.ctypes.data_as(C.POINTER(C.c_float)), n))
         return v
@@ -475,12 +542,19 @@ class SceneParameters(dict):
                 for k in ("sigma_blood.value", "sigma_bile.value", "sigma_lipid_water.value"):
                     super().__setitem__(f"{mid}.{k}", scene.param_get(f"{mid}.{k}", 3))
                 super().__setitem__(f"{mid}.sigma_hepatocity", scene.param_get(f"{mid}.sigma_hepatocity", 1))
+            if m.type == _lib.MEDIUM["heterogeneous"]:          # the grid volume's values (src/volumes/grid.cpp traverse), as (res_z, res_y, res_x)
+                super().__setitem__(f"{m.id.decode()}.sigma_t.data", scene.param_get(f"{m.id.decode()}.sigma_t.data"))
         self._dirty = set()
 
     def __setitem__(self, k, v):
         if k not in self:
             raise KeyError(k)
-        super().__setitem__(k, np.atleast_1d(np.asarray(v, dtype=np.float32)))
+        a = np.atleast_1d(np.asarray(v, dtype=np.float32))
+        if k.endswith(".sigma_t.data"):
+            if a.size != self[k].size:
+                raise ValueError(f"{k}: expected {self[k].shape} (res_z, res_y, res_x), got {a.shape}")
+            a = a.reshape(self[k].shape)
+        super().__setitem__(k, a)
         self._dirty.add(k)
 
     def update(self, values=None):

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LRT_LIBRARY") or os.path.join(_HERE, "libliverrt.so")     # LRT_LIBRARY: developer builds (csrc/Makefile: exp)
 
-OK = 0
+OK, INVALID, UNSUPPORTED = 0, 1, 4      # lrt_status values the wrappers and tests name
 INTEGRATOR = {"path": 0, "volpath": 1, "prbvolpath": 2, "biovolpath": 3, "biovolpath06": 4, "volpathmis": 5}
 MEDIUM = {"homogeneous": 0, "liver": 1, "parenchyma": 2, "glissonCapsule": 3, "heterogeneous": 4}
 EMITTER = {"area": 0, "envmap": 1, "constant": 2}
@@ -197,6 +197,8 @@ def lib():
     L.lrt_film_develop.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.lrt_render_samples.argtypes = [C.c_void_p, P(RenderOpts), C.c_uint64, C.c_uint32, C.c_void_p]
     L.lrt_render_backward.argtypes = [C.c_void_p, P(RenderOpts), C.c_void_p, P(ParamGrads)]
+    L.lrt_render_backward_grid.argtypes = [C.c_void_p, P(RenderOpts), C.c_void_p, P(ParamGrads), C.c_void_p]
+    L.lrt_render_backward_grid.restype = C.c_int
     L.lrt_trace.argtypes = [C.c_void_p, P(RaysSoA), P(HitsSoA), C.c_uint32, C.c_int]
     L.lrt_emitter_probe.argtypes = [C.c_void_p, P(C.c_float), P(C.c_float), C.c_uint32, P(C.c_float), C.c_int]
     L.lrt_envmap_probe.argtypes = [C.c_void_p, P(C.c_float), C.c_uint32, P(C.c_float), C.c_int]
@@ -239,7 +241,7 @@ def lib():
 
 EXPORTED_SYMBOLS = ["lrt_last_error", "lrt_version", "lrt_scene_load_xml", "lrt_scene_load_xml_string", "lrt_scene_from_desc",
                     "lrt_scene_desc_get", "lrt_scene_free", "lrt_render", "lrt_render_multi", "lrt_render_backward_multi", "lrt_math_eval", "lrt_render_stats_get", "lrt_film_develop",
-                    "lrt_render_samples", "lrt_render_backward", "lrt_trace", "lrt_emitter_probe", "lrt_envmap_probe", "lrt_param_set", "lrt_param_get",
+                    "lrt_render_samples", "lrt_render_backward", "lrt_render_backward_grid", "lrt_trace", "lrt_emitter_probe", "lrt_envmap_probe", "lrt_param_set", "lrt_param_get",
                     "lrt_image_read", "lrt_image_free", "lrt_image_write_exr", "lrt_image_write_png",
                     "lrt_vae_model_create", "lrt_vae_model_free", "lrt_vae_scatter",
                     "lrt_scene_aov_get", "lrt_aov_channel_name", "lrt_render_aov", "lrt_render_aov_samples", "lrt_image_write_exr_channels",

@@ -4,6 +4,8 @@
 #include "host_scene.h"
 #include "device_scene.h"
 #include "image_io.h"
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <cstdio>
 #include <fstream>
@@ -28,7 +30,7 @@ static lrt_status fail(lrt_status st, const std::string &msg) { g_error = msg; r
 extern "C" {
 
 const char *lrt_last_error(void) { return g_error.c_str(); }
-int lrt_version(void) { return 111; }    // 1.11: lrt_envmap_probe; 1.10: the moment integrator (lrt_render_moment, lrt_render_moment_samples, lrt_scene_moment_get, lrt_moment_channel_name); 1.9: the guided denoiser (lrt_denoiser_create / lrt_denoise / lrt_denoiser_free), lrt_image_read_named; 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
+int lrt_version(void) { return 112; }    // 1.12: lrt_render_backward_grid, "<id>.sigma_t.data" in lrt_param_set / lrt_param_get; 1.11: lrt_envmap_probe; 1.10: the moment integrator (lrt_render_moment, lrt_render_moment_samples, lrt_scene_moment_get, lrt_moment_channel_name); 1.9: the guided denoiser (lrt_denoiser_create / lrt_denoise / lrt_denoiser_free), lrt_image_read_named; 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
 
 static std::vector<std::pair<std::string, std::string>> parse_defines(const char *const *defines, int n) {
     std::vector<std::pair<std::string, std::string>> r;
@@ -164,7 +166,8 @@ static void ensure_devices(lrt_scene *s, int n, const int *ids) {
         multi_release(s);
         for (int dev : want) s->multi.push_back(device_scene_create(s->st.desc, dev));
         s->multi_ids = want; s->multi_params_dirty = false;
-    } else if (s->multi_params_dirty) { for (auto *D : s->multi) device_scene_update_params(D, s->st.desc); s->multi_params_dirty = false; }
+    } else if (s->multi_params_dirty) { for (auto *D : s->multi) device_scene_update_params(D, s->st.desc, s->multi_grids_dirty); s->multi_params_dirty = false; }
+    s->multi_grids_dirty = false;
 }
 
 // device < 0: whatever device the image already lives on (0 when there is none yet).  A render that names another device
@@ -173,7 +176,8 @@ static void ensure_devices(lrt_scene *s, int n, const int *ids) {
 static void ensure_device(lrt_scene *s, int device) {
     if (s->dev && device >= 0 && device != s->dev_ordinal) { device_scene_destroy(s->dev); s->dev = nullptr; }
     if (!s->dev) { s->dev_ordinal = device < 0 ? 0 : device; s->dev = device_scene_create(s->st.desc, s->dev_ordinal); s->params_dirty = false; }
-    else if (s->params_dirty) { device_scene_update_params(s->dev, s->st.desc); s->params_dirty = false; }
+    else if (s->params_dirty) { device_scene_update_params(s->dev, s->st.desc, s->grids_dirty); s->params_dirty = false; }
+    s->grids_dirty = false;               // (a fresh device image has uploaded the current grids)
 }
 
 lrt_status lrt_render(lrt_scene *scene, const lrt_render_opts *opts, float *film_raw, float *image) {
@@ -247,6 +251,20 @@ lrt_status lrt_render_backward(lrt_scene *scene, const lrt_render_opts *opts, co
     LRT_TRY
         ensure_device(scene, opts ? opts->device : 0);
         device_render_backward(scene->dev, scene->st.desc, opts, grad_image, out, scene->stats);
+        return LRT_OK;
+    LRT_CATCH
+}
+
+lrt_status lrt_render_backward_grid(lrt_scene *scene, const lrt_render_opts *opts, const float *grad_image, lrt_param_grads *out, float *d_grid) {
+    if (!scene || !grad_image || !out || !d_grid) return fail(LRT_ERR_INVALID, "lrt_render_backward_grid: null argument");
+    if (scene->st.has_aov) return fail(LRT_ERR_UNSUPPORTED, "lrt_render_backward_grid: the aov integrator has no adjoint here");
+    if (scene->st.has_moment) return fail(LRT_ERR_UNSUPPORTED, "lrt_render_backward_grid: the moment integrator has no adjoint here");
+    const int gm = opts ? opts->grad_medium : 0;
+    if (gm < 0 || gm >= (int) scene->st.desc.n_media || scene->st.desc.media[gm].type != LRT_MEDIUM_HETEROGENEOUS)
+        return fail(LRT_ERR_INVALID, "lrt_render_backward_grid: grad_medium " + std::to_string(gm) + " is not a heterogeneous medium of the scene (the grid gradient belongs to one medium with a sigma_t grid)");
+    LRT_TRY
+        ensure_device(scene, opts ? opts->device : 0);
+        device_render_backward(scene->dev, scene->st.desc, opts, grad_image, out, scene->stats, d_grid);
         return LRT_OK;
     LRT_CATCH
 }
@@ -379,6 +397,20 @@ lrt_status lrt_param_set(lrt_scene *scene, const char *key, const float *v, int 
         if (n != 1 && n != 3) return fail(LRT_ERR_INVALID, "expected 1 or 3 values");
         float *dst = rest[0] == 's' ? M->sigma_t : M->albedo;
         for (int i = 0; i < 3; ++i) dst[i] = v[n == 3 ? i : 0];
+    } else if (!strcmp(rest, "sigma_t.data") && M->type == LRT_MEDIUM_HETEROGENEOUS) {
+        // mi.traverse's "<medium>.sigma_t.data" (src/volumes/grid.cpp traverse): same resolution, new values; the maximum is taken again
+        // as parameters_changed() does (src/media/heterogeneous.cpp).  Checked in full before anything is written.
+        std::vector<float> &data = scene->st.meddata[(size_t) (M - scene->st.media.data())];
+        if (n < 0 || (size_t) n != data.size()) return fail(LRT_ERR_INVALID, std::string("\"") + key + "\": expected " + std::to_string(data.size()) + " values (res_x * res_y * res_z), got " + std::to_string(n));
+        float mx = 0.f;
+        for (int i = 0; i < n; ++i) {
+            if (!std::isfinite(v[i]) || v[i] < 0.f) return fail(LRT_ERR_INVALID, std::string("\"") + key + "\": the grid values must be finite and >= 0");
+            mx = std::max(mx, v[i]);
+        }
+        if (!(mx > 0.f)) return fail(LRT_ERR_INVALID, std::string("\"") + key + "\": the grid's maximum must be above 0 (it is the majorant)");
+        std::copy(v, v + n, data.begin());                  // in place: lrt_scene_desc_get()->media[i].grid_data keeps pointing here
+        M->grid_max = mx;
+        scene->grids_dirty = true; scene->multi_grids_dirty = true;
     } else if (!strcmp(rest, "scale")) M->scale = v[0];
     else if (M->type == LRT_MEDIUM_PARENCHYMA && (!strcmp(rest, "sigma_blood.value") || !strcmp(rest, "sigma_bile.value") || !strcmp(rest, "sigma_lipid_water.value"))) {
         // what `parenchyma` puts into mi.traverse (src/media/parenchyma.cpp:154-160): the absorbers' coefficients and sigma_hepatocity
@@ -407,6 +439,11 @@ lrt_status lrt_param_get(const lrt_scene *scene, const char *key, float *v, int 
     if (!M) return fail(LRT_ERR_INVALID, std::string("unknown parameter \"") + key + "\"");
     if (!strcmp(rest, "sigma_t.value")) { for (int i = 0; i < n && i < 3; ++i) v[i] = M->sigma_t[i]; }
     else if (!strcmp(rest, "albedo.value")) { for (int i = 0; i < n && i < 3; ++i) v[i] = M->albedo[i]; }
+    else if (!strcmp(rest, "sigma_t.data") && M->type == LRT_MEDIUM_HETEROGENEOUS) {
+        const size_t nv = (size_t) M->grid_res[0] * M->grid_res[1] * M->grid_res[2];
+        if (n < 0 || (size_t) n != nv) return fail(LRT_ERR_INVALID, std::string("\"") + key + "\": expected room for " + std::to_string(nv) + " values (res_x * res_y * res_z), got " + std::to_string(n));
+        std::copy(M->grid_data, M->grid_data + nv, v);
+    }
     else if (!strcmp(rest, "scale")) v[0] = M->scale;
     else if (!strcmp(rest, "phase_function.g")) v[0] = M->g;
     else if (M->type == LRT_MEDIUM_PARENCHYMA && !strcmp(rest, "sigma_blood.value")) { for (int i = 0; i < n && i < 3; ++i) v[i] = M->sigma_blood[i]; }

@@ -68,6 +68,7 @@ struct DeviceScene {
     std::vector<DHetMedium> h_het; DHetMedium *d_het = nullptr; std::vector<float *> het_data; bool has_het = false, has_non_bio = false, need_mis = false, mis_alloc = false;
     bool ext = false;                      // spheres, point emitters or area emitters on meshes: the EXT kernel instances (ExtTracer, point- / mesh-emitter sampling), wide records
     bool has_area_emitter = false;         // decides the record layout: only an area emitter's pdf reads the last scatter position (kernels.h, store_state)
+    float *dgrid = nullptr; size_t dgrid_floats = 0;   // lrt_render_backward_grid with a host result: the device-side gradient grid
     bool prb_null = false;                 // prbvolpath.py:84-91 `handle_null_scattering`: a heterogeneous medium is attached to a shape
     DLdsInfo lds{}; bool use_lds = false; int n_cus = 256; int bvh_leaf = 4;
     // aov integrator: the AOV table (device copy), the AOV film and the inner images / merged image of the last aov render
@@ -380,6 +381,7 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
             LRT_SMEM((k_render_prb<false, 1024, true, true>)); LRT_SMEM((k_render_prb<true, 1024, true, true>));
             LRT_SMEM((k_render_prb<false, 1024, true, false, true>)); LRT_SMEM((k_render_prb<true, 1024, true, false, true>));
             LRT_SMEM((k_render_prb<false, 1024, true, true, true>)); LRT_SMEM((k_render_prb<true, 1024, true, true, true>));
+            LRT_SMEM((k_render_prb_grid<1024, true, false>)); LRT_SMEM((k_render_prb_grid<1024, true, true>));
             LRT_SMEM((k_trace_lds<true>)); LRT_SMEM((k_trace_lds<false>)); LRT_SMEM((k_aov<true, false>)); LRT_SMEM((k_aov<true, true>));
             if (D->ext) {                              // spheres / point emitters / mesh emitters: the EXT instances (kernels.h)
 #define LRT_SMEM_EXT(I, BS) LRT_SMEM((k_render<I, BS, true, false, false, true>)); LRT_SMEM((k_render<I, BS, true, true, false, true>))
@@ -571,8 +573,13 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
     return D.release();
 }
 
-void device_scene_update_params(DeviceScene *D, const lrt_scene_desc &d) {
+void device_scene_update_params(DeviceScene *D, const lrt_scene_desc &d, bool grids) {
     HIP_CHECK(hipSetDevice(D->device));
+    if (grids) for (uint32_t i = 0; i < d.n_media; ++i) {         // "<id>.sigma_t.data": same resolution, new values (the description's copy outlives the sync below)
+        const lrt_medium_desc &M = d.media[i];
+        if (M.type == LRT_MEDIUM_HETEROGENEOUS && D->het_data[i])
+            HIP_CHECK(hipMemcpyAsync(D->het_data[i], M.grid_data, (size_t) M.grid_res[0] * M.grid_res[1] * M.grid_res[2] * sizeof(float), hipMemcpyHostToDevice, D->stream));
+    }
     upload_media(D, d);
     HIP_CHECK(hipStreamSynchronize(D->stream));
 }
@@ -767,20 +774,26 @@ static LaunchPtr push_launch(DeviceScene *D, const DLaunch &a) {
 
 template <bool ADJOINT>
 static void launch_prb(DeviceScene *D, const DRenderParams &rp, const PoolGeometry &g, const uint32_t *pixel_list, uint64_t lane_begin,
-                       float4 *L_buf, const float *grad_image, double *grads, float *film, float *sample_out) {
+                       float4 *L_buf, const float *grad_image, double *grads, float *film, float *sample_out, float *dgrid = nullptr) {
     hipStream_t st = D->stream;
     HIP_CHECK(hipMemsetAsync(&D->counters->next_lane, 0, sizeof(unsigned long long), st));
     DLaunch a{}; a.rp = rp; a.li = D->lds; a.q0 = D->q[0]; a.q1 = D->q[1]; a.dl0 = D->dl[0]; a.dl1 = D->dl[1]; a.P = g.P; a.cnt = D->counters;
     a.pixel_list = pixel_list; a.lane_begin = lane_begin; a.n = rp.n_lanes; a.L_buf = L_buf; a.grad_image = grad_image; a.wfilm = D->wfilm; a.grads = grads;
-    a.film = film; a.sample_out = sample_out; a.sample_base = lane_begin;
+    a.film = film; a.sample_out = sample_out; a.sample_base = lane_begin; a.dgrid = dgrid;
     const LaunchPtr lp = push_launch(D, a);             // (compact records, as run_wavefront queues them, were measured on C5: 96-byte records, 5 % SLOWER; the PRB kernels keep the wide layout)
 #ifdef LRT_DEV_VOLPATH_ONLY
     (void) lp; throw std::runtime_error("developer build: volpath only");
 #else
     #define LRT_LAUNCH_PRB(BS, LDSB, LD) do { if (D->prb_null) k_render_prb<ADJOINT, BS, LDSB, LD, true><<<g.n_wg, BS, g.smem, st>>>((ScenePtr) D->d_sc, lp); \
                                               else k_render_prb<ADJOINT, BS, LDSB, LD, false><<<g.n_wg, BS, g.smem, st>>>((ScenePtr) D->d_sc, lp); } while (0)
-    if (D->use_lds) { if (rp.ld_count) LRT_LAUNCH_PRB(1024, true, true); else LRT_LAUNCH_PRB(1024, true, false); }
+    #define LRT_LAUNCH_PRB_GRID(BS, LDSB, LD) k_render_prb_grid<BS, LDSB, LD><<<g.n_wg, BS, g.smem, st>>>((ScenePtr) D->d_sc, lp)
+    if (ADJOINT && dgrid) {                             // lrt_render_backward_grid (the caller has checked that the graded medium is heterogeneous: prb_null)
+        if (D->use_lds) { if (rp.ld_count) LRT_LAUNCH_PRB_GRID(1024, true, true); else LRT_LAUNCH_PRB_GRID(1024, true, false); }
+        else { if (rp.ld_count) LRT_LAUNCH_PRB_GRID(LRT_BLOCK, false, true); else LRT_LAUNCH_PRB_GRID(LRT_BLOCK, false, false); }
+    }
+    else if (D->use_lds) { if (rp.ld_count) LRT_LAUNCH_PRB(1024, true, true); else LRT_LAUNCH_PRB(1024, true, false); }
     else { if (rp.ld_count) LRT_LAUNCH_PRB(LRT_BLOCK, false, true); else LRT_LAUNCH_PRB(LRT_BLOCK, false, false); }
+    #undef LRT_LAUNCH_PRB_GRID
     #undef LRT_LAUNCH_PRB
 #endif
     HIP_CHECK(hipGetLastError());
@@ -1269,7 +1282,9 @@ namespace lrt {
 
 // RBIntegrator.render_backward (common.py:625-783): weight film (non-box filters) -> per chunk: primal pass into L_buf,
 // adjoint replay accumulating d(sum(image * grad_image)) / d(sigma_t, albedo, g) into 7 doubles.
-void device_render_backward(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, const float *grad_image, lrt_param_grads *out, lrt_render_stats &stats) {
+// d_grid != null (lrt_render_backward_grid): the adjoint pass is k_render_prb_grid, which also scatters d / d(grid values) of the
+// heterogeneous medium opts->grad_medium into a zeroed buffer of res_x * res_y * res_z floats (float atomics: last bits vary from run to run).
+void device_render_backward(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, const float *grad_image, lrt_param_grads *out, lrt_render_stats &stats, float *d_grid) {
     HIP_CHECK(hipSetDevice(D->device));
     lrt_render_opts oprb = opts ? *opts : lrt_render_opts{ -1, -2, -1, -1, 0, 0, 0, 1, 0, 0, 0, 0 };
     oprb.integrator = LRT_INTEGRATOR_PRBVOLPATH;                               // resolve as the adjoint integrator: RBIntegrator.render_backward has no pass split (common.py prepare())
@@ -1278,6 +1293,19 @@ void device_render_backward(DeviceScene *D, const lrt_scene_desc &d, const lrt_r
     const int grad_medium = opts ? opts->grad_medium : 0;
     if (grad_medium < -1 || grad_medium >= (int) d.n_media) throw std::runtime_error("lrt_render_backward: grad_medium " + std::to_string(grad_medium) + " is not a medium of the scene");
     hipStream_t st = D->stream;
+    float *dg = nullptr; size_t n_vox = 0;
+    if (d_grid) {
+        if (grad_medium < 0 || d.media[grad_medium].type != LRT_MEDIUM_HETEROGENEOUS)
+            throw std::invalid_argument("lrt_render_backward_grid: grad_medium " + std::to_string(grad_medium) + " is not a heterogeneous medium (the grid gradient belongs to one medium with a sigma_t grid)");
+        if (!D->prb_null) throw std::runtime_error("unsupported: lrt_render_backward_grid on a heterogeneous medium that is attached to no shape");
+        const lrt_medium_desc &M = d.media[grad_medium];
+        n_vox = (size_t) M.grid_res[0] * M.grid_res[1] * M.grid_res[2];
+        if (opts && opts->output_on_device) dg = d_grid;
+        else {
+            if (D->dgrid_floats < n_vox) { D->release(D->dgrid); D->dgrid = nullptr; D->dgrid_floats = 0; HIP_CHECK(hipMalloc((void **) &D->dgrid, n_vox * 4)); D->track(D->dgrid); D->dgrid_floats = n_vox; }
+            dg = D->dgrid;
+        }
+    }
     const DFilm &F = D->sc.film;
     const size_t np = (size_t) F.width * F.height, T = F.has_alpha ? 4 : 3;
     if ((uint64_t) np * O.spp > 0xffffffffull) throw std::runtime_error("more than 2^32 samples per render");
@@ -1313,6 +1341,7 @@ void device_render_backward(DeviceScene *D, const lrt_scene_desc &d, const lrt_r
         }
     }
     HIP_CHECK(hipMemsetAsync(D->d_grads, 0, 7 * sizeof(double), st));
+    if (dg) HIP_CHECK(hipMemsetAsync(dg, 0, n_vox * 4, st));
     HIP_CHECK(hipMemsetAsync(D->counters, 0, sizeof(DCounters), st));
     LaunchLog log;
     hipEvent_t e_begin = get_event(D, log.ev++), e_end = get_event(D, log.ev++);
@@ -1323,7 +1352,7 @@ void device_render_backward(DeviceScene *D, const lrt_scene_desc &d, const lrt_r
             hipEvent_t a = get_event(D, log.ev++), b = get_event(D, log.ev++);
             HIP_CHECK(hipEventRecord(a, st));
             if (!adjoint) launch_prb<false>(D, rp, g, pixel_list, base, D->L_buf, nullptr, nullptr, nullptr, nullptr);
-            else launch_prb<true>(D, rp, g, pixel_list, base, D->L_buf, g_img, D->d_grads, nullptr, nullptr);
+            else launch_prb<true>(D, rp, g, pixel_list, base, D->L_buf, g_img, D->d_grads, nullptr, nullptr, dg);
             HIP_CHECK(hipEventRecord(b, st));
             log.launches.emplace_back(a, b); log.sizes.push_back(0);
         }
@@ -1336,6 +1365,7 @@ void device_render_backward(DeviceScene *D, const lrt_scene_desc &d, const lrt_r
     HIP_CHECK(hipMemcpy(h, D->d_grads, sizeof(h), hipMemcpyDeviceToHost));
     for (int k = 0; k < 3; ++k) { out->d_sigma_t[k] = (float) h[k]; out->d_albedo[k] = (float) h[3 + k]; }
     out->d_g = (float) h[6];
+    if (dg && dg != d_grid) HIP_CHECK(hipMemcpy(d_grid, dg, n_vox * 4, hipMemcpyDeviceToHost));
 }
 
 // ---- learned subsurface model, network stage (include/liverrt.h; one lane per sample, weights through the scalar cache)

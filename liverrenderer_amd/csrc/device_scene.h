@@ -8,7 +8,7 @@ namespace lrt {
 struct DeviceScene;
 DeviceScene *device_scene_create(const lrt_scene_desc &d, int device);
 void device_scene_destroy(DeviceScene *d);
-void device_scene_update_params(DeviceScene *D, const lrt_scene_desc &d);
+void device_scene_update_params(DeviceScene *D, const lrt_scene_desc &d, bool grids = false);   // grids: the heterogeneous media's grid values changed too
 void device_render(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, float *film_raw, float *image, lrt_render_stats &stats);
 void device_develop(DeviceScene *D, const float *film_raw, float *image, int on_device);
 // the aov integrator (kernels_aov.h): nested renders, then the first-hit AOV pass; merged image on the device
@@ -24,7 +24,8 @@ void device_emitter_probe(DeviceScene *D, const float *ref_p, const float *sampl
 // network stage of the learned subsurface model (kernels_vae.h): host arrays in, host arrays out
 void device_vae_scatter(const float *blob, uint32_t n, const float *in_pos, const float *in_dir, const float *poly, const float albedo[3], float g, float ior,
                         const float sigma_t[3], float fit_scale, uint32_t seed, float *out_pos, float *out_absorption, int device);
-void device_render_backward(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, const float *grad_image, lrt_param_grads *out, lrt_render_stats &stats);
+void device_render_backward(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, const float *grad_image, lrt_param_grads *out, lrt_render_stats &stats,
+                            float *d_grid = nullptr);   // d_grid: lrt_render_backward_grid (host or device pointer, as opts->output_on_device says)
 void device_math_eval(int fn, const float *x, const float *y, uint32_t n, float *out, float *out2, int device);   // test hook: dmath.h on the device
 // guided denoiser (kernels_denoise.h): the workspace and a non-blocking stream belong to the object; `params` arrives resolved (no zeros)
 struct Denoiser;

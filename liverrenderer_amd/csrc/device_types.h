@@ -243,6 +243,7 @@ struct DLaunch {
     uint32_t P, pad; DCounters *cnt; const uint32_t *pixel_list; uint64_t lane_begin, n;
     float4 *L_buf; const float *grad_image; const float *wfilm; double *grads;
     float *film; float *sample_out; uint64_t sample_base;
+    float *dgrid;                         // k_render_prb_grid: gradient w.r.t. the sigma_t grid of medium rp.grad_medium (x fastest, zeroed by the host)
 };
 typedef const LRT_CONST DRenderParams &RpRef;
 typedef const LRT_CONST DLaunch *LaunchPtr;

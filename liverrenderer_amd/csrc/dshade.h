@@ -998,6 +998,26 @@ DEV float grid_eval(const DHetMedium &H, V3 pl) {
     return fma_(w0z, c0, w1z * c1);
 }
 
+// The transpose of grid_eval for the PRB adjoint (kernels_prb.h, GRID): dg[v] += a * scale * w_v(pl) over the eight corners, with the
+// float32 weights and the clamped corner indices of the lookup above (two corners that clamp onto one voxel both add there).
+// sigma_t(p) = scale * sum_v w_v grid[v], so `a` is d / d sigma_t(p).  One no-return global_atomic_add_f32 per non-zero corner.
+DEV void grid_scatter(const DHetMedium &H, float *__restrict__ dg, V3 pl, float a) {
+    const int rx = H.res[0], ry = H.res[1], rz = H.res[2];
+    float fx = fma_(pl.x, (float) rx, -.5f), fy = fma_(pl.y, (float) ry, -.5f), fz = fma_(pl.z, (float) rz, -.5f);
+    float flx = __builtin_floorf(fx), fly = __builtin_floorf(fy), flz = __builtin_floorf(fz);
+    float w1x = fx - flx, w1y = fy - fly, w1z = fz - flz, w0x = 1.f - w1x, w0y = 1.f - w1y, w0z = 1.f - w1z;
+    auto cl = [](float v, int n) { int i = (v < -2e9f) ? -2000000000 : (v > 2e9f ? 2000000000 : (int) v); return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); };
+    int x0 = cl(flx, rx), x1 = cl(flx + 1.f, rx), y0 = cl(fly, ry), y1 = cl(fly + 1.f, ry), z0 = cl(flz, rz), z1 = cl(flz + 1.f, rz);
+    const float as = a * H.scale;
+#ifdef LRT_COUNT_SCATTER_ADDS                                   // (`make count`: the number of adds per voxel instead of their sum, for scripts/bench_grid_grad.py)
+    auto add = [&](int x, int y, int z, float w) { const float v = as * w; if (v != 0.f) atomicAdd(&dg[((size_t) z * ry + y) * rx + x], 1.f); };
+#else
+    auto add = [&](int x, int y, int z, float w) { const float v = as * w; if (v != 0.f) atomicAdd(&dg[((size_t) z * ry + y) * rx + x], v); };
+#endif
+    add(x0, y0, z0, w0x * w0y * w0z); add(x1, y0, z0, w1x * w0y * w0z); add(x0, y1, z0, w0x * w1y * w0z); add(x1, y1, z0, w1x * w1y * w0z);
+    add(x0, y0, z1, w0x * w0y * w1z); add(x1, y0, z1, w1x * w0y * w1z); add(x0, y1, z1, w0x * w1y * w1z); add(x1, y1, z1, w1x * w1y * w1z);
+}
+
 // include/mitsuba/core/bbox.h:303-340 (Williams et al.)
 DEV bool bbox_ray_intersect(const float *lo, const float *hi, const Ray &ray, float &mint, float &maxt) {
     bool active = ray.d.x != 0.f || ray.d.y != 0.f || ray.d.z != 0.f;

@@ -52,6 +52,7 @@ struct lrt_scene {
     lrt::SceneStorage st;
     lrt::DeviceScene *dev = nullptr;     // created lazily on first device call
     bool params_dirty = true;
+    bool grids_dirty = false, multi_grids_dirty = false;   // lrt_param_set("<id>.sigma_t.data"): the next update uploads the grids again
     int dev_ordinal = -1;                  // HIP device the device image lives on
     lrt_render_stats stats{};
     // lrt_render_multi: one device image per entry of the last device list, and that list's communicators

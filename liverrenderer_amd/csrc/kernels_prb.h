@@ -16,6 +16,9 @@
 //   real collision  d ln(sigma_s_c) / d scale = 1 / scale,   d ln(sigma_s_c) / d a_c = 1 / a_c
 //   null collision  d ln(sigma_n_c) / d scale = -sigma_t(p) / (sigma_n_c scale)
 // and d_sigma_t[c] of such a medium is channel c's share of d / d scale (include/liverrt.h).
+// GRID (k_render_prb_grid, lrt_render_backward_grid): beside that, d / d grid[v] of sigma_t(p) = scale * sum_v w_v(p) grid[v], one float per voxel:
+//   real collision  d ln(sigma_s_c) / d sigma_t(p) = 1 / sigma_t(p),   null collision  d ln(sigma_n_c) / d sigma_t(p) = -1 / sigma_n_c
+// times d sigma_t(p) / d grid[v] = scale * w_v(p), scattered to the eight trilinear corners (grid_scatter, dshade.h).
 #pragma once
 #include "kernels.h"
 
@@ -32,9 +35,13 @@ DEV float hg_dlog_dg(float g, float c) {
 // medium segments the reference backpropagates through (segments that end on a surface with tr_c > 0, :425-427).
 DEV float het_null_dlog_dscale(const DMedium &M, float sigma_t, float sigma_n) { return sigma_n > 0.f ? -(sigma_t / sigma_n) / M.scale : 0.f; }
 
-template <bool HET, typename SMP, typename TR>
+// SCATTER (the GRID adjoint's second march, on a copy of the sampler taken before the first): the same draws and ray queries; every
+// ratio-tracking null collision inside the graded medium adds coef_c * d ln(sigma_n_c) / d sigma_t(p) = -coef_c / sigma_n_c, summed over
+// the channels with tr_multiplier_c > 0, to the eight corners of dgrid (coef = delta_L * contrib, known only after the first march).
+template <bool HET, bool SCATTER = false, typename SMP, typename TR>
 DEV V3 prb_sample_emitter(SceneRef sc, SMP &rng, V3 ref_p, V3 ref_n, bool ref_is_surface, uint32_t ref_shape, V3 ref_geo_n,
-                          int medium, uint32_t channel, DirSample *ds_out, const TR &tr, uint32_t &n_shadow, V3 *seg_sum, int grad_medium) {
+                          int medium, uint32_t channel, DirSample *ds_out, const TR &tr, uint32_t &n_shadow, V3 *seg_sum, int grad_medium,
+                          V3 coef = V3(0.f), float *__restrict__ dgrid = nullptr) {
     float sx, sy; rng.next2(sx, sy);
     DirSample ds; V3 emitter_val = sample_emitter_direction(sc, ref_p, sx, sy, &ds);
     *ds_out = ds;
@@ -69,6 +76,12 @@ DEV V3 prb_sample_emitter(SceneRef sc, SMP &rng, V3 ref_p, V3 ref_n, bool ref_is
                     ray.o = mei.p; si.t = si.t - mei.t; mei_t = mei.t;
                     tr_multiplier = mei.sigma_n / mei.combined;
                     if (graded) null_dlog = V3(het_null_dlog_dscale(M, mei.sigma_t.x, mei.sigma_n.x), het_null_dlog_dscale(M, mei.sigma_t.x, mei.sigma_n.y), het_null_dlog_dscale(M, mei.sigma_t.x, mei.sigma_n.z));
+                    if (SCATTER && graded) {
+                        const float a = (tr_multiplier.x > 0.f ? -coef.x / mei.sigma_n.x : 0.f) + (tr_multiplier.y > 0.f ? -coef.y / mei.sigma_n.y : 0.f) +
+                                        (tr_multiplier.z > 0.f ? -coef.z / mei.sigma_n.z : 0.f);
+                        const DHetMedium H = tab(sc.het, medium);
+                        if (a != 0.f) grid_scatter(H, dgrid, xform_point12(H.to_local, mei.p), a);
+                    }
                 }
             } else {                                 // homogeneous: straight to the next surface / the end of the segment (:403-407)
                 (void) rng.next();
@@ -105,9 +118,10 @@ DEV V3 prb_sample_emitter(SceneRef sc, SMP &rng, V3 ref_p, V3 ref_n, bool ref_is
 
 // One trip of prbvolpath's loop (prbvolpath.py:139-349).  s.res holds L: accumulated radiance (primal) or the
 // radiance still to be collected (adjoint).  Returns true when the path survives.
-template <bool ADJOINT, bool HET, typename SMP, typename TR>
+// GRID (ADJOINT && HET only): beside G, the gradient w.r.t. the sigma_t grid of medium rp.grad_medium is scattered into dgrid.
+template <bool ADJOINT, bool HET, bool GRID = false, typename SMP, typename TR>
 DEV bool prb_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const TR &tr, uint32_t &n_shadow,
-                       V3 delta_L, PrbGrads &G) {
+                       V3 delta_L, PrbGrads &G, float *__restrict__ dgrid = nullptr) {
     uint32_t depth = s.flags & PF_DEPTH_MASK;
     const bool proven_empty = (s.flags & PF_NOHIT) != 0;               // look-ahead of the previous trip, see below
     const bool needs_intersection = !(HET && (s.flags & PF_HAVE_SI));  // HET: a null collision keeps the surface interaction found earlier (record's hit stream)
@@ -191,6 +205,19 @@ DEV bool prb_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const TR &
         term(weight.x, L.x, delta_L.x, M.sigma_t[0], M.albedo[0], mei.sigma_n.x, G.sigma_t[0], G.albedo[0]);
         term(weight.y, L.y, delta_L.y, M.sigma_t[1], M.albedo[1], mei.sigma_n.y, G.sigma_t[1], G.albedo[1]);
         term(weight.z, L.z, delta_L.z, M.sigma_t[2], M.albedo[2], mei.sigma_n.z, G.sigma_t[2], G.albedo[2]);
+        if (GRID && het && (act_medium_scatter || act_null_scatter)) {
+            // the last link of the chain rule, sigma_t(p) = scale * sum_v w_v(p) grid[v]: d ln(sigma_s_c) / d sigma_t(p) = 1 / sigma_t(p) at a real
+            // collision, d ln(sigma_n_c) / d sigma_t(p) = -1 / sigma_n_c at a null one (not the d / d scale share divided by grid(p): where the
+            // grid is 0 that share is 0 and this is not); the three channels are summed before the scatter: one add per corner
+            auto coef = [&](float w, float l, float dl, float sn) {
+                const float c = dl * (l / fmax_(1e-8f, w)) * w;
+                if (act_medium_scatter) return mei.sigma_t.x > 0.f ? c / mei.sigma_t.x : 0.f;
+                return sn > 0.f ? -c / sn : 0.f;
+            };
+            const float a = coef(weight.x, L.x, delta_L.x, mei.sigma_n.x) + coef(weight.y, L.y, delta_L.y, mei.sigma_n.y) + coef(weight.z, L.z, delta_L.z, mei.sigma_n.z);
+            const DHetMedium H = tab(sc.het, medium);
+            if (a != 0.f) grid_scatter(H, dgrid, xform_point12(H.to_local, mei.p), a);
+        }
     }
     // ---- surface interactions
     active_surface = active_surface || escaped_medium;
@@ -231,6 +258,7 @@ DEV bool prb_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const TR &
     if (active_e_surface || active_e_medium) {
         DirSample ds; V3 seg_sum;
         V3 rp_ = active_e_medium ? mei.p : si.p, rn = active_e_medium ? V3(0.f) : si.n;
+        SMP rng_march = rng;                          // GRID: the second march replays these draws (prbvolpath.py:268,282-284); unused otherwise
         V3 emitted = prb_sample_emitter<HET>(sc, rng, rp_, rn, active_e_surface, active_e_surface ? si.shape : 0u, si.n, medium, channel, &ds, tr, n_shadow, &seg_sum, gm);
         V3 nee_weight; float nee_pdf;
         if (active_e_surface) { V3 wo = si.sh.to_local(ds.d); nee_weight = bsdf_eval(sc, b, si, wo); nee_pdf = bsdf_pdf(sc, b, si, wo); }
@@ -242,6 +270,13 @@ DEV bool prb_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const TR &
 #endif
         if (ADJOINT) {
             G.sigma_t[0] += delta_L.x * contrib.x * seg_sum.x; G.sigma_t[1] += delta_L.y * contrib.y * seg_sum.y; G.sigma_t[2] += delta_L.z * contrib.z * seg_sum.z;
+            if (GRID) {
+                const V3 coef = delta_L * contrib;
+                if (any_nonzero(coef)) {              // the lane's own sampler is not advanced, and only n_shadow counts the repeated ray queries
+                    DirSample ds2; V3 seg2;
+                    (void) prb_sample_emitter<HET, true>(sc, rng_march, rp_, rn, active_e_surface, active_e_surface ? si.shape : 0u, si.n, medium, channel, &ds2, tr, n_shadow, &seg2, gm, coef, dgrid);
+                }
+            }
             if (active_e_medium && tab(sc.media, medium).phase == LRT_PHASE_HG && (gm < 0 || medium == gm))
                 G.g += (delta_L.x * contrib.x + delta_L.y * contrib.y + delta_L.z * contrib.z) * hg_dlog_dg(tab(sc.media, medium).g, dot(ds.d, mei.wi));
         }
@@ -353,126 +388,21 @@ DEV V3 lane_delta_L(SceneRef sc, RpRef rp, uint32_t lane, const float *__restric
 //                   accumulated per workgroup in f64 (LDS) and added to grads[7] once at the end.
 // 4 waves per SIMD for every variant (128 VGPRs): one 1024-thread workgroup per CU, or four 256-thread ones
 // HET: the scene holds a heterogeneous medium: null collisions (prb_iteration<.., true>), 120-B records (+ the kept surface hit)
+// GRID (k_render_prb_grid; ADJOINT && HET): the adjoint also scatters the gradient w.r.t. the sigma_t grid of medium rp.grad_medium into
+// A.dgrid (grid_scatter, dshade.h).  Both kernels share one body, kernels_prb_body.h, included as text: a body function inlined into
+// both reorders k_render_prb's instructions, and a sixth template parameter renames its symbols; this way both stay as they were.
 template <bool ADJOINT, int BLOCK, bool LDS_BVH, bool LD, bool HET = false>
 __global__ void __launch_bounds__(BLOCK, 4)
 k_render_prb(ScenePtr scp, LaunchPtr lp) {
-    constexpr int MODE = HET ? 2 : 0;
-    SceneRef sc = *scp;
-    const LRT_CONST DLaunch &A = *lp;
-    RpRef rp = A.rp;
-    const LRT_CONST DLdsInfo &li = A.li;
-    const uint32_t P = A.P;
-    float4 *__restrict__ L_buf = A.L_buf; const float *__restrict__ grad_image = A.grad_image; const float *__restrict__ wfilm = A.wfilm;
-    extern __shared__ __align__(16) unsigned char smem[];
-    __shared__ uint32_t s_in[3], s_out[3], s_ticket, s_fresh;
-    __shared__ unsigned long long s_fresh_base;
-    __shared__ double s_grad[7];
-    const uint32_t tid = threadIdx.x, lane_in_wave = tid & 63u;
-    LdsScene L{};
-    if (LDS_BVH) {
-        const uint4 *src = li.blob; uint4 *dst = reinterpret_cast<uint4 *>(smem);
-        for (uint32_t k = tid; k < li.blob_bytes / 16u; k += BLOCK) dst[k] = src[k];
-        L.nodes = reinterpret_cast<const float4 *>(smem + li.nodes_off); L.verts = reinterpret_cast<const float4 *>(smem + li.verts_off);
-        L.tris = reinterpret_cast<const uint2 *>(smem + li.tris_off);
-        L.n_faces = sc.n_faces; L.root_is_leaf = (uint32_t) sc.root_is_leaf; L.root_first = sc.root_leaf_first; L.root_count = sc.root_leaf_count;
-    }
-    const LdsTracer<BLOCK> tr_lds{ L, reinterpret_cast<uint16_t *>(smem + li.stack_off) + tid };
-    const GlobalTracer tr_glb{ sc, reinterpret_cast<int *>(smem) + tid };
-    const size_t pool = (size_t) blockIdx.x * 2u * P;
-    uint32_t parity = 0;                                      // queue the round reads: parity ? q1 : q0 (scalar loads at the point of use)
-    if (tid == 0) { s_in[0] = s_in[1] = s_in[2] = 0; }
-    if (tid < 7) s_grad[tid] = 0.0;
-    bool lanes_left = true;                                   // thread 0
-    uint32_t n_shadow = 0, n_trips = 0, n_loaded = 0;
-    for (;;) {
-        if (tid == 0) {
-            const uint32_t want = P - (s_in[0] + s_in[1] + s_in[2]);
-            uint32_t got = 0; unsigned long long base = 0;
-            if (want && lanes_left) {
-                base = atomicAdd(&A.cnt->next_lane, (unsigned long long) want);
-                if (base < rp.n_lanes) got = (uint32_t) (rp.n_lanes - base < (unsigned long long) want ? rp.n_lanes - base : (unsigned long long) want);
-                lanes_left = base + want < rp.n_lanes;
-            }
-            s_fresh = got; s_fresh_base = base; s_ticket = 0; s_out[0] = s_out[1] = s_out[2] = 0;
-        }
-        __syncthreads();
-        // queue regions as in k_render: A [0, n_a) proven-free in-medium paths, C [P, P + n_c) in-medium paths that need their
-        // ray query, B 2P-1-j paths outside media
-        const uint32_t n_a = s_in[0], n_c = s_in[1], n_s = s_in[2], fresh = s_fresh;
-        const unsigned long long fresh_base = s_fresh_base;
-        if (n_a + n_c + n_s + fresh == 0) break;
-        const uint32_t ta = (n_a + 63u) >> 6, tc = (n_c + 63u) >> 6, ts = (n_s + 63u) >> 6, tf = (fresh + 63u) >> 6, tm = ta + tc;
-        for (;;) {
-            uint32_t t = 0;
-            if (lane_in_wave == 0) t = atomicAdd(&s_ticket, 1u);
-            t = (uint32_t) __builtin_amdgcn_readfirstlane((int) t);
-            if (t >= tm + ts + tf) break;
-            bool had_path = false, alive = false;
-            PathState s; s.flags = 0; s.lane = 0; s.res = V3(0.f);
-            float4 dl = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (t < tm + ts) {
-                uint32_t i;
-                if (t < ta) { i = (t << 6) + lane_in_wave; had_path = i < n_a; }
-                else if (t < tm) { i = ((t - ta) << 6) + lane_in_wave; had_path = i < n_c; i += P; }
-                else { i = ((t - tm) << 6) + lane_in_wave; had_path = i < n_s; i = 2u * P - 1u - i; }
-                if (had_path) { load_state<MODE>(parity ? A.q1 : A.q0, pool + i, s); dl = (parity ? A.dl1 : A.dl0)[pool + i]; n_loaded += 1; }
-            } else {
-                const uint32_t i = ((t - tm - ts) << 6) + lane_in_wave;
-                had_path = i < fresh;
-                if (had_path) {                                // common.py:231-309 + prbvolpath.py:113-137
-                    const unsigned long long slot = fresh_base + i;
-                    s = generate_camera_path<LD>(sc, rp, A.pixel_list, A.lane_begin + slot);
-                    s.flags = PF_SPECULAR | (s.flags & (3u << PF_CHANNEL_SHIFT));      // valid_ray = false, specular_chain = true, medium = none
-                    V3 dL(0.f);
-                    if (ADJOINT) { float4 l = L_buf[slot]; s.res = V3(l.x, l.y, l.z); dL = lane_delta_L(sc, rp, s.lane, grad_image, wfilm); }
-                    dl = make_float4(dL.x, dL.y, dL.z, u2f((uint32_t) slot));
-                }
-            }
-            PrbGrads G; G.sigma_t[0] = G.sigma_t[1] = G.sigma_t[2] = G.albedo[0] = G.albedo[1] = G.albedo[2] = G.g = 0.f;
-            if (had_path) {
-                SamplerT<LD> rng = lane_rng_resume<LD>(rp, s.lane, s.rng_state);
-                alive = LDS_BVH ? prb_iteration<ADJOINT, HET>(sc, rp, s, rng, tr_lds, n_shadow, V3(dl.x, dl.y, dl.z), G)
-                                : prb_iteration<ADJOINT, HET>(sc, rp, s, rng, tr_glb, n_shadow, V3(dl.x, dl.y, dl.z), G);
-                s.rng_state = rng.state;
-                n_trips += 1;
-            }
-            if (!ADJOINT) {
-                if (L_buf) { if (had_path && !alive) L_buf[f2u(dl.w)] = make_float4(s.res.x, s.res.y, s.res.z, (s.flags & PF_VALID) ? 1.f : 0.f); }
-                else finish_paths_wave(sc, rp, A.film, A.sample_out, A.sample_base, had_path && !alive, s.lane, s.res, (s.flags & PF_VALID) != 0);
-            } else {
-                float g[7] = { G.sigma_t[0], G.sigma_t[1], G.sigma_t[2], G.albedo[0], G.albedo[1], G.albedo[2], G.g };
-#pragma unroll
-                for (int k = 0; k < 7; ++k) {
-                    const float v = wave_sum(g[k]);
-                    if (lane_in_wave == 0 && v != 0.f) atomicAdd(&s_grad[k], (double) v);
-                }
-            }
-            // compaction into the three regions
-            const int region = !(s.flags & PF_MEDIUM_MASK) ? 2 : ((s.flags & PF_NOHIT) ? 0 : 1);
-            const unsigned long long m0 = __ballot(alive && region == 0), m1 = __ballot(alive && region == 1), m2 = __ballot(alive && region == 2);
-            uint32_t base = 0;
-            if (lane_in_wave < 3) { const uint32_t c = (uint32_t) __popcll(lane_in_wave == 0 ? m0 : (lane_in_wave == 1 ? m1 : m2)); if (c) base = atomicAdd(&s_out[lane_in_wave], c); }
-            const uint32_t b0 = (uint32_t) __builtin_amdgcn_readlane((int) base, 0), b1 = (uint32_t) __builtin_amdgcn_readlane((int) base, 1), b2 = (uint32_t) __builtin_amdgcn_readlane((int) base, 2);
-            const uint32_t b = region == 0 ? b0 : (region == 1 ? b1 : b2);          // (v_readlane, not a shuffle through LDS: see retire_and_compact_wave)
-            if (alive) {
-                const uint32_t slot = b + (uint32_t) __popcll((region == 0 ? m0 : (region == 1 ? m1 : m2)) & ((1ull << lane_in_wave) - 1ull));
-                const uint32_t rec = region == 0 ? slot : (region == 1 ? P + slot : 2u * P - 1u - slot);
-                store_state<MODE>(parity ? A.q0 : A.q1, pool + rec, s); (parity ? A.dl0 : A.dl1)[pool + rec] = dl;
-            }
-        }
-        __syncthreads();
-        if (tid == 0) { s_in[0] = s_out[0]; s_in[1] = s_out[1]; s_in[2] = s_out[2]; }
-        parity ^= 1u;
-    }
-    if (ADJOINT && tid < 7 && s_grad[tid] != 0.0) atomicAdd(&A.grads[tid], s_grad[tid]);
-    for (int off = 32; off > 0; off >>= 1) {
-        n_shadow += __shfl_down(n_shadow, off); n_trips += __shfl_down(n_trips, off); n_loaded += __shfl_down(n_loaded, off);
-    }
-    if (lane_in_wave == 0) {
-        if (n_shadow) atomicAdd(&A.cnt->n_shadow, (unsigned long long) n_shadow);
-        if (n_trips) atomicAdd(&A.cnt->n_iter, (unsigned long long) n_trips);
-        if (n_loaded) atomicAdd(&A.cnt->n_records, (unsigned long long) n_loaded);
-    }
+    constexpr bool GRID = false;
+#include "kernels_prb_body.h"
+}
+
+template <int BLOCK, bool LDS_BVH, bool LD>
+__global__ void __launch_bounds__(BLOCK, 4)
+k_render_prb_grid(ScenePtr scp, LaunchPtr lp) {
+    constexpr bool ADJOINT = true, HET = true, GRID = true;
+#include "kernels_prb_body.h"
 }
 
 } // namespace lrt
