@@ -255,7 +255,7 @@ typedef struct {
 typedef struct lrt_scene lrt_scene;
 
 LRT_API const char *lrt_last_error(void);
-LRT_API int         lrt_version(void);   /* 112: lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
+LRT_API int         lrt_version(void);   /* 113: lrt_bsdf_probe; 112:lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
 
 LRT_API lrt_status lrt_scene_load_xml(const char *path, const char *const *defines,
                                       int n_defines, lrt_scene **out);
@@ -341,6 +341,20 @@ LRT_API lrt_status lrt_emitter_probe(lrt_scene *scene, const float *ref_p, const
  * leaves the scene: out[4 i] = Scene::pdf_emitter_direction for the miss (the factor 1 / n_emitters included), out[4 i + 1 .. 3] =
  * the emitter's eval.  LRT_ERR_* if the scene has no environment emitter. */
 LRT_API lrt_status lrt_envmap_probe(lrt_scene *scene, const float *dir, uint32_t n, float *out, int device);
+
+/* Test hook [v113]: the surface code of the render kernels (csrc/dshade.h) at chosen rays, one per lane.  For input i: a closest-hit
+ * query along (o[3 i ..], d[3 i ..]) over triangles and spheres, without a ray offset (Scene::ray_intersect); the surface
+ * interaction of the hit (Mesh / Sphere::compute_surface_interaction: p, n, sh_frame, uv, wi); then, on the hit shape's BSDF,
+ * BSDF::sample(ctx, si, sample[3 i], (sample[3 i + 1], sample[3 i + 2])) in radiance mode as the integrators draw it, and
+ * BSDF::eval / BSDF::pdf(ctx, si, si.to_local(wo_query[3 i ..])) as they evaluate it for an emitter sample.
+ * out: LRT_BSDF_PROBE_FLOATS floats per input:
+ *   [0] shape of the hit (-1: miss, the rest is then 0), [1] t, [2..4] p, [5..7] n (geometric), [8..10] sh_frame.n, [11..12] uv,
+ *   [13..15] wi (local); the sample: [16..18] si.to_world(bs.wo), [19] bs.wo.z (local), [20] bs.pdf, [21] bs.eta,
+ *   [22] bs.sampled_type as this library keeps it (1 delta, 2 smooth, 4 null, 0 none), [23..25] the BSDF weight;
+ *   [26..28] eval and [29] pdf at wo_query.  Indices are stored as floats. */
+#define LRT_BSDF_PROBE_FLOATS 30
+LRT_API lrt_status lrt_bsdf_probe(lrt_scene *scene, const float *o, const float *d, const float *sample, const float *wo_query,
+                                  uint32_t n, float *out, int device);
 
 /* SoA ray queries (layout mirrors RayHit of src/render/scene_native.inl:135-142).
  * Miss: t = +inf, prim = 0xffffffff.  any_hit: only t (0 on hit, +inf on miss). */

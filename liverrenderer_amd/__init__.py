@@ -494,6 +494,20 @@ class Scene:
         _lib.check(self._lib.lrt_envmap_probe(self._h, d.ctypes.data_as(FP), d.shape[0], out.ctypes.data_as(FP), int(device)))
         return out[:, 0].copy(), out[:, 1:4].copy()
 
+    def bsdf_probe(self, o, d, sample, wo_query, device=0):
+        """lrt_bsdf_probe (test hook): per ray (o, d) (n x 3 each) the closest hit without a ray offset, its surface interaction, the hit
+        shape's BSDF sampled with sample (n x 3: s1, s2.x, s2.y) as the integrators do, and its eval / pdf at the world direction
+        wo_query (n x 3).  Returns a dict of arrays: shape (int, -1: miss), t, p, n, sh_n, uv, wi (local), wo (world), wo_z (local),
+        pdf, eta, type (int), weight, eval, eval_pdf, and raw (n x LRT_BSDF_PROBE_FLOATS, every float as returned)."""
+        a = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3) for x in (o, d, sample, wo_query)]
+        n = a[0].shape[0]
+        if any(x.shape[0] != n for x in a):
+            raise ValueError("bsdf_probe: o, d, sample and wo_query must have the same number of rows")
+        out = np.empty((n, _lib.BSDF_PROBE_FLOATS), dtype=np.float32)
+        FP = C.POINTER(C.c_float)
+        _lib.check(self._lib.lrt_bsdf_probe(self._h, *[x.ctypes.data_as(FP) for x in a], n, out.ctypes.data_as(FP), int(device)))
+        return _lib.bsdf_probe_fields(out)
+
     # -- parameters (mi.traverse) -------------------------------------------
     def param_set(self, key, value):
         """lrt_param_set.  "<id>.sigma_t.data" takes an array of shape (res_z, res_y, res_x) (or its flattening)."""

@@ -1566,6 +1566,24 @@ void device_envmap_probe(DeviceScene *D, const float *dir, uint32_t n, float *ou
     HIP_CHECK(hipStreamSynchronize(st));
 }
 
+// Test hook (include/liverrt.h lrt_bsdf_probe): k_bsdf_probe (kernels.h) on the scene's device image
+void device_bsdf_probe(DeviceScene *D, const float *o, const float *d, const float *sample, const float *wo_query, uint32_t n, float *out) {
+    HIP_CHECK(hipSetDevice(D->device));
+    if (!n) return;
+    hipStream_t st = D->stream;
+    struct Tmp { float *p = nullptr; ~Tmp() { if (p) (void) hipFree(p); } } in[4], dout;
+    const float *src[4] = { o, d, sample, wo_query };
+    for (int k = 0; k < 4; ++k) {
+        HIP_CHECK(hipMalloc((void **) &in[k].p, (size_t) n * 3 * 4));
+        HIP_CHECK(hipMemcpyAsync(in[k].p, src[k], (size_t) n * 3 * 4, hipMemcpyHostToDevice, st));
+    }
+    HIP_CHECK(hipMalloc((void **) &dout.p, (size_t) n * LRT_BSDF_PROBE_FLOATS * 4));
+    k_bsdf_probe<<<(n + LRT_BLOCK - 1) / LRT_BLOCK, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, in[0].p, in[1].p, in[2].p, in[3].p, n, dout.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * LRT_BSDF_PROBE_FLOATS * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
 // Test hook (include/liverrt.h lrt_math_eval): the transcendental kernels of csrc/dmath.h evaluated on the device, one lane per value.
 // orc_math.h holds the same polynomials written a second time, so bit-equality of the render lanes says nothing about their accuracy:
 // tests/test_parity_gpu.py bounds the DEVICE values against float64 and checks them bit for bit against the oracle's twins.

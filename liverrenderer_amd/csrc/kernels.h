@@ -1224,4 +1224,38 @@ k_envmap_probe(ScenePtr scp, const float *__restrict__ dir, uint32_t n, float *_
     o[0] = pdf; o[1] = le.x; o[2] = le.y; o[3] = le.z;
 }
 
+// Test hook (lrt_bsdf_probe): the surface code at a chosen ray, one per lane: a closest-hit query through the EXT tracer (spheres count),
+// no ray offset; the surface interaction; bsdf_sample with the lane's (s1, s2x, s2y) as path_iteration calls it; bsdf_eval and bsdf_pdf
+// at the world direction woq, brought into the shading frame as the integrators bring an emitter sample's direction.
+__global__ void __launch_bounds__(LRT_BLOCK)
+k_bsdf_probe(ScenePtr scp, const float *__restrict__ ro, const float *__restrict__ rd, const float *__restrict__ smp, const float *__restrict__ woq,
+             uint32_t n, float *__restrict__ out) {
+    SceneRef sc = *scp;
+    __shared__ int s_stack[LRT_STACK * LRT_BLOCK];
+    const uint32_t i = blockIdx.x * LRT_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const size_t k = 3 * (size_t) i;
+    float *o = out + (size_t) LRT_BSDF_PROBE_FLOATS * i;
+    const GlobalTracer tg{ sc, s_stack + threadIdx.x };
+    const ExtTracer<GlobalTracer> tr{ tg, sc };
+    Ray r; r.o = V3(ro[k], ro[k + 1], ro[k + 2]); r.d = V3(rd[k], rd[k + 1], rd[k + 2]); r.maxt = kLargest;
+    const Hit h = tr.closest(r);
+    const SI si = tr.surface(sc, r, h);
+    if (!si.valid) {
+        o[0] = -1.f;
+        for (int j = 1; j < LRT_BSDF_PROBE_FLOATS; ++j) o[j] = 0.f;
+        return;
+    }
+    const int b = tab(sc.shapes, si.shape, sc.one_shape).bsdf;
+    const BSDFSample bs = bsdf_sample(sc, b, si, smp[k], smp[k + 1], smp[k + 2]);
+    const V3 wow = si.sh.to_world(bs.wo);
+    const V3 wo = si.sh.to_local(V3(woq[k], woq[k + 1], woq[k + 2]));
+    const V3 ev = bsdf_eval(sc, b, si, wo);
+    const float pdf = bsdf_pdf(sc, b, si, wo);
+    o[0] = (float) si.shape; o[1] = si.t; o[2] = si.p.x; o[3] = si.p.y; o[4] = si.p.z; o[5] = si.n.x; o[6] = si.n.y; o[7] = si.n.z;
+    o[8] = si.sh.n.x; o[9] = si.sh.n.y; o[10] = si.sh.n.z; o[11] = si.uv.x; o[12] = si.uv.y; o[13] = si.wi.x; o[14] = si.wi.y; o[15] = si.wi.z;
+    o[16] = wow.x; o[17] = wow.y; o[18] = wow.z; o[19] = bs.wo.z; o[20] = bs.pdf; o[21] = bs.eta; o[22] = (float) bs.type;
+    o[23] = bs.weight.x; o[24] = bs.weight.y; o[25] = bs.weight.z; o[26] = ev.x; o[27] = ev.y; o[28] = ev.z; o[29] = pdf;
+}
+
 } // namespace lrt

@@ -13,7 +13,9 @@
  * (tests/test_oracle_pins.py): TEA vectors (src/core/tests/test_random.py:9-26),
  * the Cornell-box radiance known answer (src/integrators/tests/test_integrators.py:28-53),
  * the staircase ray depths (src/render/tests/test_kdtrees.py:47-83), phase
- * function values (src/phase/tests/test_isotropic.py:11-21), published PCG32
+ * function values (src/phase/tests/test_isotropic.py:11-21), the BSDF vectors of
+ * src/bsdfs/tests/test_dielectric.py, test_diffuse.py and src/render/tests/test_fresnel.py
+ * (tests/golden/bsdf_known_answers.json through orc_bsdf_probe), published PCG32
  * vectors, plus analytic furnace tests.  volpath radiance and PRB gradients
  * have no in-tree numeric fixture: "parity unpinned by the reference" for those,
  * pinned by analytic tests + finite differences instead.
@@ -86,6 +88,8 @@ float orc_hg_eval(float g, float cos_theta);
 void  orc_square_to_cosine_hemisphere(float u1, float u2, float out[3]);
 void  orc_square_to_uniform_sphere(float u1, float u2, float out[3]);
 void  orc_fresnel(float cos_theta_i, float eta, float out[4]);
+/* lrt_bsdf_probe on the oracle: LRT_BSDF_PROBE_FLOATS floats per input, the layout of include/liverrt.h (triangle shapes only) */
+void  orc_bsdf_probe(orc_scene *s, const float *o, const float *d, const float *sample, const float *wo_query, uint32_t n, float *out);
 void  orc_envmap_sample(orc_scene *s, float u1, float u2, float ref[3], float d[3], float *pdf, float rgb[3]);
 float orc_envmap_pdf(orc_scene *s, const float d[3]);
 void  orc_envmap_eval(orc_scene *s, const float d[3], float rgb[3]);

@@ -1477,6 +1477,31 @@ extern "C" float orc_hg_eval(float g, float c) { return hg_eval(g, c); }
 extern "C" void orc_square_to_cosine_hemisphere(float u1, float u2, float o[3]) { V3 v = square_to_cosine_hemisphere(u1, u2); o[0] = v.x; o[1] = v.y; o[2] = v.z; }
 extern "C" void orc_square_to_uniform_sphere(float u1, float u2, float o[3]) { V3 v = square_to_uniform_sphere(u1, u2); o[0] = v.x; o[1] = v.y; o[2] = v.z; }
 extern "C" void orc_fresnel(float c, float eta, float out[4]) { fresnel(c, eta, &out[0], &out[1], &out[2], &out[3]); }
+/* The oracle's side of lrt_bsdf_probe (include/liverrt.h): closest hit along (o, d) without a ray offset, the surface interaction,
+   bsdf_sample as path_iteration draws it, bsdf_eval / bsdf_pdf at the world direction wo_query.  The oracle holds no spheres. */
+extern "C" void orc_bsdf_probe(orc_scene *s, const float *o, const float *d, const float *sample, const float *wo_query, uint32_t n, float *out) {
+    const Scene &S = s->s;
+    for (uint32_t i = 0; i < n; ++i) {
+        float *q = out + (size_t) LRT_BSDF_PROBE_FLOATS * i;
+        for (int k = 0; k < LRT_BSDF_PROBE_FLOATS; ++k) q[k] = 0.f;
+        q[0] = -1.f;
+        Ray r; r.o = V3(o[3 * i], o[3 * i + 1], o[3 * i + 2]); r.d = V3(d[3 * i], d[3 * i + 1], d[3 * i + 2]); r.maxt = kLargest;
+        const Hit h = S.intersect(r, false, false);
+        const SI si = S.compute_si(r, h);
+        if (!si.valid) continue;
+        const int b = S.shapes[si.shape].bsdf;
+        BSDFSample bs; V3 w;
+        bsdf_sample(S, b, si, sample[3 * i], sample[3 * i + 1], sample[3 * i + 2], &bs, &w);
+        const V3 wow = si.sh.to_world(bs.wo);
+        const V3 woq = si.sh.to_local(V3(wo_query[3 * i], wo_query[3 * i + 1], wo_query[3 * i + 2]));
+        const V3 ev = bsdf_eval(S, b, si, woq);
+        const float pdf = bsdf_pdf(S, b, si, woq);
+        q[0] = (float) si.shape; q[1] = si.t; q[2] = si.p.x; q[3] = si.p.y; q[4] = si.p.z; q[5] = si.n.x; q[6] = si.n.y; q[7] = si.n.z;
+        q[8] = si.sh.n.x; q[9] = si.sh.n.y; q[10] = si.sh.n.z; q[11] = si.uv.x; q[12] = si.uv.y; q[13] = si.wi.x; q[14] = si.wi.y; q[15] = si.wi.z;
+        q[16] = wow.x; q[17] = wow.y; q[18] = wow.z; q[19] = bs.wo.z; q[20] = bs.pdf; q[21] = bs.eta; q[22] = (float) bs.type;
+        q[23] = w.x; q[24] = w.y; q[25] = w.z; q[26] = ev.x; q[27] = ev.y; q[28] = ev.z; q[29] = pdf;
+    }
+}
 extern "C" void orc_envmap_sample(orc_scene *s, float u1, float u2, float ref[3], float d[3], float *pdf, float rgb[3]) {
     DirSample ds; V3 w = sample_emitter_direction(s->s, V3(ref[0], ref[1], ref[2]), u1, u2, &ds);
     d[0] = ds.d.x; d[1] = ds.d.y; d[2] = ds.d.z; *pdf = ds.pdf; rgb[0] = w.x; rgb[1] = w.y; rgb[2] = w.z;

@@ -75,6 +75,8 @@ def lib():
     L.orc_envmap_pdf.argtypes = [C.c_void_p, P(C.c_float)]
     L.orc_envmap_pdf.restype = C.c_float
     L.orc_envmap_eval.argtypes = [C.c_void_p, P(C.c_float), P(C.c_float)]
+    L.orc_bsdf_probe.argtypes = [C.c_void_p, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), C.c_uint32, P(C.c_float)]
+    L.orc_bsdf_probe.restype = None
     L.orc_rfilter_eval.argtypes = [C.c_void_p, C.c_float]
     L.orc_rfilter_eval.restype = C.c_float
     L.orc_sample_ray.argtypes = [C.c_void_p, C.c_float, C.c_float, P(C.c_float), P(C.c_float), P(C.c_float)]
@@ -187,6 +189,15 @@ class OrcScene:
         d = np.asarray(d, np.float32); rgb = np.zeros(3, np.float32)
         self._L.orc_envmap_eval(self._h, _fp(d), _fp(rgb))
         return rgb
+
+    def bsdf_probe(self, o, d, sample, wo_query):
+        """orc_bsdf_probe: the oracle's twin of Scene.bsdf_probe, the same dict of arrays (triangle shapes only)"""
+        a = [np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (o, d, sample, wo_query)]
+        n = a[0].shape[0]
+        assert all(x.shape[0] == n for x in a)
+        out = np.empty((n, _lib.BSDF_PROBE_FLOATS), np.float32)
+        self._L.orc_bsdf_probe(self._h, *[_fp(x) for x in a], n, _fp(out))
+        return _lib.bsdf_probe_fields(out)
 
     def envmap_sample_n(self, samples, ref=(0, 0, 0)):
         """envmap_sample at n samples (n, 2): directions (n, 3), pdfs (n,), weights (n, 3)"""
