@@ -826,6 +826,20 @@ static void check_integrator_media(DeviceScene *D, int integrator) {
 //   3. the only emitter hit is the escape to the infinite emitter (c), and it ends the path.  A lane inside a medium never escapes (its
 //      free flight is finite, (a)), so the escape follows a surface event, a delta bounce (b), which sets specular_chain; or it happens
 //      at depth 0.  Either way count_direct holds and last_pdf / the last scatter position are not read.
+// What the closed instances no longer compile (volpath_iteration<false, CLOSED = true>; each branch below is dead by the clause it names):
+//   4. the surface emitter sampling (a second inlined volpath_sample_emitter, bsdf_eval, bsdf_pdf): 1., (b).  Its not-taken rng.skip(1) stays;
+//   5. the hide_emitters skip loop at depth 0: it runs only when the first hit is a shape that is an emitter; no shape is one, (c).  The
+//      `active_e` test after it still reads hide_emitters (the escape at depth 0 is hidden);
+//   6. the in-medium shadow march beyond its observable part.  Its value is +0 by 2. and is not added, so what remains is the emitter sample
+//      (two draws; a zero density ends it there), the march's single free-flight draw (or the skipped one when the segment is empty) and
+//      the count of the shadow query the reference needs: exactly when that free flight leaves the segment (`!elide`: no null BSDF (b),
+//      no heterogeneous medium (a)).  The march has no second trip: a valid collision multiplies the transmittance by sigma_n / combined
+//      = 0 (a), an escape meets a non-null surface (b) or nothing.  The query itself is not traced: its result fed the discarded value only;
+//   7. the BSDF dispatch of bsdf_sample: every leaf is a dielectric, under a bumpmap or not (b); the diffuse and null branches go;
+//   8. emitters on shapes: si_emitter of a hit is -1 and emitter_eval is the infinite emitter's value on a miss, (c).
+//      Since then the guard's "emitter hit without count_direct" sees the escape only: an emitting shape on a scene that got past this function
+//      would lose its radiance without tripping n_closed_guard.  Clause (c) is tested below on the host for every render and is what rules it out.
+//   (target_medium keeps its exterior branch although (a) makes it dead: removing it did not make the kernels smaller)
 // So every queued record's radiance is +0 and a path's radiance is its last trip's: 0 + ... + 0 + c = c, bit for bit.  The kernels check 3. on every
 // trip (DCounters::n_closed_guard: nonzero radiance on a lane that goes on, an emitter hit without count_direct) and the render fails instead of
 // returning a wrong image.  2. is not checked (that check cost 2.5 % on C3): it rests on the conditions above alone.

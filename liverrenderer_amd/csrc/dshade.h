@@ -616,16 +616,18 @@ DEV float shadow_terminator(V3 pn, V3 wo) {       // src/bsdfs/normalmap_helpers
 }
 
 // Leaf BSDFs (diffuse / dielectric / null), evaluated in the frame `wi` is given in.
+// DIELECTRIC: the caller has proven that the leaf is a dielectric (the 64-byte-record kernels, closed_records (b) in device.hip): no dispatch.
+template <bool DIELECTRIC = false>
 DEV BSDFSample leaf_sample(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, float s1, float s2x, float s2y) {
     BSDFSample bs;
     bs.wo = V3(0.f); bs.pdf = 0.f; bs.eta = 0.f; bs.type = 0; bs.weight = V3(0.f);       // dr::zeros<BSDFSample3f>
-    if (B.type == LRT_BSDF_DIFFUSE) {               // src/bsdfs/diffuse.cpp sample()
+    if (!DIELECTRIC && B.type == LRT_BSDF_DIFFUSE) {               // src/bsdfs/diffuse.cpp sample()
         if (wi.z > 0.f) {
             bs.wo = square_to_cosine_hemisphere(s2x, s2y);
             bs.pdf = kInvPi * bs.wo.z; bs.eta = 1.f; bs.type = F_SMOOTH;
             if (bs.pdf > 0.f) bs.weight = tex_eval(sc, B.reflectance, si);
         }
-    } else if (B.type == LRT_BSDF_DIELECTRIC) {     // src/bsdfs/dielectric.cpp:230-367
+    } else if (DIELECTRIC || B.type == LRT_BSDF_DIELECTRIC) {     // src/bsdfs/dielectric.cpp:230-367
         float r_i, ctt, eta_it, eta_ti;
         fresnel(wi.z, B.eta, &r_i, &ctt, &eta_it, &eta_ti);
         float t_i = 1.f - r_i;
@@ -657,12 +659,13 @@ DEV float leaf_pdf(const DBsdf &B, V3 wi, V3 wo) {
     return 0.f;
 }
 
+template <bool DIELECTRIC = false>                 // (every leaf is a dielectric, see leaf_sample)
 DEV BSDFSample bsdf_sample(SceneRef sc, int b, const SI &si, float s1, float s2x, float s2y) {
     const DBsdf B = tab(sc.bsdfs, b, sc.one_shape);
     if (B.type == LRT_BSDF_BUMPMAP) {               // src/bsdfs/bumpmap.cpp:138-162
         Frame pf = bump_frame(sc, B, si);
         V3 pwi = pf.to_local(si.wi);
-        BSDFSample bs = leaf_sample(sc, tab(sc.bsdfs, B.nested, sc.one_shape), si, pwi, s1, s2x, s2y);
+        BSDFSample bs = leaf_sample<DIELECTRIC>(sc, tab(sc.bsdfs, B.nested, sc.one_shape), si, pwi, s1, s2x, s2y);
         bool active = any_nonzero(bs.weight);
         V3 pwo = pf.to_world(bs.wo);
         active = active && (bs.wo.z * pwo.z > 0.f);
@@ -671,7 +674,7 @@ DEV BSDFSample bsdf_sample(SceneRef sc, int b, const SI &si, float s1, float s2x
         bs.weight = active ? w : V3(0.f);
         return bs;
     }
-    return leaf_sample(sc, B, si, si.wi, s1, s2x, s2y);
+    return leaf_sample<DIELECTRIC>(sc, B, si, si.wi, s1, s2x, s2y);
 }
 DEV V3 bsdf_eval(SceneRef sc, int b, const SI &si, V3 wo) {
     const DBsdf B = tab(sc.bsdfs, b, sc.one_shape);

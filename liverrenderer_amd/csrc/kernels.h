@@ -421,8 +421,9 @@ struct WaveCount {
 // that is known to run its next trip, with the throughput already divided by the survival probability, the free-flight distance
 // in the record (ff_t) and, when the distance field proves that distance free of surfaces, PF_NOHIT.
 // CLOSED (64-byte records, MODE 4): the host has proven that only a path's last trip adds radiance (closed_records in device.hip): `result`
-// starts at 0 every trip and leaves in s.res for the film only; in-medium NEE, which the proof makes +0, is run for its draws and shadow-ray
-// counts but not added; last_pdf and the last scatter position are never read.  A trip that breaks the premise (nonzero radiance on a lane that
+// starts at 0 every trip and leaves in s.res for the film only; in-medium NEE, which the proof makes +0, is reduced to its draws and its
+// shadow-ray count; last_pdf and the last scatter position are never read.  The branches the same proof makes dead (surface NEE, the
+// hide_emitters skip, BSDFs other than a dielectric, emitters on shapes) are not compiled: closed_records, steps 4 to 8.  A trip that breaks the premise (nonzero radiance on a lane that
 // goes on, an emitter hit that needs the MIS weight) adds one to *guard: the host reports an error.  (Checking the in-medium NEE term too was
 // measured at 2.5 % on C3: it keeps the phase function and the emitter value alive through the march.  DESIGN.md section 6c.)
 template <bool HET, bool CLOSED = false, typename SMP, typename TR, typename CNT>
@@ -554,12 +555,25 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
                 }
                 if (!rejected) rng = saved;
             }
-            if (!rejected) {
+            if (!rejected && CLOSED) {
+                // What volpath_sample_emitter observably does on a closed scene (closed_records in device.hip, steps 2 and 6): its value is +0 and was
+                // never added, so only its draws and its count of shadow queries remain.  The march runs ONE trip: a valid collision multiplies
+                // the transmittance by sigma_n / combined = 0 (homogeneous medium, (a)), an escape meets a surface whose null transmission
+                // is 0 (b), or nothing; either way `active` is false after the trip.  Its query is needed exactly when the collision is not valid
+                // (`!elide`: no null BSDF (b), no heterogeneous medium (a)); it is counted, not traced: its result fed the discarded value only.
+                float sx, sy; rng.next2(sx, sy);
+                DirSample ds; (void) sample_emitter_direction<TR::kExt>(sc, mei.p, sx, sy, &ds);
+                if (ds.pdf != 0.f) {                                        // (a zero density skips the march and its draw)
+                    const Ray r2 = spawn_ray_to(mei.p, V3(0.f), ds.p);
+                    if (!(r2.maxt > 0.f)) rng.skip(1);
+                    else { const MI m2 = medium_sample_interaction(M, r2, rng.next(), channel); if (!m2.valid()) n_shadow++; }
+                }
+            } else if (!rejected) {
                 DirSample ds;
                 V3 emitted = volpath_sample_emitter<HET>(sc, rng, mei.p, V3(0.f), false, 0, V3(0.f), medium, channel, &ds, tr, n_shadow);
                 float phase_val = phase_eval(M, mei.wi, ds.d);
                 V3 c = throughput * phase_val * emitted * mis_weight(ds.pdf, ds.delta ? 0.f : phase_val);
-                if (!CLOSED) result = result + c;
+                result = result + c;
             }
         }
         (void) rng.next();
@@ -579,7 +593,7 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
         if (active_surface) si = tr.surface(sc, ray, h);
     } else if (intersect) { Hit h = tr.closest(ray); si = tr.surface(sc, ray, h); }
     if (active_surface) {
-        if (rp.hide_emitters && depth == 0 && intersect) {         // volpath.cpp:304-320, integrator.cpp:96-123
+        if (!CLOSED && rp.hide_emitters && depth == 0 && intersect) {         // volpath.cpp:304-320, integrator.cpp:96-123 (CLOSED: no shape is an emitter, (c): `skip` is false)
             bool skip = si.valid && tab(sc.shapes, si.shape, sc.one_shape).emitter >= 0;
             if (skip) {
                 Ray r2 = spawn_ray(si.p, si.n, ray.d);
@@ -593,10 +607,10 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
             }
         }
         bool count_direct = (depth == 0) || specular_chain;
-        int emitter = si_emitter(sc, si);
+        int emitter = CLOSED ? (si.valid ? -1 : sc.env.emitter) : si_emitter(sc, si);      // (CLOSED: no shape is an emitter, (c): only a miss reaches one)
         bool active_e = emitter >= 0 && !(depth == 0 && rp.hide_emitters);
         if (active_e) {
-            if (CLOSED) { broken = broken || !count_direct; result = result + throughput * emitter_eval(sc, emitter, si); }     // (count_direct: no MIS weight)
+            if (CLOSED) { broken = broken || !count_direct; result = result + throughput * emitter_eval_env(sc, -si.wi); }     // (count_direct: no MIS weight; emitter_eval of a miss)
             else {
                 float emitter_pdf = 1.f;
                 if (!count_direct) emitter_pdf = pdf_emitter_direction<TR::kExt>(sc, s.lp, si, emitter);
@@ -612,7 +626,7 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
         const DShape sd = tab(sc.shapes, si.shape, sc.one_shape);
         int b = sd.bsdf;
         int flags = tab(sc.bsdfs, b, sc.one_shape).flags;
-        bool active_e = (flags & F_SMOOTH) && (depth + 1 < max_depth);
+        bool active_e = !CLOSED && (flags & F_SMOOTH) && (depth + 1 < max_depth);     // (CLOSED: no F_SMOOTH lobe, (b); the draw below is still skipped)
         if (!active_e) rng.skip(1);
         if (active_e) {
             DirSample ds;
@@ -624,7 +638,7 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
             result = result + c;
         }
         float s1 = rng.next(), s2x, s2y; rng.next2(s2x, s2y);
-        const BSDFSample bs = bsdf_sample(sc, b, si, s1, s2x, s2y);
+        const BSDFSample bs = bsdf_sample<CLOSED>(sc, b, si, s1, s2x, s2y);    // (CLOSED: dielectric, or bumpmap over dielectric, (b))
         throughput = throughput * bs.weight;
         eta *= bs.eta;
         ray = spawn_ray(si.p, si.n, si.sh.to_world(bs.wo));
