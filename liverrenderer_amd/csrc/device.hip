@@ -35,6 +35,35 @@ template <typename T> static T *dev_upload(const T *src, size_t n, hipStream_t s
     return p;
 }
 
+// A temporary device buffer of one call, freed when the call returns or throws.
+struct DevTmp {
+    float *p = nullptr;
+    DevTmp() = default;
+    explicit DevTmp(size_t floats) { alloc(floats); }
+    DevTmp(const DevTmp &) = delete; DevTmp &operator=(const DevTmp &) = delete;
+    void alloc(size_t floats) { HIP_CHECK(hipMalloc((void **) &p, std::max<size_t>(floats, 1) * sizeof(float))); }
+    void upload(const float *src, size_t floats, hipStream_t st) { alloc(floats); HIP_CHECK(hipMemcpyAsync(p, src, floats * sizeof(float), hipMemcpyHostToDevice, st)); }
+    ~DevTmp() { if (p) (void) hipFree(p); }
+};
+
+// the checks of every entry point that names a device by its ordinal
+static void select_device(int device) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) throw std::runtime_error("no HIP device available: the hip_ad_rgb back-end has no CPU fallback");
+    if (device < 0 || device >= count) throw std::runtime_error("invalid HIP device ordinal " + std::to_string(device));
+    HIP_CHECK(hipSetDevice(device));
+}
+
+// lrt_render_opts of a call without any: everything "the scene's own", one tile
+static lrt_render_opts default_opts() { return lrt_render_opts{ -1, -2, -1, -1, 0, 0, 0, 1, 0, 0, 0, 0 }; }
+
+// one launch's (or one nested render's) stats added to a sequential total
+static void add_stats(lrt_render_stats &total, const lrt_render_stats &s) {
+    total.n_samples += s.n_samples; total.n_iter += s.n_iter; total.n_shadow += s.n_shadow; total.n_launches += s.n_launches;
+    total.n_records += s.n_records; total.kernel_ms += s.kernel_ms; total.total_ms += s.total_ms;
+    total.record_bytes = s.record_bytes; total.n_closed_guard += s.n_closed_guard;
+}
+
 #define LRT_LAUNCH_SLOTS 64
 #define LRT_WIDE_BLOCK 768          // workgroup size of the render kernels with wide path records (volpathmis, volpath with heterogeneous media) on the LDS BVH
 
@@ -51,13 +80,13 @@ struct DeviceScene {
     // wavefront workspace
     uint32_t capacity = 0;
     DPathStreams q[2]{};
-    float4 *dl[2] = { nullptr, nullptr }; float4 *L_buf = nullptr; uint32_t prb_capacity = 0; uint64_t l_buf_lanes = 0;   // PRB: delta_L streams, primal radiance
+    float4 *dl[2] = { nullptr, nullptr }; size_t dl_records[2] = { 0, 0 }; float4 *L_buf = nullptr; size_t l_buf_lanes = 0;   // PRB: delta_L streams, primal radiance
     double *d_grads = nullptr; float *wfilm = nullptr; size_t wfilm_floats = 0; float *grad_image = nullptr; size_t grad_floats = 0;
     DCounters *counters = nullptr;
     DCounters *h_counters = nullptr;       // pinned
     float *film = nullptr; size_t film_floats = 0;
     float *image = nullptr; size_t image_floats = 0;
-    unsigned long long *pass_state[2] = { nullptr, nullptr }; uint64_t pass_state_lanes = 0;   // multi-pass renders: per-lane PCG32 states
+    unsigned long long *pass_state[2] = { nullptr, nullptr }; size_t pass_state_lanes[2] = { 0, 0 };   // multi-pass renders: per-lane PCG32 states
     const unsigned long long *cur_pass_in = nullptr; unsigned long long *cur_pass_out = nullptr;
     uint32_t *pixel_slot = nullptr;         // inverse of pixel_list (pixel -> index in the list), tile-sharded renders
     uint32_t *pixel_list = nullptr; uint32_t pixel_list_rank = 0xffffffffu, pixel_list_count = 0, n_owned_pixels = 0;
@@ -80,6 +109,17 @@ struct DeviceScene {
         if (!p) return;
         for (auto it = allocs.begin(); it != allocs.end(); ++it) if (*it == p) { allocs.erase(it); break; }
         (void) hipFree(p);
+    }
+    // Grows one of the buffers above to `want` elements (`have`: its size counter).  The order is ensure_workspace's: the old buffer is released and
+    // pointer and counter are cleared BEFORE the allocation, the counter is set only after it, so a failed hipMalloc leaves p = nullptr, have = 0
+    // and the next call allocates again instead of writing through a stale size.
+    template <typename T> T *grow(T *&p, size_t &have, size_t want) {
+        if (have >= want) return p;
+        HIP_CHECK(hipStreamSynchronize(stream));
+        release(p); p = nullptr; have = 0;
+        HIP_CHECK(hipMalloc((void **) &p, std::max<size_t>(want, 1) * sizeof(T))); track(p);
+        have = want;
+        return p;
     }
     ~DeviceScene() {
         for (void *p : allocs) (void) hipFree(p);
@@ -248,12 +288,96 @@ static void upload_media(DeviceScene *D, const lrt_scene_desc &d) {
     HIP_CHECK(hipGetLastError());
 }
 
+// ------------------------------------------------------------------ the kernel instances
+// Naming an instance's address instantiates it, so the tables below ARE the set of compiled render kernels (tests/golden/kernel_names.txt pins it):
+// device_scene_create raises the LDS limit of their LDS rows, the launches pick from them, and a new instance is a new row here.
+typedef void (*RenderFn)(ScenePtr, LaunchPtr);
+// One k_render<mode, block, lds, ld, compact, ext>.  mode: the kernel selector (an LRT_INTEGRATOR_* value of the API or of device_types.h).
+struct RenderRow { int mode; bool lds, ld, compact, ext; uint32_t block, record_bytes; RenderFn fn; };
+
+// bytes per queued path record of a mode's layout, as lrt_render_stats reports them
+static constexpr uint32_t record_bytes(int mode, bool compact) {
+    return mode == LRT_INTEGRATOR_VOLPATH_CLOSED ? LRT_STATE_BYTES_CLOSED
+         : mode == LRT_INTEGRATOR_BIOVOLPATH || mode == LRT_INTEGRATOR_BIOVOLPATH06 ? (compact ? LRT_STATE_BYTES_BIO - 8 : LRT_STATE_BYTES_BIO)
+         : compact ? LRT_STATE_BYTES_COMPACT
+         : mode == LRT_INTEGRATOR_VOLPATH_HET ? LRT_STATE_BYTES_HET
+         : mode == LRT_INTEGRATOR_VOLPATHMIS || mode == LRT_INTEGRATOR_VOLPATHMIS_PLAIN ? LRT_STATE_BYTES_MIS : LRT_STATE_BYTES;
+}
+template <int MODE, int BLOCK, bool LDS, bool LD, bool COMPACT = false, bool EXT = false> static void add_row(std::vector<RenderRow> &t) {
+    t.push_back({ MODE, LDS, LD, COMPACT, EXT, BLOCK, record_bytes(MODE, COMPACT), k_render<MODE, BLOCK, LDS, LD, COMPACT, EXT> });
+}
+// a mode's wide-record instances: {LDS BVH (LDS_BLOCK threads), global BVH (LRT_BLOCK)} x {independent, ld} x {plain, EXT}
+template <int MODE, int LDS_BLOCK> static void add_mode(std::vector<RenderRow> &t) {
+    add_row<MODE, LDS_BLOCK, true, false>(t); add_row<MODE, LDS_BLOCK, true, true>(t);
+    add_row<MODE, LDS_BLOCK, true, false, false, true>(t); add_row<MODE, LDS_BLOCK, true, true, false, true>(t);
+    add_row<MODE, LRT_BLOCK, false, false>(t); add_row<MODE, LRT_BLOCK, false, true>(t);
+    add_row<MODE, LRT_BLOCK, false, false, false, true>(t); add_row<MODE, LRT_BLOCK, false, true, false, true>(t);
+}
+// a mode's compact-record instances (80 / 88 bytes, or the 64-byte closed records): LDS BVH, 1024 threads, no EXT; {independent, ld}
+template <int MODE> static void add_compact(std::vector<RenderRow> &t) { add_row<MODE, 1024, true, false, true>(t); add_row<MODE, 1024, true, true, true>(t); }
+
+// every k_render instance, and k_render_prb [adjoint][lds][ld][het] / k_render_prb_grid [lds][ld] (1024 threads on the LDS BVH, else LRT_BLOCK; null: not compiled)
+struct KernelTable { std::vector<RenderRow> render; RenderFn prb[2][2][2][2] = {}, prb_grid[2][2] = {}; };
+template <bool LDS, bool LD> static void add_prb(KernelTable &t) {
+    constexpr int BLOCK = LDS ? 1024 : LRT_BLOCK;
+    t.prb[0][LDS][LD][0] = k_render_prb<false, BLOCK, LDS, LD, false>; t.prb[0][LDS][LD][1] = k_render_prb<false, BLOCK, LDS, LD, true>;
+    t.prb[1][LDS][LD][0] = k_render_prb<true, BLOCK, LDS, LD, false>; t.prb[1][LDS][LD][1] = k_render_prb<true, BLOCK, LDS, LD, true>;
+    t.prb_grid[LDS][LD] = k_render_prb_grid<BLOCK, LDS, LD>;
+}
+static const KernelTable &kernels() {
+    static const KernelTable table = [] {
+        KernelTable t; std::vector<RenderRow> &r = t.render;
+#ifdef LRT_DEV_VOLPATH_ONLY                 // developer build (make dev): only ONE integrator's render kernels are compiled (default: volpath, independent sampler, LDS BVH;
+#ifndef LRT_DEV_INTEGRATOR                  // make dev DEVFLAGS="-DLRT_DEV_INTEGRATOR=LRT_INTEGRATOR_BIOVOLPATH -DLRT_DEV_LD=true" for another) and no PRB kernel
+#define LRT_DEV_INTEGRATOR LRT_INTEGRATOR_VOLPATH
+#endif
+#ifndef LRT_DEV_LD
+#define LRT_DEV_LD false
+#endif
+#ifndef LRT_DEV_BLOCK
+#define LRT_DEV_BLOCK 1024
+#endif
+        // the 64-byte-record instance stands in for "the C3 kernel" of a volpath developer build (any other integrator: its compact instance again)
+#define LRT_DEV_CLOSED (LRT_DEV_INTEGRATOR == LRT_INTEGRATOR_VOLPATH ? LRT_INTEGRATOR_VOLPATH_CLOSED : LRT_DEV_INTEGRATOR)
+        add_row<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD>(r); add_row<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD, true>(r);
+        add_row<LRT_DEV_CLOSED, LRT_DEV_BLOCK, true, LRT_DEV_LD, true>(r);
+#else
+        add_mode<LRT_INTEGRATOR_PATH, 1024>(r); add_mode<LRT_INTEGRATOR_VOLPATH, 1024>(r); add_mode<LRT_INTEGRATOR_BIOVOLPATH, 1024>(r); add_mode<LRT_INTEGRATOR_BIOVOLPATH06, 1024>(r);
+        // (the wide-record integrators run 768-thread workgroups on the LDS BVH: 3 waves per SIMD, 168 VGPRs instead of 128 + 200 - 430 B of scratch per lane;
+        //  measured on the f4 bench configs: volpathmis +58 %, volpath with heterogeneous media +9 %; 512 threads: +54 % / -18 %)
+        add_mode<LRT_INTEGRATOR_VOLPATH_HET, LRT_WIDE_BLOCK>(r); add_mode<LRT_INTEGRATOR_VOLPATHMIS, LRT_WIDE_BLOCK>(r); add_mode<LRT_INTEGRATOR_VOLPATHMIS_PLAIN, LRT_WIDE_BLOCK>(r);
+        add_compact<LRT_INTEGRATOR_PATH>(r); add_compact<LRT_INTEGRATOR_VOLPATH>(r); add_compact<LRT_INTEGRATOR_BIOVOLPATH>(r); add_compact<LRT_INTEGRATOR_BIOVOLPATH06>(r);
+        add_compact<LRT_INTEGRATOR_VOLPATH_CLOSED>(r);
+        add_prb<false, false>(t); add_prb<false, true>(t); add_prb<true, false>(t); add_prb<true, true>(t);
+#endif
+        return t;
+    }();
+    return table;
+}
+
+typedef void (*AovFn)(ScenePtr, LaunchPtr, AovSpecPtr);
+static AovFn aov_kernel(bool lds, bool ld, bool ext) {                  // k_aov<LDS, LD, EXT>: 1024 threads on the LDS BVH, else LRT_BLOCK
+    static const AovFn t[2][2][2] = { { { k_aov<false, false, false>, k_aov<false, false, true> }, { k_aov<false, true, false>, k_aov<false, true, true> } },
+                                      { { k_aov<true, false, false>, k_aov<true, false, true> }, { k_aov<true, true, false>, k_aov<true, true, true> } } };
+    return t[lds][ld][ext];
+}
+typedef decltype(&k_trace<false, false>) TraceFn;
+typedef decltype(&k_trace_lds<false, false>) TraceLdsFn;
+static TraceFn trace_kernel(bool any_hit, bool ext) {                   // k_trace<ANY_HIT, EXT>: BVH in global memory
+    static const TraceFn t[2][2] = { { k_trace<false, false>, k_trace<false, true> }, { k_trace<true, false>, k_trace<true, true> } };
+    return t[any_hit][ext];
+}
+static TraceLdsFn trace_lds_kernel(bool any_hit, bool ext) {            // k_trace_lds<ANY_HIT, EXT>: the render kernels' tracer, BVH image in LDS
+    static const TraceLdsFn t[2][2] = { { k_trace_lds<false, false>, k_trace_lds<false, true> }, { k_trace_lds<true, false>, k_trace_lds<true, true> } };
+    return t[any_hit][ext];
+}
+static RenderFn moment_splat_kernel(bool wide, bool alpha) {            // k_moment_splat<WIDE, ALPHA> for a reconstruction filter and a film
+    static const RenderFn t[2][2] = { { k_moment_splat<false, false>, k_moment_splat<false, true> }, { k_moment_splat<true, false>, k_moment_splat<true, true> } };
+    return t[wide][alpha];
+}
+
 DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-        throw std::runtime_error("no HIP device available: the hip_ad_rgb back-end has no CPU fallback");
-    if (device < 0 || device >= count) throw std::runtime_error("invalid HIP device ordinal " + std::to_string(device));
-    HIP_CHECK(hipSetDevice(device));
+    select_device(device);
     std::unique_ptr<DeviceScene> D(new DeviceScene());
     D->device = device;
     HIP_CHECK(hipStreamCreateWithFlags(&D->stream, hipStreamNonBlocking));
@@ -348,51 +472,14 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
             D->lds.blob = (const uint4 *) D->track(dev_upload(blob.data(), blob.size(), st));
             D->lds.blob_bytes = (uint32_t) blob.size(); D->lds.nodes_off = 0; D->lds.verts_off = (uint32_t) nodes_b; D->lds.tris_off = (uint32_t) (nodes_b + verts_b);
             D->lds.stack_off = (uint32_t) blob.size(); D->lds.total_bytes = (uint32_t) total;
-            #define LRT_SMEM(K) HIP_CHECK(hipFuncSetAttribute((const void *) K, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_limit))
-#ifdef LRT_DEV_VOLPATH_ONLY                 // developer build (make dev): only ONE render kernel is compiled (default: volpath, independent sampler, LDS BVH;
-#ifndef LRT_DEV_INTEGRATOR                  // make dev DEVFLAGS="-DLRT_DEV_INTEGRATOR=LRT_INTEGRATOR_BIOVOLPATH -DLRT_DEV_LD=true" for another)
-#define LRT_DEV_INTEGRATOR LRT_INTEGRATOR_VOLPATH
-#endif
-#ifndef LRT_DEV_LD
-#define LRT_DEV_LD false
-#endif
-#ifndef LRT_DEV_BLOCK
-#define LRT_DEV_BLOCK 1024
-#endif
-            // the 64-byte-record instance stands in for "the C3 kernel" of a volpath developer build (any other integrator: its compact instance again)
-#define LRT_DEV_CLOSED (LRT_DEV_INTEGRATOR == LRT_INTEGRATOR_VOLPATH ? LRT_INTEGRATOR_VOLPATH_CLOSED : LRT_DEV_INTEGRATOR)
-            LRT_SMEM((k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD>)); LRT_SMEM((k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD, true>)); LRT_SMEM((k_render<LRT_DEV_CLOSED, LRT_DEV_BLOCK, true, LRT_DEV_LD, true>)); LRT_SMEM((k_trace_lds<true>)); LRT_SMEM((k_trace_lds<false>)); LRT_SMEM((k_aov<true, false>)); LRT_SMEM((k_aov<true, true>));
-#else
-            LRT_SMEM((k_render<LRT_INTEGRATOR_PATH, 1024, true, false>)); LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH, 1024, true, false>));
-            LRT_SMEM((k_render<LRT_INTEGRATOR_PATH, 1024, true, true>)); LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH, 1024, true, true>));
-            LRT_SMEM((k_render<LRT_INTEGRATOR_BIOVOLPATH, 1024, true, false>)); LRT_SMEM((k_render<LRT_INTEGRATOR_BIOVOLPATH, 1024, true, true>));
-            LRT_SMEM((k_render<LRT_INTEGRATOR_BIOVOLPATH06, 1024, true, false>)); LRT_SMEM((k_render<LRT_INTEGRATOR_BIOVOLPATH06, 1024, true, true>));
-            LRT_SMEM((k_render<LRT_INTEGRATOR_PATH, 1024, true, false, true>)); LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH, 1024, true, false, true>));       // (compact records)
-            LRT_SMEM((k_render<LRT_INTEGRATOR_PATH, 1024, true, true, true>)); LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH, 1024, true, true, true>));
-            LRT_SMEM((k_render<LRT_INTEGRATOR_BIOVOLPATH, 1024, true, false, true>)); LRT_SMEM((k_render<LRT_INTEGRATOR_BIOVOLPATH, 1024, true, true, true>));
-            LRT_SMEM((k_render<LRT_INTEGRATOR_BIOVOLPATH06, 1024, true, false, true>)); LRT_SMEM((k_render<LRT_INTEGRATOR_BIOVOLPATH06, 1024, true, true, true>));
-            LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH_CLOSED, 1024, true, false, true>)); LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH_CLOSED, 1024, true, true, true>));   // (64-byte records)
-            // (the wide-record integrators run 768-thread workgroups: 3 waves per SIMD, 168 VGPRs instead of 128 + 200 - 430 B of scratch per lane;
-            //  measured on the f4 bench configs: volpathmis +58 %, volpath with heterogeneous media +9 %; 512 threads: +54 % / -18 %)
-            LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH_HET, LRT_WIDE_BLOCK, true, false>)); LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATH_HET, LRT_WIDE_BLOCK, true, true>));
-            LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATHMIS, LRT_WIDE_BLOCK, true, false>)); LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATHMIS, LRT_WIDE_BLOCK, true, true>));
-            LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATHMIS_PLAIN, LRT_WIDE_BLOCK, true, false>)); LRT_SMEM((k_render<LRT_INTEGRATOR_VOLPATHMIS_PLAIN, LRT_WIDE_BLOCK, true, true>));
-            LRT_SMEM((k_render_prb<false, 1024, true, false>)); LRT_SMEM((k_render_prb<true, 1024, true, false>));
-            LRT_SMEM((k_render_prb<false, 1024, true, true>)); LRT_SMEM((k_render_prb<true, 1024, true, true>));
-            LRT_SMEM((k_render_prb<false, 1024, true, false, true>)); LRT_SMEM((k_render_prb<true, 1024, true, false, true>));
-            LRT_SMEM((k_render_prb<false, 1024, true, true, true>)); LRT_SMEM((k_render_prb<true, 1024, true, true, true>));
-            LRT_SMEM((k_render_prb_grid<1024, true, false>)); LRT_SMEM((k_render_prb_grid<1024, true, true>));
-            LRT_SMEM((k_trace_lds<true>)); LRT_SMEM((k_trace_lds<false>)); LRT_SMEM((k_aov<true, false>)); LRT_SMEM((k_aov<true, true>));
-            if (D->ext) {                              // spheres / point emitters / mesh emitters: the EXT instances (kernels.h)
-#define LRT_SMEM_EXT(I, BS) LRT_SMEM((k_render<I, BS, true, false, false, true>)); LRT_SMEM((k_render<I, BS, true, true, false, true>))
-                LRT_SMEM_EXT(LRT_INTEGRATOR_PATH, 1024); LRT_SMEM_EXT(LRT_INTEGRATOR_VOLPATH, 1024); LRT_SMEM_EXT(LRT_INTEGRATOR_BIOVOLPATH, 1024);
-                LRT_SMEM_EXT(LRT_INTEGRATOR_BIOVOLPATH06, 1024); LRT_SMEM_EXT(LRT_INTEGRATOR_VOLPATH_HET, LRT_WIDE_BLOCK);
-                LRT_SMEM_EXT(LRT_INTEGRATOR_VOLPATHMIS, LRT_WIDE_BLOCK); LRT_SMEM_EXT(LRT_INTEGRATOR_VOLPATHMIS_PLAIN, LRT_WIDE_BLOCK);
-#undef LRT_SMEM_EXT
-                LRT_SMEM((k_trace_lds<true, true>)); LRT_SMEM((k_trace_lds<false, true>)); LRT_SMEM((k_aov<true, false, true>)); LRT_SMEM((k_aov<true, true, true>));
+            auto raise_lds = [&](const void *k) { if (k) HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_limit)); };
+            const KernelTable &K = kernels();
+            for (const RenderRow &r : K.render) if (r.lds && (!r.ext || D->ext)) raise_lds((const void *) r.fn);     // (the EXT instances: scenes with spheres / point emitters / mesh emitters only)
+            for (const auto &adjoint : K.prb) for (const auto &ld : adjoint[1]) for (RenderFn fn : ld) raise_lds((const void *) fn);
+            for (RenderFn fn : K.prb_grid[1]) raise_lds((const void *) fn);
+            for (int i = 0; i < 2; ++i) for (int ext = 0; ext <= (D->ext ? 1 : 0); ++ext) {            // (i: k_aov's LD, k_trace_lds's ANY_HIT)
+                raise_lds((const void *) aov_kernel(true, i, ext)); raise_lds((const void *) trace_lds_kernel(i, ext));
             }
-#endif
-            #undef LRT_SMEM
             D->use_lds = true;
         }
     }
@@ -692,12 +779,8 @@ static void ensure_halo_list(DeviceScene *D, const ResolvedOpts &O, uint32_t hal
 }
 
 static void ensure_prb_workspace(DeviceScene *D, uint32_t records, uint64_t l_buf_lanes) {
-    if (D->prb_capacity < records) {
-        HIP_CHECK(hipStreamSynchronize(D->stream));
-        for (int k = 0; k < 2; ++k) { D->release(D->dl[k]); HIP_CHECK(hipMalloc((void **) &D->dl[k], (size_t) records * 16)); D->track(D->dl[k]); }
-        D->prb_capacity = records;
-    }
-    if (D->l_buf_lanes < l_buf_lanes) { HIP_CHECK(hipStreamSynchronize(D->stream)); D->release(D->L_buf); HIP_CHECK(hipMalloc((void **) &D->L_buf, (size_t) l_buf_lanes * 16)); D->track(D->L_buf); D->l_buf_lanes = l_buf_lanes; }
+    for (int k = 0; k < 2; ++k) D->grow(D->dl[k], D->dl_records[k], records);
+    D->grow(D->L_buf, D->l_buf_lanes, l_buf_lanes);
     if (!D->d_grads) { HIP_CHECK(hipMalloc((void **) &D->d_grads, 7 * sizeof(double))); D->track(D->d_grads); }
 }
 
@@ -746,7 +829,7 @@ static void finish_stats(DeviceScene *D, LaunchLog &log, hipEvent_t e_begin, hip
 
 // Geometry of the persistent kernels: one 1024-thread workgroup per CU when the BVH lives in LDS, else four 256-thread
 // ones; P = paths in flight per workgroup (multiple of 64), queues of 2P records per workgroup.
-struct PoolGeometry { uint32_t n_wg, P, block; size_t smem; };
+struct PoolGeometry { uint32_t n_wg, P; size_t smem; };
 static PoolGeometry pool_geometry(DeviceScene *D, uint64_t n_lanes) {
     PoolGeometry g;
     g.n_wg = D->use_lds ? (uint32_t) D->n_cus : 4u * (uint32_t) D->n_cus;
@@ -758,7 +841,6 @@ static PoolGeometry pool_geometry(DeviceScene *D, uint64_t n_lanes) {
         const uint64_t per_wg = (n_lanes + g.n_wg - 1) / g.n_wg, want = (per_wg / 48 + 63) / 64 * 64;
         if (want < g.P) g.P = (uint32_t) std::max<uint64_t>(want, std::min<uint64_t>(g.P, 8192));
     }
-    g.block = D->use_lds ? 1024u : (uint32_t) LRT_BLOCK;
     g.smem = D->use_lds ? D->lds.total_bytes : (size_t) LRT_STACK * LRT_BLOCK * sizeof(int);
     return g;
 }
@@ -781,21 +863,11 @@ static void launch_prb(DeviceScene *D, const DRenderParams &rp, const PoolGeomet
     a.pixel_list = pixel_list; a.lane_begin = lane_begin; a.n = rp.n_lanes; a.L_buf = L_buf; a.grad_image = grad_image; a.wfilm = D->wfilm; a.grads = grads;
     a.film = film; a.sample_out = sample_out; a.sample_base = lane_begin; a.dgrid = dgrid;
     const LaunchPtr lp = push_launch(D, a);             // (compact records, as run_wavefront queues them, were measured on C5: 96-byte records, 5 % SLOWER; the PRB kernels keep the wide layout)
-#ifdef LRT_DEV_VOLPATH_ONLY
-    (void) lp; throw std::runtime_error("developer build: volpath only");
-#else
-    #define LRT_LAUNCH_PRB(BS, LDSB, LD) do { if (D->prb_null) k_render_prb<ADJOINT, BS, LDSB, LD, true><<<g.n_wg, BS, g.smem, st>>>((ScenePtr) D->d_sc, lp); \
-                                              else k_render_prb<ADJOINT, BS, LDSB, LD, false><<<g.n_wg, BS, g.smem, st>>>((ScenePtr) D->d_sc, lp); } while (0)
-    #define LRT_LAUNCH_PRB_GRID(BS, LDSB, LD) k_render_prb_grid<BS, LDSB, LD><<<g.n_wg, BS, g.smem, st>>>((ScenePtr) D->d_sc, lp)
-    if (ADJOINT && dgrid) {                             // lrt_render_backward_grid (the caller has checked that the graded medium is heterogeneous: prb_null)
-        if (D->use_lds) { if (rp.ld_count) LRT_LAUNCH_PRB_GRID(1024, true, true); else LRT_LAUNCH_PRB_GRID(1024, true, false); }
-        else { if (rp.ld_count) LRT_LAUNCH_PRB_GRID(LRT_BLOCK, false, true); else LRT_LAUNCH_PRB_GRID(LRT_BLOCK, false, false); }
-    }
-    else if (D->use_lds) { if (rp.ld_count) LRT_LAUNCH_PRB(1024, true, true); else LRT_LAUNCH_PRB(1024, true, false); }
-    else { if (rp.ld_count) LRT_LAUNCH_PRB(LRT_BLOCK, false, true); else LRT_LAUNCH_PRB(LRT_BLOCK, false, false); }
-    #undef LRT_LAUNCH_PRB_GRID
-    #undef LRT_LAUNCH_PRB
-#endif
+    // ADJOINT && dgrid: lrt_render_backward_grid (the caller has checked that the graded medium is heterogeneous: prb_null)
+    const bool ld = rp.ld_count != 0;
+    const RenderFn fn = (ADJOINT && dgrid) ? kernels().prb_grid[D->use_lds][ld] : kernels().prb[ADJOINT][D->use_lds][ld][D->prb_null];
+    if (!fn) throw std::runtime_error("developer build: volpath only");
+    fn<<<g.n_wg, D->use_lds ? 1024 : LRT_BLOCK, g.smem, st>>>((ScenePtr) D->d_sc, lp);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -860,12 +932,18 @@ static bool closed_records(const DeviceScene *D, const lrt_scene_desc &d) {
     }
     return true;
 }
-// bytes per queued path record of the wide (not compact) layouts, as lrt_render_stats reports them
-static uint32_t wide_record_bytes(const DeviceScene *D, int integrator) {
-    if (integrator == LRT_INTEGRATOR_VOLPATHMIS) return LRT_STATE_BYTES_MIS;
-    if (integrator == LRT_INTEGRATOR_BIOVOLPATH || integrator == LRT_INTEGRATOR_BIOVOLPATH06) return LRT_STATE_BYTES_BIO;
-    if (integrator == LRT_INTEGRATOR_VOLPATH && D->has_het) return LRT_STATE_BYTES_HET;
-    return LRT_STATE_BYTES;
+
+// The render-kernel instance of a forward render: the row of kernels().render for an integrator on this scene.  compact / closed: run_wavefront's predicates.
+static const RenderRow &select_render_kernel(int integrator, bool has_het, bool spectral_mis, bool lds, bool ld, bool ext, bool compact, bool closed) {
+    int mode;
+    switch (integrator) {
+        case LRT_INTEGRATOR_PATH: case LRT_INTEGRATOR_BIOVOLPATH: case LRT_INTEGRATOR_BIOVOLPATH06: mode = integrator; break;
+        case LRT_INTEGRATOR_VOLPATHMIS: mode = spectral_mis ? LRT_INTEGRATOR_VOLPATHMIS : LRT_INTEGRATOR_VOLPATHMIS_PLAIN; break;
+        default: mode = closed ? LRT_INTEGRATOR_VOLPATH_CLOSED : (has_het ? LRT_INTEGRATOR_VOLPATH_HET : LRT_INTEGRATOR_VOLPATH);      // volpath
+    }
+    for (const RenderRow &r : kernels().render) if (r.mode == mode && r.lds == lds && r.ld == ld && r.compact == compact && r.ext == ext) return r;
+    throw std::runtime_error("no render-kernel instance for mode " + std::to_string(mode) + (lds ? ", LDS BVH" : ", global BVH") + (ld ? ", ld sampler" : ", independent sampler") +
+                             (compact ? ", compact records" : ", wide records") + (ext ? ", EXT" : ""));
 }
 
 // One persistent launch per render (k_render / k_render_prb): per-workgroup path pools, in-kernel regeneration; see
@@ -879,7 +957,6 @@ static void run_wavefront(DeviceScene *D, const lrt_scene_desc &d, const Resolve
     const bool prb = O.integrator == LRT_INTEGRATOR_PRBVOLPATH;
     check_integrator_media(D, O.integrator);
     PoolGeometry g = pool_geometry(D, n_lanes);
-    if (prb && D->use_lds) g.block = 1024;
     const uint32_t records = (uint32_t) std::min<uint64_t>((uint64_t) g.n_wg * 2u * g.P, 0xffffffffull);
     ensure_workspace(D, records);
     if (prb) ensure_prb_workspace(D, records, 0);
@@ -902,39 +979,14 @@ static void run_wavefront(DeviceScene *D, const lrt_scene_desc &d, const Resolve
         // lrt_param_set can change sigma_t after the scene was loaded
         const bool closed = compact && O.integrator == LRT_INTEGRATOR_VOLPATH && closed_records(D, d) && !getenv("LRT_NO_CLOSED_RECORDS");
         a.rp.compact = compact ? 1u : 0u;
-        stats.record_bytes = closed ? LRT_STATE_BYTES_CLOSED : (compact ? (O.integrator == LRT_INTEGRATOR_BIOVOLPATH || O.integrator == LRT_INTEGRATOR_BIOVOLPATH06 ? LRT_STATE_BYTES_BIO - 8 : LRT_STATE_BYTES_COMPACT) : wide_record_bytes(D, O.integrator));
-        const LaunchPtr lp = push_launch(D, a);
 #ifdef LRT_DEV_VOLPATH_ONLY
         if (D->ext) throw std::runtime_error("developer build: no EXT instances (spheres / point emitters)");
         if (!(D->use_lds && (O.integrator == LRT_DEV_INTEGRATOR || (LRT_DEV_INTEGRATOR == LRT_INTEGRATOR_VOLPATH_HET && D->has_het)) && (rp.ld_count != 0) == LRT_DEV_LD)) throw std::runtime_error("developer build: one integrator / sampler / LDS BVH only");
-        if (closed) k_render<LRT_DEV_CLOSED, LRT_DEV_BLOCK, true, LRT_DEV_LD, true><<<g.n_wg, LRT_DEV_BLOCK, g.smem, st>>>((ScenePtr) D->d_sc, lp);
-        else if (compact) k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD, true><<<g.n_wg, LRT_DEV_BLOCK, g.smem, st>>>((ScenePtr) D->d_sc, lp);
-        else k_render<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD><<<g.n_wg, LRT_DEV_BLOCK, g.smem, st>>>((ScenePtr) D->d_sc, lp);
-        #define LRT_LAUNCH_I(BS, LDSB)
-        #define LRT_LAUNCH(I, BS, LDSB)
-#else
-        #define LRT_LAUNCH(I, BS, LDSB) do { if (D->ext) { if (rp.ld_count) k_render<I, BS, LDSB, true, false, true><<<g.n_wg, BS, g.smem, st>>>((ScenePtr) D->d_sc, lp); \
-                                                               else k_render<I, BS, LDSB, false, false, true><<<g.n_wg, BS, g.smem, st>>>((ScenePtr) D->d_sc, lp); } \
-                                             else if (rp.ld_count) k_render<I, BS, LDSB, true><<<g.n_wg, BS, g.smem, st>>>((ScenePtr) D->d_sc, lp); \
-                                             else k_render<I, BS, LDSB, false><<<g.n_wg, BS, g.smem, st>>>((ScenePtr) D->d_sc, lp); } while (0)
-        #define LRT_LAUNCH_COMPACT(I) do { if (rp.ld_count) k_render<I, 1024, true, true, true><<<g.n_wg, 1024, g.smem, st>>>((ScenePtr) D->d_sc, lp); \
-                                           else k_render<I, 1024, true, false, true><<<g.n_wg, 1024, g.smem, st>>>((ScenePtr) D->d_sc, lp); } while (0)
-        #define LRT_LAUNCH_I(BS, LDSB) do { switch (O.integrator) { \
-            case LRT_INTEGRATOR_PATH: LRT_LAUNCH(LRT_INTEGRATOR_PATH, BS, LDSB); break; \
-            case LRT_INTEGRATOR_BIOVOLPATH: LRT_LAUNCH(LRT_INTEGRATOR_BIOVOLPATH, BS, LDSB); break; \
-            case LRT_INTEGRATOR_BIOVOLPATH06: LRT_LAUNCH(LRT_INTEGRATOR_BIOVOLPATH06, BS, LDSB); break; \
-            case LRT_INTEGRATOR_VOLPATHMIS: if (d.use_spectral_mis) LRT_LAUNCH(LRT_INTEGRATOR_VOLPATHMIS, (LDSB ? LRT_WIDE_BLOCK : BS), LDSB); else LRT_LAUNCH(LRT_INTEGRATOR_VOLPATHMIS_PLAIN, (LDSB ? LRT_WIDE_BLOCK : BS), LDSB); break; \
-            default: if (D->has_het) LRT_LAUNCH(LRT_INTEGRATOR_VOLPATH_HET, (LDSB ? LRT_WIDE_BLOCK : BS), LDSB); else LRT_LAUNCH(LRT_INTEGRATOR_VOLPATH, BS, LDSB); } } while (0)
-        if (compact) switch (O.integrator) {
-            case LRT_INTEGRATOR_PATH: LRT_LAUNCH_COMPACT(LRT_INTEGRATOR_PATH); break;
-            case LRT_INTEGRATOR_BIOVOLPATH: LRT_LAUNCH_COMPACT(LRT_INTEGRATOR_BIOVOLPATH); break;
-            case LRT_INTEGRATOR_BIOVOLPATH06: LRT_LAUNCH_COMPACT(LRT_INTEGRATOR_BIOVOLPATH06); break;
-            default: if (closed) LRT_LAUNCH_COMPACT(LRT_INTEGRATOR_VOLPATH_CLOSED); else LRT_LAUNCH_COMPACT(LRT_INTEGRATOR_VOLPATH); }
-        else if (D->use_lds) LRT_LAUNCH_I(1024, true); else LRT_LAUNCH_I(LRT_BLOCK, false);
-        #undef LRT_LAUNCH_COMPACT
 #endif
-        #undef LRT_LAUNCH_I
-        #undef LRT_LAUNCH
+        const RenderRow &row = select_render_kernel(O.integrator, D->has_het, d.use_spectral_mis != 0, D->use_lds, rp.ld_count != 0, D->ext, compact, closed);
+        stats.record_bytes = row.record_bytes;
+        const LaunchPtr lp = push_launch(D, a);
+        row.fn<<<g.n_wg, row.block, g.smem, st>>>((ScenePtr) D->d_sc, lp);
         HIP_CHECK(hipGetLastError());
     }
     HIP_CHECK(hipEventRecord(b, st));
@@ -961,13 +1013,20 @@ void device_render(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opt
     render_passes(D, d, opts, film_raw, image, stats, nullptr);
 }
 
-// the instance of k_moment_splat<WIDE, ALPHA> for a reconstruction filter and a film
-static void launch_moment_splat(DeviceScene *D, bool wide, bool alpha, uint32_t grid, LaunchPtr lp) {
-    const ScenePtr sc = (ScenePtr) D->d_sc;
-    if (wide && alpha) k_moment_splat<true, true><<<grid, LRT_BLOCK, 0, D->stream>>>(sc, lp);
-    else if (wide) k_moment_splat<true, false><<<grid, LRT_BLOCK, 0, D->stream>>>(sc, lp);
-    else if (alpha) k_moment_splat<false, true><<<grid, LRT_BLOCK, 0, D->stream>>>(sc, lp);
-    else k_moment_splat<false, false><<<grid, LRT_BLOCK, 0, D->stream>>>(sc, lp);
+// The tail of a render: develops `film` (device) into the image and downloads what the caller asked for.  image / film_raw are host buffers
+// (the image is developed into D->image first) unless on_device; film_raw == nullptr or == film: no film download.
+static void develop_and_download(DeviceScene *D, const float *film, float *film_raw, float *image, size_t film_floats, size_t image_floats, bool on_device, bool moment = false) {
+    const DFilm &F = D->sc.film; const size_t np = (size_t) F.width * F.height;
+    if (image) {
+        float *img = on_device ? image : D->grow(D->image, D->image_floats, image_floats);
+        if (!moment) k_develop<<<(uint32_t) ((np + 255) / 256), 256, 0, D->stream>>>(F, film, img, (uint32_t) np);
+        else if (F.has_alpha) k_moment_develop<true><<<(uint32_t) ((np + 255) / 256), 256, 0, D->stream>>>(film, img, (uint32_t) np);
+        else k_moment_develop<false><<<(uint32_t) ((np + 255) / 256), 256, 0, D->stream>>>(film, img, (uint32_t) np);
+        if (!on_device) HIP_CHECK(hipMemcpyAsync(image, img, image_floats * 4, hipMemcpyDeviceToHost, D->stream));
+    }
+    if (film_raw && !on_device) HIP_CHECK(hipMemcpyAsync(film_raw, film, film_floats * 4, hipMemcpyDeviceToHost, D->stream));
+    HIP_CHECK(hipStreamSynchronize(D->stream));
+    HIP_CHECK(hipGetLastError());
 }
 
 static void render_passes(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, float *film_raw, float *image, lrt_render_stats &stats,
@@ -980,17 +1039,11 @@ static void render_passes(DeviceScene *D, const lrt_scene_desc &d, const lrt_ren
     size_t np = (size_t) F.width * F.height, film_floats = np * film_channels, image_floats = np * image_channels;
     ensure_pixel_list(D, O);
     const uint64_t n_lanes = (uint64_t) D->n_owned_pixels * O.spp;            // this rank's lanes of ONE pass
-    float *film = nullptr;
-    if (on_device && film_raw) film = film_raw;
-    else { if (D->film_floats < film_floats) { D->release(D->film); D->film = nullptr; HIP_CHECK(hipMalloc((void **) &D->film, film_floats * 4)); D->track(D->film); D->film_floats = film_floats; } film = D->film; }
+    float *film = (on_device && film_raw) ? film_raw : D->grow(D->film, D->film_floats, film_floats);
     HIP_CHECK(hipMemsetAsync(film, 0, film_floats * 4, D->stream));
     const uint32_t *pixel_list = O.tile_count > 1 ? D->pixel_list : nullptr;
     const bool carry = O.n_passes > 1 && d.sampler_type != LRT_SAMPLER_LD;     // the independent sampler's streams run on from pass to pass
-    if (carry && D->pass_state_lanes < n_lanes) {
-        HIP_CHECK(hipStreamSynchronize(D->stream));
-        for (int k = 0; k < 2; ++k) { D->release(D->pass_state[k]); HIP_CHECK(hipMalloc((void **) &D->pass_state[k], std::max<uint64_t>(n_lanes, 1) * 8)); D->track(D->pass_state[k]); }
-        D->pass_state_lanes = n_lanes;
-    }
+    if (carry) for (int k = 0; k < 2; ++k) D->grow(D->pass_state[k], D->pass_state_lanes[k], n_lanes);
     const bool lane_splat = moment || (F.rfilter != LRT_RFILTER_BOX && (O.n_passes > 1 || !getenv("LRT_NO_LANE_SPLAT")));
     lrt_render_stats total{};
     for (uint32_t pass = 0; pass < O.n_passes; ++pass) {                       // integrator.cpp:343-353
@@ -1000,9 +1053,7 @@ static void render_passes(DeviceScene *D, const lrt_scene_desc &d, const lrt_ren
         if (!lane_splat) {
             lrt_render_stats st1{};
             run_wavefront(D, d, O, 0, n_lanes, pixel_list, film, nullptr, st1);
-            total.n_samples += st1.n_samples; total.n_iter += st1.n_iter; total.n_shadow += st1.n_shadow; total.n_launches += st1.n_launches;
-            total.n_records += st1.n_records; total.kernel_ms += st1.kernel_ms; total.total_ms += st1.total_ms;
-            total.record_bytes = st1.record_bytes; total.n_closed_guard += st1.n_closed_guard;
+            add_stats(total, st1);
             if (after_pass) after_pass(O);
             continue;
         }
@@ -1019,28 +1070,16 @@ static void render_passes(DeviceScene *D, const lrt_scene_desc &d, const lrt_ren
             const uint32_t grid = (uint32_t) ((n + LRT_BLOCK - 1) / LRT_BLOCK);
             const LaunchPtr lp = push_launch(D, a);
             if (!moment) k_splat_lanes<false><<<grid, LRT_BLOCK, 0, D->stream>>>((ScenePtr) D->d_sc, lp);
-            else launch_moment_splat(D, F.rfilter != LRT_RFILTER_BOX, F.has_alpha != 0, grid, lp);
+            else moment_splat_kernel(F.rfilter != LRT_RFILTER_BOX, F.has_alpha != 0)<<<grid, LRT_BLOCK, 0, D->stream>>>((ScenePtr) D->d_sc, lp);
             HIP_CHECK(hipGetLastError());
-            total.n_samples += st1.n_samples; total.n_iter += st1.n_iter; total.n_shadow += st1.n_shadow; total.n_launches += st1.n_launches;
-            total.n_records += st1.n_records; total.kernel_ms += st1.kernel_ms; total.total_ms += st1.total_ms;
-            total.record_bytes = st1.record_bytes; total.n_closed_guard += st1.n_closed_guard;
+            add_stats(total, st1);
         }
         if (after_pass) after_pass(O);
     }
     D->cur_pass_in = nullptr; D->cur_pass_out = nullptr;
     total.lds_resident = D->use_lds ? 1 : 0;
     stats = total;
-    if (image) {
-        float *img = image;
-        if (!on_device) { if (D->image_floats < image_floats) { D->release(D->image); D->image = nullptr; HIP_CHECK(hipMalloc((void **) &D->image, image_floats * 4)); D->track(D->image); D->image_floats = image_floats; } img = D->image; }
-        if (!moment) k_develop<<<(uint32_t) ((np + 255) / 256), 256, 0, D->stream>>>(F, film, img, (uint32_t) np);
-        else if (F.has_alpha) k_moment_develop<true><<<(uint32_t) ((np + 255) / 256), 256, 0, D->stream>>>(film, img, (uint32_t) np);
-        else k_moment_develop<false><<<(uint32_t) ((np + 255) / 256), 256, 0, D->stream>>>(film, img, (uint32_t) np);
-        if (!on_device) HIP_CHECK(hipMemcpyAsync(image, img, image_floats * 4, hipMemcpyDeviceToHost, D->stream));
-    }
-    if (film_raw && !on_device) HIP_CHECK(hipMemcpyAsync(film_raw, film, film_floats * 4, hipMemcpyDeviceToHost, D->stream));
-    HIP_CHECK(hipStreamSynchronize(D->stream));
-    HIP_CHECK(hipGetLastError());
+    develop_and_download(D, film, film_raw, image, film_floats, image_floats, on_device, moment);
 }
 
 // ------------------------------------------------------------------ the moment integrator (kernels_moment.h)
@@ -1054,58 +1093,40 @@ void device_render_moment_samples(DeviceScene *D, const lrt_scene_desc &d, const
     ResolvedOpts O = resolve(d, opts);
     if (lane_begin + n > 0x100000000ull) throw std::runtime_error("lane range exceeds 2^32");
     if (!n) { stats = lrt_render_stats{}; return; }
-    float *d_buf = nullptr;                          // n float4 of radiance, then n * 6 floats of moments
-    HIP_CHECK(hipMalloc((void **) &d_buf, (size_t) n * (16 + 24)));
-    try {
-        float *d_m = d_buf + (size_t) n * 4;
-        HIP_CHECK(hipMemsetAsync(d_buf, 0, (size_t) n * 16, D->stream));
-        run_wavefront(D, d, O, lane_begin, n, nullptr, nullptr, d_buf, stats);
-        k_moment_lanes<<<(n + 255u) / 256u, 256, 0, D->stream>>>(reinterpret_cast<const float4 *>(d_buf), O.integrator == LRT_INTEGRATOR_PATH ? 1 : 0, n, d_m);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(out, d_m, (size_t) n * 24, hipMemcpyDeviceToHost, D->stream));
-        HIP_CHECK(hipStreamSynchronize(D->stream));
-    } catch (...) { (void) hipFree(d_buf); throw; }
-    HIP_CHECK(hipFree(d_buf));
+    DevTmp buf((size_t) n * 10);                     // n float4 of radiance, then n * 6 floats of moments
+    float *d_buf = buf.p, *d_m = d_buf + (size_t) n * 4;
+    HIP_CHECK(hipMemsetAsync(d_buf, 0, (size_t) n * 16, D->stream));
+    run_wavefront(D, d, O, lane_begin, n, nullptr, nullptr, d_buf, stats);
+    k_moment_lanes<<<(n + 255u) / 256u, 256, 0, D->stream>>>(reinterpret_cast<const float4 *>(d_buf), O.integrator == LRT_INTEGRATOR_PATH ? 1 : 0, n, d_m);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, d_m, (size_t) n * 24, hipMemcpyDeviceToHost, D->stream));
+    HIP_CHECK(hipStreamSynchronize(D->stream));
 }
 
 void device_develop(DeviceScene *D, const float *film_raw, float *image, int on_device) {
     HIP_CHECK(hipSetDevice(D->device));
     const DFilm &F = D->sc.film;
     size_t np = (size_t) F.width * F.height, film_floats = np * F.channels, image_floats = np * (F.has_alpha ? 4 : 3);
-    const float *film = film_raw; float *img = image;
+    const float *film = film_raw;
     if (!on_device) {
-        if (D->film_floats < film_floats) { D->release(D->film); D->film = nullptr; HIP_CHECK(hipMalloc((void **) &D->film, film_floats * 4)); D->track(D->film); D->film_floats = film_floats; }
-        if (D->image_floats < image_floats) { D->release(D->image); D->image = nullptr; HIP_CHECK(hipMalloc((void **) &D->image, image_floats * 4)); D->track(D->image); D->image_floats = image_floats; }
+        film = D->grow(D->film, D->film_floats, film_floats);
         HIP_CHECK(hipMemcpyAsync(D->film, film_raw, film_floats * 4, hipMemcpyHostToDevice, D->stream));
-        film = D->film; img = D->image;
     }
-    k_develop<<<(uint32_t) ((np + 255) / 256), 256, 0, D->stream>>>(F, film, img, (uint32_t) np);
-    if (!on_device) HIP_CHECK(hipMemcpyAsync(image, img, image_floats * 4, hipMemcpyDeviceToHost, D->stream));
-    HIP_CHECK(hipStreamSynchronize(D->stream));
-    HIP_CHECK(hipGetLastError());
+    develop_and_download(D, film, nullptr, image, film_floats, image_floats, on_device != 0);
 }
 
 void device_render_samples(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out, lrt_render_stats &stats) {
     HIP_CHECK(hipSetDevice(D->device));
     ResolvedOpts O = resolve(d, opts);
     if (lane_begin + n > 0x100000000ull) throw std::runtime_error("lane range exceeds 2^32");
-    float *d_out = nullptr;
-    HIP_CHECK(hipMalloc((void **) &d_out, (size_t) std::max<uint32_t>(n, 1) * 16));
-    try {
-        HIP_CHECK(hipMemsetAsync(d_out, 0, (size_t) n * 16, D->stream));
-        run_wavefront(D, d, O, lane_begin, n, nullptr, nullptr, d_out, stats);
-        HIP_CHECK(hipMemcpyAsync(out, d_out, (size_t) n * 16, hipMemcpyDeviceToHost, D->stream));
-        HIP_CHECK(hipStreamSynchronize(D->stream));
-    } catch (...) { (void) hipFree(d_out); throw; }
-    HIP_CHECK(hipFree(d_out));
+    DevTmp d_out((size_t) n * 4);
+    HIP_CHECK(hipMemsetAsync(d_out.p, 0, (size_t) n * 16, D->stream));
+    run_wavefront(D, d, O, lane_begin, n, nullptr, nullptr, d_out.p, stats);
+    HIP_CHECK(hipMemcpyAsync(out, d_out.p, (size_t) n * 16, hipMemcpyDeviceToHost, D->stream));
+    HIP_CHECK(hipStreamSynchronize(D->stream));
 }
 
 // ------------------------------------------------------------------ the aov integrator (kernels_aov.h)
-static float *aov_buffer(DeviceScene *D, float *&buf, size_t &have, size_t floats) {
-    if (have < floats) { D->release(buf); buf = nullptr; HIP_CHECK(hipMalloc((void **) &buf, std::max<size_t>(floats, 1) * 4)); D->track(buf); have = floats; }
-    return buf;
-}
-
 // The AOV table and the shapes' first faces, uploaded (stream-ordered) before each aov render.
 static void upload_aov_spec(DeviceScene *D, const lrt_scene_desc &d, const lrt_aov_desc &aov) {
     if (!D->d_aov_spec) { HIP_CHECK(hipMalloc((void **) &D->d_aov_spec, sizeof(DAovSpec))); D->track(D->d_aov_spec); }
@@ -1137,19 +1158,13 @@ static void launch_aov(DeviceScene *D, const lrt_scene_desc &d, const ResolvedOp
     DLaunch a{}; a.rp = rp; a.li = D->lds; a.lane_begin = lane_begin; a.n = n; a.film = film; a.sample_out = sample_out; a.sample_base = lane_begin;
     const LaunchPtr lp = push_launch(D, a);
     const AovSpecPtr spec = (AovSpecPtr) D->d_aov_spec;
+    const AovFn fn = aov_kernel(D->use_lds, rp.ld_count != 0, D->ext);
     if (D->use_lds) {
         const uint32_t g = (uint32_t) std::min<uint64_t>((uint64_t) D->n_cus, (n + 1023) / 1024);       // one workgroup per CU: the LDS image is copied once
-        if (D->ext) { if (rp.ld_count) k_aov<true, true, true><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, lp, spec);
-                      else k_aov<true, false, true><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, lp, spec); }
-        else if (rp.ld_count) k_aov<true, true><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, lp, spec);
-        else k_aov<true, false><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, lp, spec);
+        fn<<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, lp, spec);
     } else {
         const uint32_t g = (uint32_t) std::min<uint64_t>((uint64_t) D->n_cus * 8u, (n + LRT_BLOCK - 1) / LRT_BLOCK);
-        const size_t smem = (size_t) LRT_STACK * LRT_BLOCK * sizeof(int);
-        if (D->ext) { if (rp.ld_count) k_aov<false, true, true><<<g, LRT_BLOCK, smem, st>>>((ScenePtr) D->d_sc, lp, spec);
-                      else k_aov<false, false, true><<<g, LRT_BLOCK, smem, st>>>((ScenePtr) D->d_sc, lp, spec); }
-        else if (rp.ld_count) k_aov<false, true><<<g, LRT_BLOCK, smem, st>>>((ScenePtr) D->d_sc, lp, spec);
-        else k_aov<false, false><<<g, LRT_BLOCK, smem, st>>>((ScenePtr) D->d_sc, lp, spec);
+        fn<<<g, LRT_BLOCK, (size_t) LRT_STACK * LRT_BLOCK * sizeof(int), st>>>((ScenePtr) D->d_sc, lp, spec);
     }
     HIP_CHECK(hipGetLastError());
 }
@@ -1176,10 +1191,10 @@ void device_render_aov(DeviceScene *D, const lrt_scene_desc &d, const lrt_aov_de
         throw std::runtime_error("lrt_render_aov: a nested prbvolpath renders in one pass; several AOV passes around it are not supported");
     upload_aov_spec(D, d, aov);
     hipStream_t st = D->stream;
-    float *film = (on_device && aov_film_raw) ? aov_film_raw : aov_buffer(D, D->aov_film, D->aov_film_floats, np * C);
+    float *film = (on_device && aov_film_raw) ? aov_film_raw : D->grow(D->aov_film, D->aov_film_floats, np * C);
     HIP_CHECK(hipMemsetAsync(film, 0, np * C * 4, st));
     float *img = nullptr;
-    if (image) img = on_device ? image : aov_buffer(D, D->aov_image, D->aov_image_floats, np * T);
+    if (image) img = on_device ? image : D->grow(D->aov_image, D->aov_image_floats, np * T);
     const uint64_t n_lanes = np * O.spp;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t ev_next = 0;
     auto aov_pass = [&](uint32_t pass, const unsigned long long *in, unsigned long long *out) {
@@ -1197,26 +1212,20 @@ void device_render_aov(DeviceScene *D, const lrt_scene_desc &d, const lrt_aov_de
         const bool hook = carry && k == 0;
         if (!image && !hook) continue;           // nothing of it is asked for
         lrt_scene_desc dk = d; dk.integrator = aov.integrators[k];
-        lrt_render_opts ok{}; if (opts) ok = *opts; else { ok.integrator = -1; ok.max_depth = -2; ok.rr_depth = -1; ok.hide_emitters = -1; }
+        lrt_render_opts ok = opts ? *opts : default_opts();
         ok.output_on_device = 1; ok.tile_rank = 0; ok.tile_count = 1;
-        float *inner = image ? aov_buffer(D, D->aov_inner, D->aov_inner_floats, np * IC) : nullptr;
+        float *inner = image ? D->grow(D->aov_inner, D->aov_inner_floats, np * IC) : nullptr;
         lrt_render_stats sk{};
         std::function<void(const ResolvedOpts &)> after;
         if (hook) after = [&](const ResolvedOpts &Oc) { aov_pass(Oc.pass, D->cur_pass_in, nullptr); };
         render_passes(D, dk, &ok, nullptr, inner, sk, after);
         if (hook) aov_done = true;
         if (image) { k_aov_copy<<<(uint32_t) ((np + 255) / 256), 256, 0, st>>>(inner, IC, img, T, k * IC, (uint32_t) np); HIP_CHECK(hipGetLastError()); }
-        total.n_samples += sk.n_samples; total.n_iter += sk.n_iter; total.n_shadow += sk.n_shadow; total.n_launches += sk.n_launches;
-        total.n_records += sk.n_records; total.kernel_ms += sk.kernel_ms; total.total_ms += sk.total_ms;
-        total.record_bytes = sk.record_bytes; total.n_closed_guard += sk.n_closed_guard;
+        add_stats(total, sk);
     }
     // 2. the AOV pass (Base::render, aov.cpp:382-391)
     if (!aov_done) {
-        if (carry && D->pass_state_lanes < n_lanes) {
-            HIP_CHECK(hipStreamSynchronize(st));
-            for (int k = 0; k < 2; ++k) { D->release(D->pass_state[k]); D->pass_state[k] = nullptr; HIP_CHECK(hipMalloc((void **) &D->pass_state[k], std::max<uint64_t>(n_lanes, 1) * 8)); D->track(D->pass_state[k]); }
-            D->pass_state_lanes = n_lanes;
-        }
+        if (carry) for (int k = 0; k < 2; ++k) D->grow(D->pass_state[k], D->pass_state_lanes[k], n_lanes);
         for (uint32_t pass = 0; pass < O.n_passes; ++pass)
             aov_pass(pass, carry ? D->pass_state[pass & 1] : nullptr, (carry && pass + 1 < O.n_passes) ? D->pass_state[(pass & 1) ^ 1] : nullptr);
     }
@@ -1242,52 +1251,37 @@ void device_render_aov_samples(DeviceScene *D, const lrt_scene_desc &d, const lr
     upload_aov_spec(D, d, aov);
     const size_t floats = (size_t) n * aov.n_aov_channels;
     if (!floats) { stats = lrt_render_stats{}; return; }
-    float *d_out = nullptr;
-    HIP_CHECK(hipMalloc((void **) &d_out, floats * 4));
-    try {
-        HIP_CHECK(hipMemsetAsync(d_out, 0, floats * 4, D->stream));
-        O.pass = 0;
-        launch_aov(D, da, O, lane_begin, n, nullptr, d_out, nullptr, nullptr);
-        HIP_CHECK(hipMemcpyAsync(out, d_out, floats * 4, hipMemcpyDeviceToHost, D->stream));
-        HIP_CHECK(hipStreamSynchronize(D->stream));
-        HIP_CHECK(hipGetLastError());
-    } catch (...) { (void) hipFree(d_out); throw; }
-    HIP_CHECK(hipFree(d_out));
+    DevTmp d_out(floats);
+    HIP_CHECK(hipMemsetAsync(d_out.p, 0, floats * 4, D->stream));
+    O.pass = 0;
+    launch_aov(D, da, O, lane_begin, n, nullptr, d_out.p, nullptr, nullptr);
+    HIP_CHECK(hipMemcpyAsync(out, d_out.p, floats * 4, hipMemcpyDeviceToHost, D->stream));
+    HIP_CHECK(hipStreamSynchronize(D->stream));
+    HIP_CHECK(hipGetLastError());
     stats = lrt_render_stats{}; stats.n_samples = n; stats.lds_resident = D->use_lds ? 1 : 0;
 }
 
 void device_trace(DeviceScene *D, const lrt_rays_soa *rays, const lrt_hits_soa *hits, uint32_t n, int any_hit) {
     HIP_CHECK(hipSetDevice(D->device));
     hipStream_t st = D->stream;
-    std::vector<void *> tmp;
-    auto up = [&](const float *h) { float *p; HIP_CHECK(hipMalloc((void **) &p, (size_t) std::max<uint32_t>(n, 1) * 4)); tmp.push_back(p); HIP_CHECK(hipMemcpyAsync(p, h, (size_t) n * 4, hipMemcpyHostToDevice, st)); return p; };
-    auto mk = [&]() { float *p; HIP_CHECK(hipMalloc((void **) &p, (size_t) std::max<uint32_t>(n, 1) * 4)); tmp.push_back(p); return p; };
-    try {
-        float *ox = up(rays->ox), *oy = up(rays->oy), *oz = up(rays->oz), *dx = up(rays->dx), *dy = up(rays->dy), *dz = up(rays->dz), *tm = up(rays->tmax);
-        float *t = mk(), *u = mk(), *v = mk(); uint32_t *prim = (uint32_t *) mk();
-        uint32_t grid = (n + LRT_BLOCK - 1) / LRT_BLOCK;
-        if (n) {
-            if (D->use_lds) {                     // the render kernels' tracer: BVH image in LDS
-                const uint32_t g = std::min<uint32_t>((uint32_t) D->n_cus, (n + 1023) / 1024);
-                if (D->ext) { if (any_hit) k_trace_lds<true, true><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, D->lds, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n);
-                              else k_trace_lds<false, true><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, D->lds, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n); }
-                else if (any_hit) k_trace_lds<true><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, D->lds, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n);
-                else k_trace_lds<false><<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, D->lds, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n);
-            } else if (D->ext) { if (any_hit) k_trace<true, true><<<grid, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n);
-                                 else k_trace<false, true><<<grid, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n); }
-            else if (any_hit) k_trace<true><<<grid, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n);
-            else k_trace<false><<<grid, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, ox, oy, oz, dx, dy, dz, tm, t, u, v, prim, n);
-        }
-        HIP_CHECK(hipMemcpyAsync(hits->t, t, (size_t) n * 4, hipMemcpyDeviceToHost, st));
-        if (!any_hit) {
-            if (hits->u) HIP_CHECK(hipMemcpyAsync(hits->u, u, (size_t) n * 4, hipMemcpyDeviceToHost, st));
-            if (hits->v) HIP_CHECK(hipMemcpyAsync(hits->v, v, (size_t) n * 4, hipMemcpyDeviceToHost, st));
-            if (hits->prim) HIP_CHECK(hipMemcpyAsync(hits->prim, prim, (size_t) n * 4, hipMemcpyDeviceToHost, st));
-        }
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipGetLastError());
-    } catch (...) { for (void *p : tmp) (void) hipFree(p); throw; }
-    for (void *p : tmp) (void) hipFree(p);
+    DevTmp in[7], res[4];                           // origin, direction, tmax; t, u, v, prim
+    const float *src[7] = { rays->ox, rays->oy, rays->oz, rays->dx, rays->dy, rays->dz, rays->tmax };
+    for (int k = 0; k < 7; ++k) in[k].upload(src[k], n, st);
+    for (DevTmp &r : res) r.alloc(n);
+    float *t = res[0].p, *u = res[1].p, *v = res[2].p; uint32_t *prim = (uint32_t *) res[3].p;
+    if (n && D->use_lds) {                          // the render kernels' tracer: BVH image in LDS
+        const uint32_t g = std::min<uint32_t>((uint32_t) D->n_cus, (n + 1023) / 1024);
+        trace_lds_kernel(any_hit != 0, D->ext)<<<g, 1024, D->lds.total_bytes, st>>>((ScenePtr) D->d_sc, D->lds, in[0].p, in[1].p, in[2].p, in[3].p, in[4].p, in[5].p, in[6].p, t, u, v, prim, n);
+    } else if (n)
+        trace_kernel(any_hit != 0, D->ext)<<<(n + LRT_BLOCK - 1) / LRT_BLOCK, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, in[0].p, in[1].p, in[2].p, in[3].p, in[4].p, in[5].p, in[6].p, t, u, v, prim, n);
+    HIP_CHECK(hipMemcpyAsync(hits->t, t, (size_t) n * 4, hipMemcpyDeviceToHost, st));
+    if (!any_hit) {
+        if (hits->u) HIP_CHECK(hipMemcpyAsync(hits->u, u, (size_t) n * 4, hipMemcpyDeviceToHost, st));
+        if (hits->v) HIP_CHECK(hipMemcpyAsync(hits->v, v, (size_t) n * 4, hipMemcpyDeviceToHost, st));
+        if (hits->prim) HIP_CHECK(hipMemcpyAsync(hits->prim, prim, (size_t) n * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
 }
 
 } // namespace lrt
@@ -1300,7 +1294,7 @@ namespace lrt {
 // heterogeneous medium opts->grad_medium into a zeroed buffer of res_x * res_y * res_z floats (float atomics: last bits vary from run to run).
 void device_render_backward(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, const float *grad_image, lrt_param_grads *out, lrt_render_stats &stats, float *d_grid) {
     HIP_CHECK(hipSetDevice(D->device));
-    lrt_render_opts oprb = opts ? *opts : lrt_render_opts{ -1, -2, -1, -1, 0, 0, 0, 1, 0, 0, 0, 0 };
+    lrt_render_opts oprb = opts ? *opts : default_opts();
     oprb.integrator = LRT_INTEGRATOR_PRBVOLPATH;                               // resolve as the adjoint integrator: RBIntegrator.render_backward has no pass split (common.py prepare())
     ResolvedOpts O = resolve(d, &oprb);
     check_integrator_media(D, LRT_INTEGRATOR_PRBVOLPATH);
@@ -1315,10 +1309,7 @@ void device_render_backward(DeviceScene *D, const lrt_scene_desc &d, const lrt_r
         const lrt_medium_desc &M = d.media[grad_medium];
         n_vox = (size_t) M.grid_res[0] * M.grid_res[1] * M.grid_res[2];
         if (opts && opts->output_on_device) dg = d_grid;
-        else {
-            if (D->dgrid_floats < n_vox) { D->release(D->dgrid); D->dgrid = nullptr; D->dgrid_floats = 0; HIP_CHECK(hipMalloc((void **) &D->dgrid, n_vox * 4)); D->track(D->dgrid); D->dgrid_floats = n_vox; }
-            dg = D->dgrid;
-        }
+        else dg = D->grow(D->dgrid, D->dgrid_floats, n_vox);
     }
     const DFilm &F = D->sc.film;
     const size_t np = (size_t) F.width * F.height, T = F.has_alpha ? 4 : 3;
@@ -1331,17 +1322,15 @@ void device_render_backward(DeviceScene *D, const lrt_scene_desc &d, const lrt_r
     // primal radiance of every lane of a pass is kept (16 B / lane); passes of at most 2^28 lanes bound that buffer to 4.3 GB
     const uint64_t pass = std::min<uint64_t>(std::max<uint64_t>(n_lanes, 1), 1ull << 28);
     PoolGeometry g = pool_geometry(D, pass);
-    if (D->use_lds) g.block = 1024;
     const uint32_t records = (uint32_t) std::min<uint64_t>((uint64_t) g.n_wg * 2u * g.P, 0xffffffffull);
     ensure_workspace(D, records); ensure_prb_workspace(D, records, pass);
     const float *g_img = grad_image;
     if (!(opts && opts->output_on_device)) {
-        if (D->grad_floats < np * T) { D->release(D->grad_image); D->grad_image = nullptr; HIP_CHECK(hipMalloc((void **) &D->grad_image, np * T * 4)); D->track(D->grad_image); D->grad_floats = np * T; }
+        g_img = D->grow(D->grad_image, D->grad_floats, np * T);
         HIP_CHECK(hipMemcpyAsync(D->grad_image, grad_image, np * T * 4, hipMemcpyHostToDevice, st));
-        g_img = D->grad_image;
     }
     if (F.rfilter != LRT_RFILTER_BOX) {
-        if (D->wfilm_floats < np) { D->release(D->wfilm); D->wfilm = nullptr; HIP_CHECK(hipMalloc((void **) &D->wfilm, np * 4)); D->track(D->wfilm); D->wfilm_floats = np; }
+        D->grow(D->wfilm, D->wfilm_floats, np);
         HIP_CHECK(hipMemsetAsync(D->wfilm, 0, np * 4, st));
         // sum of reconstruction-filter weights per pixel: over every lane of the image, or (tile-sharded) over the lanes of the rank's
         // tiles dilated by 2 fn pixels, which completes the sums at every pixel the rank's own footprints read (ensure_halo_list)
@@ -1385,18 +1374,12 @@ void device_render_backward(DeviceScene *D, const lrt_scene_desc &d, const lrt_r
 // ---- learned subsurface model, network stage (include/liverrt.h; one lane per sample, weights through the scalar cache)
 void device_vae_scatter(const float *blob, uint32_t n, const float *in_pos, const float *in_dir, const float *poly, const float albedo[3], float g, float ior,
                         const float sigma_t[3], float fit_scale, uint32_t seed, float *out_pos, float *out_absorption, int device) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-        throw std::runtime_error("no HIP device available: the hip_ad_rgb back-end has no CPU fallback");
-    if (device < 0 || device >= count) throw std::runtime_error("invalid HIP device ordinal " + std::to_string(device));
-    HIP_CHECK(hipSetDevice(device));
+    select_device(device);
     if (n == 0) return;
     // the medium-level features are the same for every sample: evaluated once, on the device (one thread), with the kernels' own log / exp
-    struct Tmp { float *p = nullptr; ~Tmp() { if (p) (void) hipFree(p); } };
-    Tmp d_blob, d_pos, d_dir, d_poly, d_opos, d_oabs, d_feat;
-    auto up = [&](Tmp &t, const float *src, size_t cnt) { HIP_CHECK(hipMalloc((void **) &t.p, cnt * sizeof(float))); if (src) HIP_CHECK(hipMemcpy(t.p, src, cnt * sizeof(float), hipMemcpyHostToDevice)); };
+    DevTmp d_blob(LRT_VAE_N_FLOATS), d_pos(3 * (size_t) n), d_dir(3 * (size_t) n), d_poly(20 * (size_t) n), d_opos(3 * (size_t) n), d_oabs(n), d_feat(4);
+    auto up = [&](DevTmp &t, const float *src, size_t cnt) { HIP_CHECK(hipMemcpy(t.p, src, cnt * sizeof(float), hipMemcpyHostToDevice)); };
     up(d_blob, blob, LRT_VAE_N_FLOATS); up(d_pos, in_pos, 3 * (size_t) n); up(d_dir, in_dir, 3 * (size_t) n); up(d_poly, poly, 20 * (size_t) n);
-    up(d_opos, nullptr, 3 * (size_t) n); up(d_oabs, nullptr, n); up(d_feat, nullptr, 4);
     k_vae_medium_features<<<1, 1>>>(d_blob.p, albedo[0], albedo[1], albedo[2], g, ior, sigma_t[0], sigma_t[1], sigma_t[2], d_feat.p);
     HIP_CHECK(hipGetLastError());
     float feat[4]; HIP_CHECK(hipMemcpy(feat, d_feat.p, sizeof feat, hipMemcpyDeviceToHost));
@@ -1445,11 +1428,6 @@ void multi_context_destroy(MultiContext *m) { delete m; }
 __global__ void k_film_add(float *__restrict__ dst, const float *__restrict__ src, size_t n) {
     const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] += src[i];
-}
-
-static float *own_film(DeviceScene *D, size_t film_floats) {
-    if (D->film_floats < film_floats) { D->release(D->film); D->film = nullptr; HIP_CHECK(hipMalloc((void **) &D->film, film_floats * 4)); D->track(D->film); D->film_floats = film_floats; }
-    return D->film;
 }
 
 // Sums buf[i] (`count` floats or doubles on device i, stream of device i) over the devices, in place.  Distinct devices: one grouped
@@ -1505,22 +1483,15 @@ void device_render_multi(std::vector<DeviceScene *> &devs, MultiContext *&ctx, c
     const auto t0 = std::chrono::steady_clock::now();
     on_every_device(N, [&](size_t i) {
         HIP_CHECK(hipSetDevice(devs[i]->device));
-        films[i] = (i == 0 && on_device && film_raw) ? film_raw : own_film(devs[i], film_floats);
-        lrt_render_opts o = opts ? *opts : lrt_render_opts{ -1, -2, -1, -1, 0, 0, 0, 1, 0, 0, 0, 0 };
+        films[i] = (i == 0 && on_device && film_raw) ? film_raw : devs[i]->grow(devs[i]->film, devs[i]->film_floats, film_floats);
+        lrt_render_opts o = opts ? *opts : default_opts();
         o.tile_rank = (uint32_t) i; o.tile_count = (uint32_t) N; o.device = devs[i]->device; o.output_on_device = 1;
         device_render(devs[i], d, &o, films[i], nullptr, st[i]);
     });
     if (N > 1 || getenv("LRT_MULTI_ALWAYS_REDUCE")) reduce_across(devs, ctx, films, film_floats);
     DeviceScene *D0 = devs[0];
     HIP_CHECK(hipSetDevice(D0->device));
-    if (image) {
-        float *img = image;
-        if (!on_device) { if (D0->image_floats < image_floats) { D0->release(D0->image); D0->image = nullptr; HIP_CHECK(hipMalloc((void **) &D0->image, image_floats * 4)); D0->track(D0->image); D0->image_floats = image_floats; } img = D0->image; }
-        k_develop<<<(uint32_t) ((np + 255) / 256), 256, 0, D0->stream>>>(F, films[0], img, (uint32_t) np);
-        if (!on_device) HIP_CHECK(hipMemcpyAsync(image, img, image_floats * 4, hipMemcpyDeviceToHost, D0->stream));
-    }
-    if (film_raw && !on_device) HIP_CHECK(hipMemcpyAsync(film_raw, films[0], film_floats * 4, hipMemcpyDeviceToHost, D0->stream));
-    HIP_CHECK(hipStreamSynchronize(D0->stream)); HIP_CHECK(hipGetLastError());
+    develop_and_download(D0, films[0], film_raw, image, film_floats, image_floats, on_device);
     lrt_render_stats total{};
     for (auto &x : st) { total.n_samples += x.n_samples; total.n_iter += x.n_iter; total.n_shadow += x.n_shadow; total.n_launches += x.n_launches; total.n_records += x.n_records;
                          total.kernel_ms = std::max(total.kernel_ms, x.kernel_ms); total.lds_resident = x.lds_resident; total.record_bytes = x.record_bytes; total.n_closed_guard += x.n_closed_guard; }
@@ -1533,7 +1504,7 @@ void device_render_backward_multi(std::vector<DeviceScene *> &devs, MultiContext
     if (opts && opts->output_on_device) throw std::runtime_error("lrt_render_backward_multi: grad_image is a host buffer (every device takes its own copy)");
     std::vector<lrt_param_grads> g(N); std::vector<lrt_render_stats> st(N);
     on_every_device(N, [&](size_t i) {
-        lrt_render_opts o = opts ? *opts : lrt_render_opts{ -1, -2, -1, -1, 0, 0, 0, 1, 0, 0, 0, 0 };
+        lrt_render_opts o = opts ? *opts : default_opts();
         o.tile_rank = (uint32_t) i; o.tile_count = (uint32_t) N; o.device = devs[i]->device; o.output_on_device = 0;
         device_render_backward(devs[i], d, &o, grad_image, &g[i], st[i]);
     });
@@ -1554,11 +1525,8 @@ void device_emitter_probe(DeviceScene *D, const float *ref_p, const float *sampl
     HIP_CHECK(hipSetDevice(D->device));
     if (!n) return;
     hipStream_t st = D->stream;
-    struct Tmp { float *p = nullptr; ~Tmp() { if (p) (void) hipFree(p); } } dr, ds, dout;
-    HIP_CHECK(hipMalloc((void **) &dr.p, (size_t) n * 3 * 4)); HIP_CHECK(hipMalloc((void **) &ds.p, (size_t) n * 2 * 4));
-    HIP_CHECK(hipMalloc((void **) &dout.p, (size_t) n * LRT_PROBE_FLOATS * 4));
-    HIP_CHECK(hipMemcpyAsync(dr.p, ref_p, (size_t) n * 3 * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(ds.p, sample, (size_t) n * 2 * 4, hipMemcpyHostToDevice, st));
+    DevTmp dr, ds, dout((size_t) n * LRT_PROBE_FLOATS);
+    dr.upload(ref_p, (size_t) n * 3, st); ds.upload(sample, (size_t) n * 2, st);
     k_emitter_probe<<<(n + LRT_BLOCK - 1) / LRT_BLOCK, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, dr.p, ds.p, n, dout.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * LRT_PROBE_FLOATS * 4, hipMemcpyDeviceToHost, st));
@@ -1571,9 +1539,8 @@ void device_envmap_probe(DeviceScene *D, const float *dir, uint32_t n, float *ou
     if (D->sc.env.emitter < 0) throw std::runtime_error("lrt_envmap_probe: the scene has no environment emitter");
     if (!n) return;
     hipStream_t st = D->stream;
-    struct Tmp { float *p = nullptr; ~Tmp() { if (p) (void) hipFree(p); } } dd, dout;
-    HIP_CHECK(hipMalloc((void **) &dd.p, (size_t) n * 3 * 4)); HIP_CHECK(hipMalloc((void **) &dout.p, (size_t) n * 4 * 4));
-    HIP_CHECK(hipMemcpyAsync(dd.p, dir, (size_t) n * 3 * 4, hipMemcpyHostToDevice, st));
+    DevTmp dd, dout((size_t) n * 4);
+    dd.upload(dir, (size_t) n * 3, st);
     k_envmap_probe<<<(n + LRT_BLOCK - 1) / LRT_BLOCK, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, dd.p, n, dout.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * 4 * 4, hipMemcpyDeviceToHost, st));
@@ -1585,13 +1552,9 @@ void device_bsdf_probe(DeviceScene *D, const float *o, const float *d, const flo
     HIP_CHECK(hipSetDevice(D->device));
     if (!n) return;
     hipStream_t st = D->stream;
-    struct Tmp { float *p = nullptr; ~Tmp() { if (p) (void) hipFree(p); } } in[4], dout;
+    DevTmp in[4], dout((size_t) n * LRT_BSDF_PROBE_FLOATS);
     const float *src[4] = { o, d, sample, wo_query };
-    for (int k = 0; k < 4; ++k) {
-        HIP_CHECK(hipMalloc((void **) &in[k].p, (size_t) n * 3 * 4));
-        HIP_CHECK(hipMemcpyAsync(in[k].p, src[k], (size_t) n * 3 * 4, hipMemcpyHostToDevice, st));
-    }
-    HIP_CHECK(hipMalloc((void **) &dout.p, (size_t) n * LRT_BSDF_PROBE_FLOATS * 4));
+    for (int k = 0; k < 4; ++k) in[k].upload(src[k], (size_t) n * 3, st);
     k_bsdf_probe<<<(n + LRT_BLOCK - 1) / LRT_BLOCK, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, in[0].p, in[1].p, in[2].p, in[3].p, n, dout.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * LRT_BSDF_PROBE_FLOATS * 4, hipMemcpyDeviceToHost, st));
@@ -1620,14 +1583,10 @@ __global__ void k_math_eval(int fn, const float *__restrict__ x, const float *__
     out[i] = a; out2[i] = b;
 }
 void device_math_eval(int fn, const float *x, const float *y, uint32_t n, float *out, float *out2, int device) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) throw std::runtime_error("no HIP device available: the hip_ad_rgb back-end has no CPU fallback");
-    if (device < 0 || device >= count) throw std::runtime_error("invalid HIP device ordinal " + std::to_string(device));
+    select_device(device);
     if (fn < 0 || fn > 8) throw std::invalid_argument("lrt_math_eval: function 0 .. 8");
-    HIP_CHECK(hipSetDevice(device));
     if (!n) return;
-    struct Tmp { float *p = nullptr; ~Tmp() { if (p) (void) hipFree(p); } } dx, dy, d1, d2;
-    for (Tmp *t : { &dx, &dy, &d1, &d2 }) HIP_CHECK(hipMalloc((void **) &t->p, (size_t) n * 4));
+    DevTmp dx(n), dy(n), d1(n), d2(n);
     HIP_CHECK(hipMemcpy(dx.p, x, (size_t) n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dy.p, y ? y : x, (size_t) n * 4, hipMemcpyHostToDevice));
     k_math_eval<<<(n + 255) / 256, 256>>>(fn, dx.p, dy.p, n, d1.p, d2.p);
     HIP_CHECK(hipGetLastError());
@@ -1653,10 +1612,7 @@ struct Denoiser {
 };
 
 Denoiser *denoiser_create(int width, int height, bool use_albedo, bool use_normals, bool denoise_alpha, const lrt_denoise_params &params, int device) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) throw std::runtime_error("no HIP device available: the hip_ad_rgb back-end has no CPU fallback");
-    if (device < 0 || device >= count) throw std::runtime_error("invalid HIP device ordinal " + std::to_string(device));
-    HIP_CHECK(hipSetDevice(device));
+    select_device(device);
     Denoiser *D = new Denoiser();
     try {
         D->device = device; D->w = width; D->h = height; D->alb = use_albedo; D->nrm = use_normals; D->alpha = denoise_alpha; D->prm = params;
