@@ -150,6 +150,12 @@ DEV uint64_t lane_local_index(RpRef rp, uint32_t lane) {
     const uint32_t pixel = (rp.log2_spp != 0xffffffffu) ? (lane >> rp.log2_spp) : (lane / rp.spp);
     return (uint64_t) rp.pixel_slot[pixel] * rp.spp + (lane - pixel * rp.spp);
 }
+// The inverse, slot j -> lane: a tile-sharded render's slots go through the rank's pixel list
+DEV uint32_t slot_to_lane(RpRef rp, const uint32_t *__restrict__ pixel_list, uint64_t j) {
+    if (!pixel_list) return (uint32_t) j;
+    const uint32_t pj = (rp.log2_spp != 0xffffffffu) ? (uint32_t) (j >> rp.log2_spp) : (uint32_t) (j / rp.spp);
+    return pixel_list[pj] * rp.spp + (uint32_t) (j - (uint64_t) pj * rp.spp);
+}
 // The sampler of a lane at the start of the current pass: freshly seeded in pass 0; in later passes the independent sampler
 // continues from the state its path of the previous pass left (Sampler::advance() does not reseed), index j = rank-local lane.
 template <bool LD>
@@ -195,7 +201,7 @@ DEV Ray camera_ray(SceneRef sc, float ax, float ay) {
 // path.cpp:95-170 up to the loop).
 template <bool LD>
 DEV PathState generate_camera_path(SceneRef sc, RpRef rp, const uint32_t *__restrict__ pixel_list, uint64_t j) {
-    uint32_t lane;
+    uint32_t lane;                               // slot_to_lane, written out: the call changes the render kernels' code
     if (pixel_list) { uint32_t pj = (rp.log2_spp != 0xffffffffu) ? (uint32_t) (j >> rp.log2_spp) : (uint32_t) (j / rp.spp); lane = pixel_list[pj] * rp.spp + (uint32_t) (j - (uint64_t) pj * rp.spp); }
     else lane = (uint32_t) j;
     SamplerT<LD> rng = lane_rng_pass_start<LD>(rp, lane, j);
@@ -223,110 +229,7 @@ DEV PathState generate_camera_path(SceneRef sc, RpRef rp, const uint32_t *__rest
 }
 
 // ------------------------------------------------------------------ film
-template <typename FP> DEV float estrin10(float x, FP c) {
-    float x2 = x * x, x4 = x2 * x2, x8 = x4 * x4;
-    float a0 = fma_(x, c[1], c[0]), a1 = fma_(x, c[3], c[2]), a2 = fma_(x, c[5], c[4]), a3 = fma_(x, c[7], c[6]), a4 = fma_(x, c[9], c[8]);
-    float b0 = fma_(x2, a1, a0), b1 = fma_(x2, a3, a2);
-    float c0 = fma_(x4, b1, b0);
-    return fma_(x8, a4, c0);
-}
-DEV float rfilter_eval(FilmRef F, float x) {
-    if (F.rfilter == LRT_RFILTER_GAUSSIAN) return fmax_(estrin10(sqr(x), F.rf_coeff), 0.f);
-    if (F.rfilter == LRT_RFILTER_TENT) return fmax_(0.f, 1.f - __builtin_fabsf(x * F.rf_inv_radius));
-    return (__builtin_fabsf(x) <= 0.5f) ? 1.f : 0.f;
-}
-
-// A finished path: splat {R,G,B,[A],W=1} (integrator.cpp:499-520, imageblock.cpp:174-232,431-500),
-// or, for the per-lane test hook, store the radiance.
-DEV void finish_path(SceneRef sc, RpRef rp, float *__restrict__ film, float *__restrict__ sample_out,
-                     uint64_t sample_base, uint32_t lane, V3 L, bool valid) {
-    if (rp.integrator == LRT_INTEGRATOR_PATH && !valid) L = V3(0.f);                 // path.cpp:342-345
-    if (sample_out) {                               // per-lane output, indexed by the rank-local lane index
-        const uint64_t j = lane_local_index(rp, lane);
-        float4 *o = reinterpret_cast<float4 *>(sample_out) + (j - sample_base);
-        *o = make_float4(L.x, L.y, L.z, valid ? 1.f : 0.f);
-        return;
-    }
-    FilmRef F = sc.film;
-    int px, py; lane_to_pixel(sc, rp, lane, &px, &py);
-    const int C = F.channels;
-    const float alpha = valid ? 1.f : 0.f;
-    auto splat = [&](float *p, float w) {
-        atomicAdd(p + 0, L.x * w); atomicAdd(p + 1, L.y * w); atomicAdd(p + 2, L.z * w);
-        if (F.has_alpha) { atomicAdd(p + 3, alpha * w); atomicAdd(p + 4, 1.f * w); } else atomicAdd(p + 3, 1.f * w);
-    };
-    if (F.rfilter == LRT_RFILTER_BOX) {
-        int x = px - F.crop_offset_x, y = py - F.crop_offset_y;
-        float *p = film + ((size_t) y * F.width + x) * C;
-        atomicAdd(p + 0, L.x); atomicAdd(p + 1, L.y); atomicAdd(p + 2, L.z);
-        if (F.has_alpha) { atomicAdd(p + 3, alpha); atomicAdd(p + 4, 1.f); } else atomicAdd(p + 3, 1.f);
-        return;
-    }
-    float jx, jy; lane_jitter(rp, lane, lane_local_index(rp, lane), jx, jy);
-    float spx = (float) px + jx, spy = (float) py + jy;
-    int n = F.fn, count = F.fcount;
-    int pix = (int) __builtin_floorf(spx) - n, piy = (int) __builtin_floorf(spy) - n;
-    float relx = (float) pix + .5f - spx, rely = (float) piy + .5f - spy;
-    for (int ys = 0; ys < count; ++ys) {
-        int y = piy - F.crop_offset_y + ys;
-        float wy = rfilter_eval(F, rely + (float) ys);
-        if (y < 0 || y >= F.height || (wy == 0.f && finite3(L))) continue;
-        for (int xs = 0; xs < count; ++xs) {
-            int x = pix - F.crop_offset_x + xs;
-            if (x < 0 || x >= F.width) continue;
-            float w = wy * rfilter_eval(F, relx + (float) xs);
-            if (w == 0.f && finite3(L)) continue;                  // a zero weight adds nothing unless the radiance is non-finite (value * 0 = NaN, as imageblock.cpp computes it)
-            splat(film + ((size_t) y * F.width + x) * C, w);
-        }
-    }
-}
-
-// Film accumulation called by EVERY lane of a wave (`finishing` selects the lanes that retire a path).  Box filter:
-// lanes that splat into the same pixel are summed inside the wave first (the wavefront keeps a pixel's samples in
-// neighbouring lanes, so a wave usually holds one or two distinct pixels) and one lane issues the atomics.
-DEV void finish_paths_wave(SceneRef sc, RpRef rp, float *__restrict__ film, float *__restrict__ sample_out,
-                           uint64_t sample_base, bool finishing, uint32_t lane, V3 L, bool valid) {
-    FilmRef F = sc.film;
-    if (sample_out || F.rfilter != LRT_RFILTER_BOX) {
-        if (finishing) finish_path(sc, rp, film, sample_out, sample_base, lane, L, valid);
-        return;
-    }
-    if (rp.integrator == LRT_INTEGRATOR_PATH && !valid) L = V3(0.f);
-    uint32_t pixel = 0xffffffffu;
-    if (finishing) { int px, py; lane_to_pixel(sc, rp, lane, &px, &py); pixel = (uint32_t) (py - F.crop_offset_y) * (uint32_t) F.width + (uint32_t) (px - F.crop_offset_x); }
-    if (__ballot(finishing) == 0ull) return;
-#ifdef LRT_FILM_LEADER_LOOP
-    unsigned long long todo = __ballot(finishing);
-    const uint32_t me = threadIdx.x & 63u;
-    while (todo) {
-        int leader = __ffsll((long long) todo) - 1;
-        uint32_t key = __shfl(pixel, leader);
-        bool mine = finishing && pixel == key;
-        unsigned long long grp = __ballot(mine);
-        float r = mine ? L.x : 0.f, g = mine ? L.y : 0.f, b = mine ? L.z : 0.f;
-        r = wave_sum(r); g = wave_sum(g); b = wave_sum(b);
-        const float w = (float) __popcll(grp), al = F.has_alpha ? (float) __popcll(__ballot(mine && valid)) : 0.f;
-        if ((int) me == leader) {
-            float *p = film + (size_t) key * F.channels;
-            atomicAdd(p + 0, r); atomicAdd(p + 1, g); atomicAdd(p + 2, b);
-            if (F.has_alpha) { atomicAdd(p + 3, al); atomicAdd(p + 4, w); } else atomicAdd(p + 3, w);
-        }
-        todo &= ~grp;
-    }
-#else
-    // Queues keep lanes in lane order, so the finishing lanes of one pixel sit in RUNS of consecutive lanes: one segmented sum over the
-    // wave adds up every run at once (no loop over the pixels of the tile, no LDS round trip) and the last lane of each run issues the
-    // atomics.  A pixel that appears in two runs simply gets two sets of atomics.  Lanes that do not finish are runs of their own (zeros).
-    const uint32_t prev = wave_prev(pixel, 0xfffffffeu), next = wave_next(pixel, 0xfffffffeu);
-    float v[5] = { finishing ? L.x : 0.f, finishing ? L.y : 0.f, finishing ? L.z : 0.f, finishing ? 1.f : 0.f, (finishing && valid) ? 1.f : 0.f };
-    wave_segmented_sums(v, pixel != prev || !finishing);
-    if (finishing && pixel != next) {
-        float *p = film + (size_t) pixel * F.channels;
-        atomicAdd(p + 0, v[0]); atomicAdd(p + 1, v[1]); atomicAdd(p + 2, v[2]);
-        if (F.has_alpha) { atomicAdd(p + 3, v[4]); atomicAdd(p + 4, v[3]); } else atomicAdd(p + 3, v[3]);
-    }
-#endif
-}
+#include "film.h"
 
 // ---------------------------------------------------------- volpath NEE
 // src/integrators/volpath.cpp:400-554.  ref_n is zero for medium interactions.
@@ -1068,11 +971,9 @@ k_build_dist_grid(const float4 *__restrict__ tris, uint32_t n_slots, DDistGrid g
     out[c] = cv.u;
 }
 
-// Film accumulation for reconstruction filters wider than a pixel (Gaussian, tent; imageblock.cpp:174-232,431-500).  The
-// render kernel stores each lane's radiance (16 B / lane); this pass then walks the lanes in order, so the 64 lanes of a
-// wave belong to one or two pixels: the filter footprint of a group of lanes with the same footprint origin is reduced
-// inside the wave (one butterfly per cell and channel) and lane c issues the atomics of cell c.  Compared with splatting
-// where paths happen to retire this divides the float atomics by the group size (up to 64).
+// Film accumulation for reconstruction filters wider than a pixel: the render kernel stores each lane's radiance (16 B / lane) and this
+// pass takes the lanes in lane order.  The loop is film_walk (film.h) written out for R, G, B, [A], W in named registers: through the
+// template the C2 frame measured 1 % slower.  The walk's rules hold here word for word.
 // WEIGHTS_ONLY: accumulate just the filter weights into a one-channel film (the PRB adjoint's normalisation image,
 // common.py:730-746); lane_L is not read.
 template <bool WEIGHTS_ONLY>
@@ -1087,12 +988,10 @@ k_splat_lanes(ScenePtr scp, LaunchPtr lp) {
     const uint64_t i = (uint64_t) blockIdx.x * LRT_BLOCK + threadIdx.x;
     const uint32_t me = threadIdx.x & 63u;
     const bool have = i < n;
-    V3 L(0.f); float alpha = 0.f, relx = 0.f, rely = 0.f; int pix = 0, piy = 0; uint32_t key = 0xffffffffu;
+    V3 L(0.f); float alpha = 0.f; FilmFootprint fp{}; uint32_t key = 0xffffffffu;
     if (have) {
         const uint64_t j = slot_base + i;
-        uint32_t lane;
-        if (pixel_list) { uint32_t pj = (rp.log2_spp != 0xffffffffu) ? (uint32_t) (j >> rp.log2_spp) : (uint32_t) (j / rp.spp); lane = pixel_list[pj] * rp.spp + (uint32_t) (j - (uint64_t) pj * rp.spp); }
-        else lane = (uint32_t) j;
+        const uint32_t lane = slot_to_lane(rp, pixel_list, j);
         if (!WEIGHTS_ONLY) {
             const float4 v = lane_L[i];
             L = V3(v.x, v.y, v.z); alpha = v.w;
@@ -1100,11 +999,10 @@ k_splat_lanes(ScenePtr scp, LaunchPtr lp) {
         }
         int px, py; lane_to_pixel(sc, rp, lane, &px, &py);
         float jx, jy; lane_jitter(rp, lane, j, jx, jy);
-        float spx = (float) px + jx, spy = (float) py + jy;
-        pix = (int) __builtin_floorf(spx) - F.fn; piy = (int) __builtin_floorf(spy) - F.fn;
-        relx = (float) pix + .5f - spx; rely = (float) piy + .5f - spy;
-        key = (uint32_t) (piy + 0x4000) << 16 | (uint32_t) (pix + 0x4000);
+        fp = film_footprint(F, px, py, jx, jy);
+        key = fp.key();
     }
+    const float relx = fp.relx, rely = fp.rely; const int pix = fp.pix, piy = fp.piy;
     const int count = F.fcount, C = F.channels;
     unsigned long long todo = __ballot(have);
     while (todo) {
@@ -1118,14 +1016,13 @@ k_splat_lanes(ScenePtr scp, LaunchPtr lp) {
             const float wy = mine ? rfilter_eval(F, rely + (float) ys) : 0.f;
             for (int xs = 0; xs < count; ++xs, ++ci) {
                 const float w = mine ? wy * rfilter_eval(F, relx + (float) xs) : 0.f;
-                // lanes outside the group add exact zeros (a product with their weight 0 would turn a non-finite radiance into NaN for this group's pixels)
                 float r = mine ? L.x * w : 0.f, g = mine ? L.y * w : 0.f, b = mine ? L.z * w : 0.f, a = alpha * w, ww = w;
                 if (!WEIGHTS_ONLY) { r = wave_sum(r); g = wave_sum(g); b = wave_sum(b); if (F.has_alpha) a = wave_sum(a); }
                 ww = wave_sum(ww);
                 if ((int) me == (ci & 63)) { tr = r; tg = g; tb = b; ta = a; tw = ww; }
-                if ((ci & 63) == 63 || ci == n_cells - 1) {            // a chunk of (up to) 64 cells is complete: lane c flushes cell base + c
-                    const int cell = (ci & ~63) + (int) me;            // (footprints wider than 8 x 8 pixels take several chunks: gaussian stddev > 0.875, tent radius > 3.5)
-                    if (cell <= ci && (tw != 0.f || tr != tr || tg != tg || tb != tb)) {   // zero-weight cells only matter when a non-finite radiance made them NaN (imageblock.cpp adds value * 0 there)
+                if ((ci & 63) == 63 || ci == n_cells - 1) {
+                    const int cell = (ci & ~63) + (int) me;
+                    if (cell <= ci && (tw != 0.f || tr != tr || tg != tg || tb != tb)) {
                         const int cy = cell / count, cx = cell - cy * count;
                         const int x = gx - F.crop_offset_x + cx, y = gy - F.crop_offset_y + cy;
                         if (x >= 0 && x < F.width && y >= 0 && y < F.height) {

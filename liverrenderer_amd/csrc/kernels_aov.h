@@ -9,8 +9,7 @@
 //   k_aov_develop  film / W into a channel range of the merged image (HDRFilm::develop without the colour conversion)
 //   k_aov_copy     an inner integrator's developed image into its channel range of the merged image (merge_channels, aov.cpp:523-545)
 //
-// The existing kernels are not touched: the film helpers below are written for a run-time channel count next to the fixed-layout
-// ones of kernels.h (finish_paths_wave, k_splat_lanes).
+// The film has a run-time channel count: the AOVs go through film_run / film_walk (film.h) one at a time, three channels each, then W.
 #pragma once
 #include "kernels.h"
 
@@ -106,7 +105,6 @@ k_aov(ScenePtr scp, LaunchPtr lp, AovSpecPtr A) {
         __syncthreads();
     }
     const int n_aovs = A->n_aovs, n_ch = A->n_ch, C = n_ch + 1;
-    const uint32_t me = tid & 63u;
     for (uint64_t base = (uint64_t) blockIdx.x * BS; base < n; base += (uint64_t) gridDim.x * BS) {
         const uint64_t i = base + tid;
         const bool have = i < n;
@@ -146,12 +144,9 @@ k_aov(ScenePtr scp, LaunchPtr lp, AovSpecPtr A) {
             continue;
         }
         if (F.rfilter == LRT_RFILTER_BOX) {
-            // as finish_paths_wave: the lanes of one pixel are runs of consecutive lanes; one segmented sum per channel, the last lane of
-            // each run issues the atomics
-            const uint32_t pixel = have ? (uint32_t) (py - F.crop_offset_y) * (uint32_t) F.width + (uint32_t) (px - F.crop_offset_x) : 0xffffffffu;
-            const uint32_t prev = wave_prev(pixel, 0xfffffffeu), next = wave_next(pixel, 0xfffffffeu);
-            const bool head = pixel != prev || !have, tail = have && pixel != next;
-            float *p = film + (size_t) pixel * C;
+            const FilmRun run = film_run(F, have, px, py);
+            const bool head = run.head, tail = run.tail;
+            float *p = film + (size_t) run.pixel * C;
             for (int k = 0; k < n_aovs; ++k) {
                 const int type = A->type[k], w = aov_width(type), off = A->offset[k];
                 float v[3]; aov_eval(sc, A, type, si, v);
@@ -166,46 +161,21 @@ k_aov(ScenePtr scp, LaunchPtr lp, AovSpecPtr A) {
             if (tail) atomicAdd(p + n_ch, wv[0]);
             continue;
         }
-        // wider filters: the footprint reduction of k_splat_lanes, per group of lanes with the same footprint origin; the group's leader
-        // adds each cell's totals (the channel count is a run-time value here, so the totals are not spread over the lanes)
-        float relx = 0.f, rely = 0.f; int pix = 0, piy = 0; uint32_t key = 0xffffffffu;
-        if (have) {
-            const float spx = (float) px + jx, spy = (float) py + jy;
-            pix = (int) __builtin_floorf(spx) - F.fn; piy = (int) __builtin_floorf(spy) - F.fn;
-            relx = (float) pix + .5f - spx; rely = (float) piy + .5f - spy;
-            key = (uint32_t) (piy + 0x4000) << 16 | (uint32_t) (pix + 0x4000);
-        }
-        const int count = F.fcount;
-        for (int k = -1; k < n_aovs; ++k) {      // k = -1: the weight channel W; each AOV is evaluated once per lane
-            const int type = k < 0 ? LRT_AOV_DEPTH : A->type[k], w = k < 0 ? 1 : aov_width(type), off = k < 0 ? n_ch : A->offset[k];
-            float v[3] = { 1.f, 0.f, 0.f };
-            if (k >= 0) aov_eval(sc, A, type, si, v);
-            unsigned long long todo = __ballot(have);
-            while (todo) {
-                const int leader = __ffsll((long long) todo) - 1;
-                const uint32_t k0 = __shfl(key, leader);
-                const bool mine = have && key == k0;
-                const int gx = __shfl(pix, leader), gy = __shfl(piy, leader);
-                for (int ys = 0; ys < count; ++ys) {
-                    const int y = gy - F.crop_offset_y + ys;
-                    const float wy = mine ? rfilter_eval(F, rely + (float) ys) : 0.f;
-                    for (int xs = 0; xs < count; ++xs) {
-                        const int x = gx - F.crop_offset_x + xs;
-                        const float wt = mine ? wy * rfilter_eval(F, relx + (float) xs) : 0.f;
-                        const float tw = wave_sum(wt);
-                        if (x < 0 || x >= F.width || y < 0 || y >= F.height) continue;     // wave-uniform
-                        float *p = film + ((size_t) y * F.width + x) * C + off;
+        // wider filters: one walk per AOV (channels at or past its width are not live), then W; each AOV is evaluated once per lane
+        const FilmFootprint fp = film_footprint(F, px, py, jx, jy);         // (lanes without a sample: zeros, not read)
+        for (int k = 0; k < n_aovs; ++k) {
+            const int type = A->type[k], w = aov_width(type), off = A->offset[k];
+            float v[3]; aov_eval(sc, A, type, si, v);
+            film_walk<3, -1>(F, have, fp, v, [&](int c) { return c < w; }, [&](int x, int y, const float (&t)[3]) {
+                float *p = film + ((size_t) y * F.width + x) * C + off;
 #pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            if (c >= w) break;                                              // wave-uniform
-                            const float s = wave_sum(mine ? v[c] * wt : 0.f);               // lanes outside the group add exact zeros
-                            if ((int) me == leader && (tw != 0.f || s != s)) atomicAdd(p + c, s);
-                        }
-                    }
-                }
-                todo &= ~__ballot(mine);
-            }
+                for (int c = 0; c < 3; ++c) if (c < w) atomicAdd(p + c, t[c]);
+            });
         }
+        const float one[1] = { 1.f };
+        film_walk<1, 0>(F, have, fp, one, [](int) { return true; }, [&](int x, int y, const float (&t)[1]) {
+            atomicAdd(film + ((size_t) y * F.width + x) * C + n_ch, t[0]);
+        });
     }
 }
 

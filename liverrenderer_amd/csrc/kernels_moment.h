@@ -6,12 +6,12 @@
 //                     squares per lane (moment_values) and accumulates R,G,B,[A],W,X,Y,Z,m2X,m2Y,m2Z through the reconstruction filter.
 //                     WIDE = false (box): the lanes of a pixel are runs of consecutive lanes, one segmented wave sum per channel, and
 //                     the 10 / 11 sums of a run are handed to 10 / 11 lanes that add one contiguous 40 / 44-byte pixel record each.
-//                     WIDE = true (gaussian, tent): the footprint reduction of k_splat_lanes with the extra channels.
+//                     WIDE = true (gaussian, tent): film_walk (film.h) over the NC channels.
 //   k_moment_develop  HDRFilm::develop of that film: every channel but W, divided by W (by 1 where W = 0)
 //   k_moment_lanes    test hook: moment_values of a lane buffer, 6 floats per lane
 //
 // The channel count is a template parameter (ALPHA): every per-channel array below is indexed by unrolled constants and lives in
-// registers.  The existing kernels are not touched.
+// registers.
 #pragma once
 #include "kernels.h"
 
@@ -62,24 +62,23 @@ k_moment_splat(ScenePtr scp, LaunchPtr lp) {
     uint32_t lane = 0; uint64_t j = 0;
     if (have) {
         j = slot_base + i;
-        if (pixel_list) { uint32_t pj = (rp.log2_spp != 0xffffffffu) ? (uint32_t) (j >> rp.log2_spp) : (uint32_t) (j / rp.spp); lane = pixel_list[pj] * rp.spp + (uint32_t) (j - (uint64_t) pj * rp.spp); }
-        else lane = (uint32_t) j;
+        lane = slot_to_lane(rp, pixel_list, j);
         const float4 r = lane_L[i];
         V3 L(r.x, r.y, r.z);
         if (rp.integrator == LRT_INTEGRATOR_PATH && r.w == 0.f) L = V3(0.f);          // path.cpp:342-345, before the conversion to XYZ
         moment_record<ALPHA>(L, r.w, v);
     }
     if (!WIDE) {
-        // Box filter: as finish_paths_wave, one segmented sum per channel over runs of lanes with the same pixel; the last lane of a run
-        // holds the run's NC sums.
-        uint32_t pixel = 0xffffffffu;
-        if (have) { int px, py; lane_to_pixel(sc, rp, lane, &px, &py); pixel = (uint32_t) (py - F.crop_offset_y) * (uint32_t) F.width + (uint32_t) (px - F.crop_offset_x); }
-        const uint32_t prev = wave_prev(pixel, 0xfffffffeu), next = wave_next(pixel, 0xfffffffeu);
-        wave_segmented_sums(v, pixel != prev || !have);
+        // Box filter (film_run): the last lane of a run holds the run's NC sums.
+        int px = 0, py = 0;
+        if (have) lane_to_pixel(sc, rp, lane, &px, &py);
+        const FilmRun run = film_run(F, have, px, py);
+        const uint32_t pixel = run.pixel;
+        wave_segmented_sums(v, run.head);
         // The adds of a run are spread over lanes: up to four runs at a time, run s of the group served by lanes 16 s .. 16 s + NC - 1,
         // each of which fetches its channel's sum from the run's last lane and adds it: one atomic instruction writes four contiguous
         // pixel records instead of NC instructions with one lane per record.
-        unsigned long long tails = __ballot(have && pixel != next);
+        unsigned long long tails = __ballot(run.tail);
         const uint32_t ch = me & 15u, slot = me >> 4;
         while (tails) {
             int src = -1;
@@ -94,60 +93,17 @@ k_moment_splat(ScenePtr scp, LaunchPtr lp) {
         }
         return;
     }
-    // Wider filters (imageblock.cpp:174-232,431-500): the footprint of a group of lanes with the same footprint origin is reduced inside
-    // the wave, one butterfly per cell and channel; lane c keeps the totals of cell (chunk base + c) and issues that cell's adds.
-    float relx = 0.f, rely = 0.f; int pix = 0, piy = 0; uint32_t key = 0xffffffffu;
+    FilmFootprint fp{};
     if (have) {
         int px, py; lane_to_pixel(sc, rp, lane, &px, &py);
         float jx, jy; lane_jitter(rp, lane, j, jx, jy);
-        const float spx = (float) px + jx, spy = (float) py + jy;
-        pix = (int) __builtin_floorf(spx) - F.fn; piy = (int) __builtin_floorf(spy) - F.fn;
-        relx = (float) pix + .5f - spx; rely = (float) piy + .5f - spy;
-        key = (uint32_t) (piy + 0x4000) << 16 | (uint32_t) (pix + 0x4000);
+        fp = film_footprint(F, px, py, jx, jy);
     }
-    const int count = F.fcount;
-    unsigned long long todo = __ballot(have);
-    while (todo) {
-        const int leader = __ffsll((long long) todo) - 1;
-        const uint32_t k0 = (uint32_t) __shfl((int) key, leader);
-        const bool mine = have && key == k0;
-        const int gx = __shfl(pix, leader), gy = __shfl(piy, leader);
-        float t[NC];
+    film_walk<NC, WI>(F, have, fp, v, [](int) { return true; }, [&](int x, int y, const float (&t)[NC]) {
+        float *p = film + ((size_t) y * F.width + x) * NC;
 #pragma unroll
-        for (int k = 0; k < NC; ++k) t[k] = 0.f;
-        const int n_cells = count * count;
-        for (int ys = 0, ci = 0; ys < count; ++ys) {
-            const float wy = mine ? rfilter_eval(F, rely + (float) ys) : 0.f;
-            for (int xs = 0; xs < count; ++xs, ++ci) {
-                const float w = mine ? wy * rfilter_eval(F, relx + (float) xs) : 0.f;
-                const bool keep = (int) me == (ci & 63);
-#pragma unroll
-                for (int k = 0; k < NC; ++k) {
-                    // lanes outside the group add exact zeros (a product with their weight 0 would turn a non-finite value into NaN for this group's pixels)
-                    const float s = wave_sum(mine ? v[k] * w : 0.f);
-                    if (keep) t[k] = s;
-                }
-                if ((ci & 63) == 63 || ci == n_cells - 1) {            // a chunk of (up to) 64 cells is complete: lane c flushes cell base + c
-                    const int cell = (ci & ~63) + (int) me;
-                    bool nan = false;                                  // zero-weight cells only matter when a non-finite value made them NaN (imageblock.cpp adds value * 0 there)
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) nan = nan || t[k] != t[k];
-                    if (cell <= ci && (t[WI] != 0.f || nan)) {
-                        const int cy = cell / count, cx = cell - cy * count;
-                        const int x = gx - F.crop_offset_x + cx, y = gy - F.crop_offset_y + cy;
-                        if (x >= 0 && x < F.width && y >= 0 && y < F.height) {
-                            float *p = film + ((size_t) y * F.width + x) * NC;
-#pragma unroll
-                            for (int k = 0; k < NC; ++k) atomicAdd(p + k, t[k]);
-                        }
-                    }
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) t[k] = 0.f;
-                }
-            }
-        }
-        todo &= ~__ballot(mine);
-    }
+        for (int k = 0; k < NC; ++k) atomicAdd(p + k, t[k]);
+    });
 }
 
 // src/films/hdrfilm.cpp:306-410 for the moment film: W is dropped, the other channels are divided by it

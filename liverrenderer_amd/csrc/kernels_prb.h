@@ -341,13 +341,6 @@ DEV bool prb_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const TR &
     return active;
 }
 
-// Filter footprint helpers shared by the weight-film and delta_L kernels (imageblock.cpp:431-500)
-DEV void lane_sample_pos(SceneRef sc, RpRef rp, uint32_t lane, float *spx, float *spy, int *px, int *py) {
-    lane_to_pixel(sc, rp, lane, px, py);
-    float jx, jy; lane_jitter(rp, lane, lane_local_index(rp, lane), jx, jy);
-    *spx = (float) *px + jx; *spy = (float) *py + jy;
-}
-
 // delta_L of a lane: gradient of sum(image * grad_image) w.r.t. the lane's radiance through splat + develop
 // (common.py:730-746).  Box filter: grad[pixel] / W[pixel].
 DEV V3 lane_delta_L(SceneRef sc, RpRef rp, uint32_t lane, const float *__restrict__ grad_image, const float *__restrict__ wfilm) {
@@ -355,24 +348,24 @@ DEV V3 lane_delta_L(SceneRef sc, RpRef rp, uint32_t lane, const float *__restric
     const int T = F.has_alpha ? 4 : 3;
     if (F.rfilter == LRT_RFILTER_BOX) {
         int px, py; lane_to_pixel(sc, rp, lane, &px, &py);
-        size_t p = (size_t) (py - F.crop_offset_y) * F.width + (px - F.crop_offset_x);
+        size_t p = film_pixel_index(F, px, py);
         float w = (float) rp.spp;
         return V3(grad_image[p * T] / w, grad_image[p * T + 1] / w, grad_image[p * T + 2] / w);
     }
-    float spx, spy; int px, py; lane_sample_pos(sc, rp, lane, &spx, &spy, &px, &py);
-    int n = F.fn, count = F.fcount;
-    int pix = (int) __builtin_floorf(spx) - n, piy = (int) __builtin_floorf(spy) - n;
-    float relx = (float) pix + .5f - spx, rely = (float) piy + .5f - spy;
+    int px, py; lane_to_pixel(sc, rp, lane, &px, &py);
+    float jx, jy; lane_jitter(rp, lane, lane_local_index(rp, lane), jx, jy);
+    const FilmFootprint fp = film_footprint(F, px, py, jx, jy);
+    const int count = F.fcount;
     V3 dL(0.f);
     for (int ys = 0; ys < count; ++ys) {
-        int y = piy - F.crop_offset_y + ys;
+        int y = fp.piy - F.crop_offset_y + ys;
         if (y < 0 || y >= F.height) continue;
-        float wy = rfilter_eval(F, rely + (float) ys);
+        float wy = rfilter_eval(F, fp.rely + (float) ys);
         for (int xs = 0; xs < count; ++xs) {
-            int x = pix - F.crop_offset_x + xs;
+            int x = fp.pix - F.crop_offset_x + xs;
             if (x < 0 || x >= F.width) continue;
             size_t p = (size_t) y * F.width + x;
-            float w = wy * rfilter_eval(F, relx + (float) xs), wp = wfilm[p]; if (wp == 0.f) wp = 1.f;
+            float w = wy * rfilter_eval(F, fp.relx + (float) xs), wp = wfilm[p]; if (wp == 0.f) wp = 1.f;
             float f = w / wp;
             dL = dL + V3(grad_image[p * T] * f, grad_image[p * T + 1] * f, grad_image[p * T + 2] * f);
         }
