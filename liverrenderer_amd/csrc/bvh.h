@@ -26,7 +26,7 @@ struct HostBVH {
 };
 
 // leaf_size: the builder splits until a node holds at most this many triangles (4 by default; the device side asks for fatter
-// leaves when that makes the LDS image of a larger mesh fit: device.hip)
+// leaves when that makes the LDS image of a larger mesh fit: scene_prep.cpp)
 void build_bvh(const float *positions, const uint32_t *faces, uint32_t n_faces, HostBVH &out, int leaf_size = 4);
 
 } // namespace lrt

@@ -1,6 +1,7 @@
 // Host driver of the wavefront renderer: device scene upload, queue management,
-// kernel launches, timing.  Everything device-related lives behind this file so
-// that the rest of the library is plain host C++.
+// kernel launches, timing.  Every HIP runtime call and every kernel lives behind this file.  What a scene's device image holds is
+// computed outside it, by the host-only scene_prep.cpp (arrays, scene record, media tables, resolved options, tile lists, the
+// 64-byte-record predicate); this file uploads that and launches.
 #include "host_scene.h"
 #include "device_scene.h"
 #include "kernels_prb.h"
@@ -9,7 +10,7 @@
 #include "kernels_denoise.h"
 #include "kernels_moment.h"
 #include <functional>
-#include "bvh.h"
+#include "scene_prep.h"
 #include <cmath>
 #include <array>
 #include <cstring>
@@ -132,97 +133,7 @@ struct DeviceScene {
 
 void device_scene_destroy(DeviceScene *d) { delete d; }
 
-static void m4_mul(const float *a, const float *b, float *r) {
-    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) { float s = a[4 * i] * b[j]; for (int k = 1; k < 4; ++k) s = fmaf(a[4 * i + k], b[4 * k + j], s); r[4 * i + j] = s; }
-}
-static void m4_ident(float *m) { for (int i = 0; i < 16; ++i) m[i] = (i % 5 == 0) ? 1.f : 0.f; }
-
-// include/mitsuba/render/sensor.h:234-269 + include/mitsuba/core/transform.h:393-410:
-// sample_to_camera = inverse of (scale * translate * scale * translate * perspective), built
-// from the analytic inverses exactly as Transform::inverse_transpose composes them.
-static void build_camera(const lrt_scene_desc &d, DCamera &cam, DFilm &film) {
-    const lrt_film_desc &F = d.film; const lrt_sensor_desc &C = d.sensor;
-    float fw = (float) F.width, fh = (float) F.height;
-    float rsx = (float) F.crop_width / fw, rsy = (float) F.crop_height / fh, rox = (float) F.crop_offset_x / fw, roy = (float) F.crop_offset_y / fh;
-    float aspect = fw / fh, recip = 1.f / (C.far_clip - C.near_clip);
-    float tn = (float) tan((double) (C.fov_x * .5f) * (3.14159265358979323846 / 180.0));
-    (void) recip;
-    float S1i[16], T1i[16], S2i[16], T2i[16], Pit[16], t0[16], t1[16], t2[16], it[16];
-    m4_ident(S1i); S1i[0] = 1.f / (1.f / rsx); S1i[5] = 1.f / (1.f / rsy); S1i[10] = 1.f / 1.f;
-    m4_ident(T1i); T1i[12] = rox; T1i[13] = roy; T1i[14] = -0.f;
-    m4_ident(S2i); S2i[0] = 1.f / -0.5f; S2i[5] = 1.f / (-0.5f * aspect); S2i[10] = 1.f;
-    m4_ident(T2i); T2i[12] = 1.f; T2i[13] = 1.f / aspect; T2i[14] = -0.f;
-    // inverse of the perspective matrix, transposed
-    float Pinv[16]; m4_ident(Pinv); Pinv[0] = tn; Pinv[5] = tn; Pinv[10] = 0.f; Pinv[15] = 1.f / C.near_clip; Pinv[11] = 1.f;
-    Pinv[14] = (C.near_clip - C.far_clip) / (C.far_clip * C.near_clip);
-    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) Pit[4 * i + j] = Pinv[4 * j + i];
-    m4_mul(S1i, T1i, t0); m4_mul(t0, S2i, t1); m4_mul(t1, T2i, t2); m4_mul(t2, Pit, it);
-    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) cam.s2c[4 * i + j] = it[4 * j + i];
-    memcpy(cam.to_world, C.to_world, sizeof(float) * 12);
-    cam.near_clip = C.near_clip; cam.far_clip = C.far_clip; cam.medium = C.medium;
-    cam.ppo_x = fw * C.principal_point_offset_x / (float) F.crop_width; cam.ppo_y = fh * C.principal_point_offset_y / (float) F.crop_height;
-
-    film.width = F.crop_width; film.height = F.crop_height; film.crop_offset_x = F.crop_offset_x; film.crop_offset_y = F.crop_offset_y;
-    film.scale_x = 1.f / (float) F.crop_width; film.scale_y = 1.f / (float) F.crop_height;
-    film.offset_x = -(float) F.crop_offset_x * film.scale_x; film.offset_y = -(float) F.crop_offset_y * film.scale_y;
-    film.has_alpha = F.has_alpha; film.channels = F.has_alpha ? 5 : 4; film.rfilter = F.rfilter;
-    film.rf_radius = 0.5f; film.rf_inv_radius = 1.f;
-    if (F.rfilter == LRT_RFILTER_GAUSSIAN) {             // src/rfilters/gaussian.cpp:52-95
-        float stddev = F.rfilter_param; film.rf_radius = 4.f * stddev;
-        static const double coeff[10] = { 9.992604880e-1, -4.977025247e-1, 1.222248550e-1, -1.932406282e-2, 2.136713061e-3,
-                                          -1.679873860e-4, 9.202145248e-6, -3.329417433e-7, 7.128382794e-9, -6.821193280e-11 };
-        double sc = 1; for (int i = 0; i < 10; ++i) { film.rf_coeff[i] = (float) (coeff[i] * sc); sc /= (double) stddev * (double) stddev; }
-        float x = film.rf_radius * film.rf_radius, x2 = x * x, x4 = x2 * x2, x8 = x4 * x4; const float *c = film.rf_coeff;
-        float a0 = fmaf(x, c[1], c[0]), a1 = fmaf(x, c[3], c[2]), a2 = fmaf(x, c[5], c[4]), a3 = fmaf(x, c[7], c[6]), a4 = fmaf(x, c[9], c[8]);
-        float b0 = fmaf(x2, a1, a0), b1 = fmaf(x2, a3, a2), c0 = fmaf(x4, b1, b0);
-        film.rf_coeff[0] -= fmaf(x8, a4, c0);
-    } else if (F.rfilter == LRT_RFILTER_TENT) { film.rf_radius = F.rfilter_param; film.rf_inv_radius = 1.f / film.rf_radius; }
-    film.fn = (int) ceilf(film.rf_radius - .5f); film.fcount = 2 * film.fn + 1;
-}
-
-static void inverse3(const float *m16, float *out9) {    // double-precision inverse of the linear part
-    double m[3][3]; for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) m[i][j] = m16[4 * i + j];
-    double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) + m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
-    double id = 1.0 / det;
-    out9[0] = (float) ((m[1][1] * m[2][2] - m[1][2] * m[2][1]) * id); out9[1] = (float) ((m[0][2] * m[2][1] - m[0][1] * m[2][2]) * id); out9[2] = (float) ((m[0][1] * m[1][2] - m[0][2] * m[1][1]) * id);
-    out9[3] = (float) ((m[1][2] * m[2][0] - m[1][0] * m[2][2]) * id); out9[4] = (float) ((m[0][0] * m[2][2] - m[0][2] * m[2][0]) * id); out9[5] = (float) ((m[0][2] * m[1][0] - m[0][0] * m[1][2]) * id);
-    out9[6] = (float) ((m[1][0] * m[2][1] - m[1][1] * m[2][0]) * id); out9[7] = (float) ((m[0][1] * m[2][0] - m[0][0] * m[2][1]) * id); out9[8] = (float) ((m[0][0] * m[1][1] - m[0][1] * m[1][0]) * id);
-}
-
-static uint32_t log2i_ceil(uint32_t v) { uint32_t r = 0; while ((1u << r) < v) ++r; return r; }
-
-// include/mitsuba/core/distr_2d.h:403-510 (normalised, single slice); levels are
-// concatenated with 16-byte aligned offsets so that a 2x2 patch is one float4 load.
-static void build_hierarchy(const std::vector<float> &lum, uint32_t w, uint32_t h, DEnv &E, std::vector<float> &out) {
-    uint32_t npx = w - 1, npy = h - 1;
-    E.patch_size[0] = 1.f / (float) npx; E.patch_size[1] = 1.f / (float) npy;
-    E.inv_patch_size[0] = (float) npx; E.inv_patch_size[1] = (float) npy;
-    E.max_patch[0] = npx - 1; E.max_patch[1] = npy - 1;
-    uint32_t max_level = log2i_ceil(std::max(npx, npy));
-    struct L { uint32_t w, h, off; };
-    std::vector<L> lv; uint32_t total = 0;
-    auto add = [&](uint32_t lw, uint32_t lh) { lv.push_back({ lw, lh, total }); total += (lw * lh + 3u) & ~3u; };
-    add(w, h);
-    uint32_t lx = npx, ly = npy;
-    for (int level = (int) max_level; level >= 0; --level) { lx += lx & 1u; ly += ly & 1u; add(lx, ly); lx >>= 1; ly >>= 1; }
-    if (lv.size() > LRT_MAX_HIER_LEVELS) throw std::runtime_error("environment map too large for the sampling hierarchy");
-    out.assign(total, 0.f);
-    auto index = [](uint32_t x, uint32_t y, uint32_t width) { return ((x & 1u) | (((x & ~1u) | (y & 1u)) << 1)) + ((y & ~1u) * width); };
-    float *l0 = &out[lv[0].off], *l1 = &out[lv[1].off];
-    const float *in = lum.data(); double sum = 0.0;
-    for (uint32_t y = 0; y < npy; ++y) { for (uint32_t x = 0; x < npx; ++x) { float avg = .25f * (in[0] + in[1] + in[w] + in[w + 1]); sum += (double) avg; l1[index(x, y, lv[1].w)] = avg; ++in; } ++in; }
-    float scale = (float) ((double) (npx * npy) / sum);
-    for (uint32_t i = 0; i < w * h; ++i) l0[i] = lum[i] * scale;
-    for (uint32_t i = 0; i < lv[1].w * lv[1].h; ++i) l1[i] *= scale;
-    lx = npx; ly = npy;
-    for (uint32_t level = 2; level <= max_level + 1; ++level) {
-        const float *a = &out[lv[level - 1].off]; float *b = &out[lv[level].off];
-        lx = (lx + 1u) >> 1; ly = (ly + 1u) >> 1;
-        for (uint32_t y = 0; y < ly; ++y) for (uint32_t x = 0; x < lx; ++x) { const float *d0 = a + index(x * 2, y * 2, lv[level - 1].w); b[index(x, y, lv[level].w)] = d0[0] + d0[1] + d0[2] + d0[3]; }
-    }
-    E.n_levels = (int) lv.size();
-    for (size_t i = 0; i < lv.size(); ++i) { E.level_offset[i] = lv[i].off; E.level_width[i] = lv[i].w; }
-}
+static_assert(PREP_F_DELTA == F_DELTA && PREP_F_SMOOTH == F_SMOOTH && PREP_F_NULL == F_NULL, "scene_prep.h restates the BSDF leaf flags of dshade.h");
 
 // log10 of the hepatocyte coefficient with the device's own arithmetic (liver.cpp:376 `dr::log2(att + 1) / dr::log2(10)`)
 __global__ void k_bio_prepare(DBioMedium *bio, uint32_t n) {
@@ -241,47 +152,13 @@ __global__ void k_medium_prepare(DMedium *media, uint32_t n) {
     M.w_spec[0] = ws.x; M.w_spec[1] = ws.y; M.w_spec[2] = ws.z; M.w_plain[0] = wp.x; M.w_plain[1] = wp.y; M.w_plain[2] = wp.z;
 }
 
+// The media tables of prepare_media, with the grids' device pointers, and the two kernels that finish them with the device's arithmetic
 static void upload_media(DeviceScene *D, const lrt_scene_desc &d) {
-    D->h_bio.assign(std::max<uint32_t>(d.n_media, 1), DBioMedium{});
-    for (uint32_t i = 0; i < d.n_media; ++i) {
-        const lrt_medium_desc &M = d.media[i]; DBioMedium &o = D->h_bio[i];
-        o.type = M.type; o.has_spectral_extinction = M.has_spectral_extinction;
-        for (int l = 0; l < 4; ++l) { o.layer_limit[l] = M.layer_limit[l]; for (int k = 0; k < 3; ++k) { o.collagen[l][k] = M.sigma_collagen[l][k]; o.elastin[l][k] = M.sigma_elastin[l][k]; } }
-        for (int k = 0; k < 3; ++k) { o.blood[k] = M.sigma_blood[k]; o.bile[k] = M.sigma_bile[k]; o.lipid_water[k] = M.sigma_lipid_water[k]; }
-        o.hepatocity = M.sigma_hepatocity; o.log10_hep = 0.f;
-        if (M.type == LRT_MEDIUM_PARENCHYMA) { o.sigmat[0] = 77.2f / 255; o.sigmat[1] = 105.0f / 255; o.sigmat[2] = 149.0f / 255; }   // parenchyma.cpp:165
-        else for (int k = 0; k < 3; ++k) o.sigmat[k] = M.sigma_t[k] * M.scale;                                                       // liver.cpp:204-209
-    }
+    prepare_media(d, D->sc.env.bsphere_r, D->h_media, D->h_bio, D->h_het);
+    for (size_t i = 0; i < D->h_het.size(); ++i) D->h_het[i].data = D->het_data[i];
     HIP_CHECK(hipMemcpyAsync(D->d_bio, D->h_bio.data(), D->h_bio.size() * sizeof(DBioMedium), hipMemcpyHostToDevice, D->stream));
     k_bio_prepare<<<1, 64, 0, D->stream>>>(D->d_bio, (uint32_t) std::min<size_t>(D->h_bio.size(), 64));
     HIP_CHECK(hipGetLastError());
-    D->h_media.resize(std::max<uint32_t>(d.n_media, 1));
-    for (uint32_t i = 0; i < d.n_media; ++i) {
-        const lrt_medium_desc &M = d.media[i]; DMedium &o = D->h_media[i];
-        for (int k = 0; k < 3; ++k) { o.sigma_t[k] = M.sigma_t[k] * M.scale; o.albedo[k] = M.albedo[k]; }   // homogeneous.cpp:121-126 eval_sigmat
-        o.has_spectral_extinction = M.has_spectral_extinction; o.sample_emitters = M.sample_emitters; o.phase = M.phase; o.g = M.g;
-        o.scale = M.scale; o.het = M.type == LRT_MEDIUM_HETEROGENEOUS ? 1 : 0;
-        // Early NEE rejection (volpath_iteration): an infinite emitter's sample lies at distance >= 2 r (r: the scene's bounding sphere); the
-        // kernel rejects when -log(1 - u) / sigma_t <= bound(dist), bound(x) = x * 0.998f - 1e-3f (monotone in x).  1 - u >= vmin implies that
-        // for dist = 2 r, hence for every sample: vmin = exp(-sigma_t bound(2 r) (1 - 1e-4)) (1 + 1e-4), far outside the 3e-7 relative error
-        // of the kernels' logarithm and the rounding of the division; 2 (never true) when sigma_t bound is too small for the margin to mean anything.
-        const float bound = (2.f * D->sc.env.bsphere_r) * 0.998f - 1e-3f;
-        for (int k = 0; k < 3; ++k) {
-            const double x = (double) o.sigma_t[k] * (double) bound;
-            double v = (x > 0.05 && std::isfinite(x)) ? std::exp(-x * (1.0 - 1e-4)) * (1.0 + 1e-4) : 2.0;
-            float vf = (float) v; if ((double) vf < v) vf = std::nextafter(vf, 3.f);
-            o.nee_vmin[k] = vf;
-        }
-    }
-    D->h_het.assign(std::max<uint32_t>(d.n_media, 1), DHetMedium{});
-    for (uint32_t i = 0; i < d.n_media; ++i) {
-        const lrt_medium_desc &M = d.media[i]; DHetMedium &o = D->h_het[i];
-        if (M.type != LRT_MEDIUM_HETEROGENEOUS) continue;
-        o.data = D->het_data[i];
-        for (int k = 0; k < 3; ++k) { o.res[k] = M.grid_res[k]; o.bbox_min[k] = M.grid_bbox_min[k]; o.bbox_max[k] = M.grid_bbox_max[k]; }
-        for (int k = 0; k < 12; ++k) o.to_local[k] = M.grid_to_local[k];
-        o.scale = M.scale; o.max_density = M.scale * M.grid_max;                    // heterogeneous.cpp:164,171
-    }
     HIP_CHECK(hipMemcpyAsync(D->d_het, D->h_het.data(), D->h_het.size() * sizeof(DHetMedium), hipMemcpyHostToDevice, D->stream));
     HIP_CHECK(hipMemcpyAsync(D->d_media, D->h_media.data(), D->h_media.size() * sizeof(DMedium), hipMemcpyHostToDevice, D->stream));
     k_medium_prepare<<<1, 64, 0, D->stream>>>(D->d_media, (uint32_t) std::min<size_t>(D->h_media.size(), 64));
@@ -382,276 +259,71 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
     D->device = device;
     HIP_CHECK(hipStreamCreateWithFlags(&D->stream, hipStreamNonBlocking));
     hipStream_t st = D->stream;
-    DScene &sc = D->sc;
-    // ---- acceleration structure
-    // LDS a workgroup may ask for: the device's opt-in maximum (160 KiB on gfx950), minus the kernel's static __shared__ words
-    hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, device)); D->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    // ---- the device: compute units, and the LDS a workgroup may ask for: the opt-in maximum (160 KiB on gfx950), minus the kernel's static __shared__ words
+    PrepOptions opt = PrepOptions::from_env();
+    hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, device)); opt.n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     int optin = 0; if (hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, device) != hipSuccess || optin <= 0) optin = (int) prop.sharedMemPerBlock;
     (void) hipGetLastError();
-    const size_t lds_limit = std::min<size_t>((size_t) std::max(optin, 0), 160 * 1024) - 512;
-    // bytes of the LDS image of a BVH: nodes, float4 vertices, 8-byte triangle slots, 16-bit traversal stacks of 1024 threads
-    auto lds_image_bytes = [&](const HostBVH &b) {
-        const size_t nodes_b = b.nodes.size() / 16 * 64, verts_b = ((size_t) d.n_vertices * 16 + 15) & ~size_t(15), tris_b = (b.tris.size() / 12 * 8 + 15) & ~size_t(15);
-        return nodes_b + verts_b + tris_b + (size_t) 2 * (b.max_depth + 2) * 1024;
-    };
-    // Leaf size: the smallest of 2, 3, 4, 6, 8, 12, 16 triangles whose BVH image fits the LDS next to the traversal stacks (fatter
-    // leaves = fewer nodes: more triangle tests per leaf, but every fetch of the traversal stays in LDS; Liver-MultiMesh's two meshes
-    // run 44 % faster with 8-triangle leaves in LDS than with 4-triangle leaves in global memory); 4 when nothing fits.
-    // LRT_BVH_LEAF=n forces a size.
-    // ---- sphere shapes (src/shapes/sphere.cpp:146-165): centre, radius and the inverse transform, outside the triangle BVH
-    std::vector<DSphere> spheres;
-    for (uint32_t i = 0; i < d.n_shapes; ++i) {
-        const lrt_shape_desc &s = d.shapes[i];
-        if (s.kind != LRT_SHAPE_SPHERE) continue;
-        DSphere o; memset(&o, 0, sizeof(o));
-        const float *m = s.to_world;
-        for (int a = 0; a < 3; ++a) o.center[a] = m[4 * a + 3];                       // to_world * (0, 0, 0)
-        o.radius = sqrtf(fmaf(m[8], m[8], fmaf(m[4], m[4], m[0] * m[0])));           // |to_world * (1, 0, 0)|
-        for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) o.to_world[3 * a + b] = m[4 * a + b];
-        double md[16]; for (int k = 0; k < 16; ++k) md[k] = m[k];
-        const double c00 = md[5] * md[10] - md[6] * md[9], c01 = md[6] * md[8] - md[4] * md[10], c02 = md[4] * md[9] - md[5] * md[8];
-        const double id = 1.0 / (md[0] * c00 + md[1] * c01 + md[2] * c02);
-        double inv[12] = { c00 * id, (md[2] * md[9] - md[1] * md[10]) * id, (md[1] * md[6] - md[2] * md[5]) * id, 0,
-                           c01 * id, (md[0] * md[10] - md[2] * md[8]) * id, (md[2] * md[4] - md[0] * md[6]) * id, 0,
-                           c02 * id, (md[1] * md[8] - md[0] * md[9]) * id, (md[0] * md[5] - md[1] * md[4]) * id, 0 };
-        for (int a = 0; a < 3; ++a) inv[4 * a + 3] = -(inv[4 * a] * md[3] + inv[4 * a + 1] * md[7] + inv[4 * a + 2] * md[11]);
-        for (int k = 0; k < 12; ++k) o.to_object[k] = (float) inv[k];
-        o.shape = i; o.flip_normals = s.flip_normals;
-        if (!(o.radius > 0.f) || !std::isfinite(o.radius)) throw std::runtime_error("sphere with a zero or invalid radius");
-        spheres.push_back(o);
-    }
-    sc.n_spheres = (uint32_t) spheres.size();
-    sc.spheres = spheres.empty() ? nullptr : D->track(dev_upload(spheres.data(), spheres.size(), st));
-    for (uint32_t i = 0; i < d.n_emitters; ++i) {
-        const lrt_emitter_desc &e = d.emitters[i];
-        if (e.type == LRT_EMITTER_POINT || (e.type == LRT_EMITTER_AREA && e.shape >= 0 && (uint32_t) e.shape < d.n_shapes && d.shapes[e.shape].kind == LRT_SHAPE_MESH)) D->ext = true;
-    }
-    if (!spheres.empty()) D->ext = true;
-    HostBVH bvh;
-    {
-        const int forced = getenv("LRT_BVH_LEAF") ? std::max(1, atoi(getenv("LRT_BVH_LEAF"))) : 0;
-        const bool lds_possible = d.n_faces > 0 && d.n_faces <= 32767 && d.n_vertices <= 65535 && !getenv("LRT_NO_LDS_BVH");
-        int chosen = forced ? forced : 4;
-        bool done = false;
-        if (!forced && lds_possible) {                     // the thinnest leaves whose image still fits (measured: 3 beats 4 by 1 % on the liver; 2 does not fit there)
-            for (int leaf : { 2, 3, 4, 6, 8, 12, 16 }) {
-                HostBVH b2; build_bvh(d.positions, d.faces, d.n_faces, b2, leaf);
-                if (lds_image_bytes(b2) <= lds_limit && b2.nodes.size() / 16 <= 32767 && b2.tris.size() / 12 <= 32767) { bvh = std::move(b2); chosen = leaf; done = true; break; }
-            }
+    opt.lds_limit = std::min<size_t>((size_t) std::max(optin, 0), 160 * 1024) - 512;
+    // ---- the scene's image on the host (scene_prep.cpp), in prepare_scene's two halves: the distance field is built on the device while the host
+    // prepares the rest.  P outlives the copies below (the synchronize at the end); the device pointers are patched into its scene record.
+    PreparedScene P; DScene &sc = P.sc;
+    prepare_geometry(d, opt, P);
+    D->n_cus = opt.n_cus; D->bvh_leaf = P.bvh_leaf; D->ext = P.ext;
+    auto up = [&](const auto &v) { return D->track(dev_upload(v.data(), v.size(), st)); };
+    sc.spheres = P.spheres.empty() ? nullptr : up(P.spheres);
+    sc.nodes = (const float4 *) up(P.bvh.nodes);
+    sc.tris = (const float4 *) up(P.bvh.tris);
+    if (P.use_lds) {                                   // the LDS image: the kernels that copy it may ask for the whole limit
+        D->lds = P.lds; D->lds.blob = (const uint4 *) up(P.lds_blob);
+        const size_t lds_limit = opt.lds_limit;
+        auto raise_lds = [&](const void *k) { if (k) HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_limit)); };
+        const KernelTable &K = kernels();
+        for (const RenderRow &r : K.render) if (r.lds && (!r.ext || D->ext)) raise_lds((const void *) r.fn);     // (the EXT instances: scenes with spheres / point emitters / mesh emitters only)
+        for (const auto &adjoint : K.prb) for (const auto &ld : adjoint[1]) for (RenderFn fn : ld) raise_lds((const void *) fn);
+        for (RenderFn fn : K.prb_grid[1]) raise_lds((const void *) fn);
+        for (int i = 0; i < 2; ++i) for (int ext = 0; ext <= (D->ext ? 1 : 0); ++ext) {            // (i: k_aov's LD, k_trace_lds's ANY_HIT)
+            raise_lds((const void *) aov_kernel(true, i, ext)); raise_lds((const void *) trace_lds_kernel(i, ext));
         }
-        if (!done) build_bvh(d.positions, d.faces, d.n_faces, bvh, chosen);
-        D->bvh_leaf = chosen;
+        D->use_lds = true;
     }
-    sc.nodes = (const float4 *) D->track(dev_upload(bvh.nodes.data(), bvh.nodes.size(), st));
-    sc.tris = (const float4 *) D->track(dev_upload(bvh.tris.data(), bvh.tris.size(), st));
-    sc.root_is_leaf = bvh.root_is_leaf; sc.root_leaf_first = bvh.root_first; sc.root_leaf_count = bvh.root_count;
-    sc.n_faces = d.n_faces; sc.n_emitters = d.n_emitters; sc.one_shape = d.n_shapes == 1;
-    // ---- LDS image of the acceleration structure (persistent kernel): used when it fits next to the traversal stacks
-    {
-        const size_t n_nodes = bvh.nodes.size() / 16, n_slots = bvh.tris.size() / 12, n_verts = d.n_vertices;
-        const size_t nodes_b = n_nodes * 64, verts_b = (n_verts * 16 + 15) & ~size_t(15), tris_b = (n_slots * 8 + 15) & ~size_t(15);
-        const size_t total = lds_image_bytes(bvh);                   // the per-lane stacks hold max_depth + 2 entries
-        if (d.n_faces > 0 && d.n_faces <= 32767 && n_verts <= 65535 && n_nodes <= 32767 && n_slots <= 32767 && total <= lds_limit && !getenv("LRT_NO_LDS_BVH")) {
-            std::vector<unsigned char> blob(nodes_b + verts_b + tris_b, 0);
-            memcpy(blob.data(), bvh.nodes.data(), nodes_b);
-            float *v = reinterpret_cast<float *>(blob.data() + nodes_b);
-            for (size_t i = 0; i < n_verts; ++i) { v[4 * i] = d.positions[3 * i]; v[4 * i + 1] = d.positions[3 * i + 1]; v[4 * i + 2] = d.positions[3 * i + 2]; v[4 * i + 3] = 0.f; }
-            uint16_t *t = reinterpret_cast<uint16_t *>(blob.data() + nodes_b + verts_b);
-            for (size_t sl = 0; sl < n_slots; ++sl) {               // 4th word: face index << 1 | "last slot of its leaf"
-                uint32_t f; memcpy(&f, &bvh.tris[12 * sl + 3], 4);
-                for (int k = 0; k < 3; ++k) t[4 * sl + k] = (uint16_t) d.faces[3 * (size_t) f + k];
-                t[4 * sl + 3] = (uint16_t) (f << 1);
-            }
-            for (size_t n = 0; n < n_nodes; ++n) {                 // mark the last slot of every leaf (trace_lds)
-                int32_t refs[4]; memcpy(refs, &bvh.nodes[16 * n + 12], 16);
-                for (int c = 0; c < 2; ++c) if (refs[c] < 0 && refs[2 + c] > 0) t[4 * ((size_t) (uint32_t) ~refs[c] + (size_t) refs[2 + c] - 1) + 3] |= 1;
-                // child references as trace_lds's 16-bit work items (inner node index, or 0x8000 | first slot of the leaf)
-                uint32_t enc[2]; for (int c = 0; c < 2; ++c) enc[c] = refs[c] < 0 ? (0x8000u | (uint32_t) ~refs[c]) : (uint32_t) refs[c];
-                memcpy(blob.data() + 64 * n + 48, enc, 8);
-            }
-            D->lds.blob = (const uint4 *) D->track(dev_upload(blob.data(), blob.size(), st));
-            D->lds.blob_bytes = (uint32_t) blob.size(); D->lds.nodes_off = 0; D->lds.verts_off = (uint32_t) nodes_b; D->lds.tris_off = (uint32_t) (nodes_b + verts_b);
-            D->lds.stack_off = (uint32_t) blob.size(); D->lds.total_bytes = (uint32_t) total;
-            auto raise_lds = [&](const void *k) { if (k) HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_limit)); };
-            const KernelTable &K = kernels();
-            for (const RenderRow &r : K.render) if (r.lds && (!r.ext || D->ext)) raise_lds((const void *) r.fn);     // (the EXT instances: scenes with spheres / point emitters / mesh emitters only)
-            for (const auto &adjoint : K.prb) for (const auto &ld : adjoint[1]) for (RenderFn fn : ld) raise_lds((const void *) fn);
-            for (RenderFn fn : K.prb_grid[1]) raise_lds((const void *) fn);
-            for (int i = 0; i < 2; ++i) for (int ext = 0; ext <= (D->ext ? 1 : 0); ++ext) {            // (i: k_aov's LD, k_trace_lds's ANY_HIT)
-                raise_lds((const void *) aov_kernel(true, i, ext)); raise_lds((const void *) trace_lds_kernel(i, ext));
-            }
-            D->use_lds = true;
-        }
+    if (sc.grid.enabled) {                             // the conservative distance field over the slots and spheres just uploaded
+        const size_t n_cells = (size_t) sc.grid.n[0] * sc.grid.n[1] * sc.grid.n[2];
+        uint16_t *buf = nullptr; HIP_CHECK(hipMalloc((void **) &buf, n_cells * sizeof(uint16_t))); D->track(buf);
+        k_build_dist_grid<<<(uint32_t) ((n_cells + LRT_BLOCK - 1) / LRT_BLOCK), LRT_BLOCK, 0, st>>>(sc.tris, d.n_faces ? (uint32_t) (P.bvh.tris.size() / 12) : 0u, sc.grid, buf, P.grid_abs_margin,
+                                                                                             sc.spheres, sc.n_spheres);
+        HIP_CHECK(hipGetLastError());
+        sc.grid.d = buf;
     }
-    // ---- conservative distance field (scenes with participating media: short free-flight segments deep inside a
-    // volume are proven surface-free with one lookup instead of a BVH traversal)
-    sc.grid = DDistGrid{};
-    // Spheres are surfaces too: their exact distance | |p - c| - r | joins the field's minimum and their bounds the grid's
-    // (k_build_dist_grid), or every medium trip inside a sphere would prove its way through the sphere's surface.
-    if (d.n_media > 0 && (d.n_faces > 0 || !spheres.empty()) && d.n_faces <= (1u << 17) && !getenv("LRT_NO_DIST_GRID")) {
-        float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-        for (uint32_t f = 0; f < 3 * d.n_faces; ++f) for (int a = 0; a < 3; ++a) { float v = d.positions[3 * (size_t) d.faces[f] + a]; lo[a] = std::min(lo[a], v); hi[a] = std::max(hi[a], v); }
-        for (const DSphere &o : spheres) for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], o.center[a] - o.radius); hi[a] = std::max(hi[a], o.center[a] + o.radius); }
-        const float ext = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
-        const int res = getenv("LRT_DIST_GRID_RES") ? std::max(8, std::min(256, atoi(getenv("LRT_DIST_GRID_RES")))) : (d.n_faces <= (1u << 14) ? 192 : 64);
-        if (ext > 0.f && std::isfinite(ext)) {
-            DDistGrid g{};
-            g.cell = ext / (float) res; g.inv_cell = 1.f / g.cell;
-            for (int a = 0; a < 3; ++a) { g.lo[a] = lo[a]; g.n[a] = std::max(1, std::min(res, (int) std::ceil((hi[a] - lo[a]) / g.cell))); }
-            const size_t n_cells = (size_t) g.n[0] * g.n[1] * g.n[2];
-            uint16_t *buf = nullptr; HIP_CHECK(hipMalloc((void **) &buf, n_cells * sizeof(uint16_t))); D->track(buf);
-            float diag = std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
-            float amax = 0.f; for (int a = 0; a < 3; ++a) amax = std::max(amax, std::max(std::fabs(lo[a]), std::fabs(hi[a])));
-            const float abs_margin = 1e-4f * diag + 1e-5f * amax;          // >> f32 rounding of positions and of the field itself
-            k_build_dist_grid<<<(uint32_t) ((n_cells + LRT_BLOCK - 1) / LRT_BLOCK), LRT_BLOCK, 0, st>>>(sc.tris, d.n_faces ? (uint32_t) (bvh.tris.size() / 12) : 0u, g, buf, abs_margin,
-                                                                                                 sc.spheres, sc.n_spheres);
-            HIP_CHECK(hipGetLastError());
-            g.d = buf; g.enabled = 1; sc.grid = g;
-        }
-    }
-    // ---- geometry attributes
+    prepare_shading(d, opt, P);
+    D->has_area_emitter = P.has_area_emitter; D->has_het = P.has_het; D->has_non_bio = P.has_non_bio; D->prb_null = P.prb_null;
     sc.positions = D->track(dev_upload(d.positions, 3 * (size_t) d.n_vertices, st));
-    {
-        std::vector<float> va(8 * (size_t) d.n_vertices, 0.f);
-        for (size_t v = 0; v < d.n_vertices; ++v) {
-            if (d.normals) for (int a = 0; a < 3; ++a) va[8 * v + a] = d.normals[3 * v + a];
-            if (d.texcoords) for (int a = 0; a < 2; ++a) va[8 * v + 4 + a] = d.texcoords[2 * v + a];
-        }
-        sc.vattr = (const float4 *) D->track(dev_upload(va.data(), va.size(), st));
-    }
+    sc.vattr = (const float4 *) up(P.vattr);
     sc.faces = D->track(dev_upload(d.faces, 3 * (size_t) d.n_faces, st));
     sc.face_shape = D->track(dev_upload(d.face_shape, d.n_faces, st));
-    std::vector<DShape> shapes(d.n_shapes);
-    for (uint32_t i = 0; i < d.n_shapes; ++i) { const lrt_shape_desc &s = d.shapes[i]; shapes[i] = { s.bsdf, s.emitter, s.interior_medium, s.exterior_medium, s.has_normals, s.has_texcoords, s.flip_normals, s.kind }; }
-    sc.shapes = D->track(dev_upload(shapes.data(), shapes.size(), st));
-    // ---- textures (bitmaps: one luminance float per texel, src/textures/bitmap.cpp:540-552)
-    std::vector<DTexture> tex(d.n_textures); std::vector<float> tex_data;
-    for (uint32_t i = 0; i < d.n_textures; ++i) {
-        const lrt_texture_desc &T = d.textures[i]; DTexture &o = tex[i]; memset(&o, 0, sizeof(o));
-        o.type = T.type; o.width = T.width; o.height = T.height; o.channels = T.channels;
-        for (int k = 0; k < 3; ++k) { o.color0[k] = T.color0[k]; o.color1[k] = T.color1[k]; }
-        for (int k = 0; k < 6; ++k) o.to_uv[k] = T.to_uv[k];
-        if (T.type == LRT_TEX_BITMAP) {
-            o.data_offset = (uint32_t) tex_data.size();
-            size_t np = (size_t) T.width * T.height;
-            for (size_t p = 0; p < np; ++p) {
-                const float *px = T.data + p * T.channels;
-                tex_data.push_back(T.channels == 1 ? px[0] : px[0] * 0.212671f + px[1] * 0.715160f + px[2] * 0.072169f);
-            }
-        }
-    }
-    sc.textures = D->track(dev_upload(tex.data(), tex.size(), st));
-    sc.tex_data = D->track(dev_upload(tex_data.data(), tex_data.size(), st));
-    // ---- BSDFs
-    std::vector<DBsdf> bsdfs(d.n_bsdfs); sc.has_null_bsdf = 0;
-    auto leaf_flags = [](int type) { return type == LRT_BSDF_DIFFUSE ? F_SMOOTH : type == LRT_BSDF_DIELECTRIC ? F_DELTA : F_NULL; };
-    for (uint32_t i = 0; i < d.n_bsdfs; ++i) {
-        const lrt_bsdf_desc &B = d.bsdfs[i];
-        bsdfs[i] = { B.type, B.reflectance, B.nested, B.texture, B.eta, B.scale, 0, 0 };
-        if (B.type == LRT_BSDF_BUMPMAP) {
-            if (B.nested < 0 || (uint32_t) B.nested >= d.n_bsdfs || d.bsdfs[B.nested].type == LRT_BSDF_BUMPMAP) throw std::runtime_error("bumpmap: invalid nested BSDF");
-            bsdfs[i].flags = leaf_flags(d.bsdfs[B.nested].type);
-        } else bsdfs[i].flags = leaf_flags(B.type);
-        if (B.type == LRT_BSDF_DIFFUSE && (B.reflectance < 0 || (uint32_t) B.reflectance >= d.n_textures || d.textures[B.reflectance].type == LRT_TEX_BITMAP))
-            throw std::runtime_error("unsupported: a bitmap texture as diffuse reflectance (bitmaps are supported as bump-map heights only)");
-        if (B.type == LRT_BSDF_NULL) sc.has_null_bsdf = 1;
-    }
-    sc.bsdfs = D->track(dev_upload(bsdfs.data(), bsdfs.size(), st));
-    // ---- bounds (src/render/scene.cpp:49; include/mitsuba/core/bbox.h:343-346; envmap.cpp:337-351)
-    DEnv &E = sc.env; memset(&E, 0, sizeof(E)); E.type = -1; E.emitter = -1;
-    {
-        float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-        for (uint32_t i = 0; i < d.n_vertices; ++i) for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], d.positions[3 * i + a]); hi[a] = fmaxf(hi[a], d.positions[3 * i + a]); }
-        for (const DSphere &o : spheres) for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], o.center[a] - o.radius); hi[a] = fmaxf(hi[a], o.center[a] + o.radius); }   // Sphere::bbox
-        const float ray_eps = 5.9604644775390625e-8f * 1500.f;
-        if (d.n_vertices || !spheres.empty()) {
-            float c[3], dd[3]; for (int a = 0; a < 3; ++a) { c[a] = (hi[a] + lo[a]) * 0.5f; dd[a] = c[a] - hi[a]; E.bsphere_c[a] = c[a]; }
-            float r = sqrtf(fmaf(dd[2], dd[2], fmaf(dd[1], dd[1], dd[0] * dd[0])));
-            E.bsphere_r = fmaxf(ray_eps, r * (1.f + ray_eps));
-        } else { E.bsphere_c[0] = E.bsphere_c[1] = E.bsphere_c[2] = 0.f; E.bsphere_r = ray_eps; }
-    }
-    // ---- media
+    sc.shapes = up(P.shapes);
+    sc.textures = up(P.textures);
+    sc.tex_data = up(P.tex_data);
+    sc.bsdfs = up(P.bsdfs);
+    // ---- media: the tables are filled by upload_media, here and again after every parameter update
     HIP_CHECK(hipMalloc((void **) &D->d_media, std::max<uint32_t>(d.n_media, 1) * sizeof(DMedium))); D->track(D->d_media);
     HIP_CHECK(hipMalloc((void **) &D->d_bio, std::max<uint32_t>(d.n_media, 1) * sizeof(DBioMedium))); D->track(D->d_bio);
-    if (d.n_media > 64) throw std::runtime_error("at most 64 media are supported");
     HIP_CHECK(hipMalloc((void **) &D->d_het, std::max<uint32_t>(d.n_media, 1) * sizeof(DHetMedium))); D->track(D->d_het);
     D->het_data.assign(std::max<uint32_t>(d.n_media, 1), nullptr);
     for (uint32_t i = 0; i < d.n_media; ++i) {
         const lrt_medium_desc &M = d.media[i];
-        if (M.type == LRT_MEDIUM_HOMOGENEOUS || M.type == LRT_MEDIUM_HETEROGENEOUS) D->has_non_bio = true;
-        if (M.type != LRT_MEDIUM_HETEROGENEOUS) continue;
-        if (!M.grid_data || M.grid_res[0] < 1 || M.grid_res[1] < 1 || M.grid_res[2] < 1 || !(M.grid_max > 0.f)) throw std::runtime_error("heterogeneous medium without a valid grid");
-        D->het_data[i] = D->track(dev_upload(M.grid_data, (size_t) M.grid_res[0] * M.grid_res[1] * M.grid_res[2], st));
-        D->has_het = true;
+        if (M.type == LRT_MEDIUM_HETEROGENEOUS) D->het_data[i] = D->track(dev_upload(M.grid_data, (size_t) M.grid_res[0] * M.grid_res[1] * M.grid_res[2], st));
     }
-    for (uint32_t i = 0; i < d.n_shapes; ++i) for (int m : { d.shapes[i].interior_medium, d.shapes[i].exterior_medium })
-        if (m >= 0 && d.media[m].type == LRT_MEDIUM_HETEROGENEOUS) D->prb_null = true;
+    D->sc = sc;                                        // (upload_media reads the bounding sphere there)
     upload_media(D.get(), d); sc.media = D->d_media; sc.bio = D->d_bio; sc.het = D->d_het;
-    // ---- emitters
-    std::vector<DEmitter> em(d.n_emitters); std::vector<float> env_rgbx, hier; bool env_interior_positive = false;
-    std::vector<DMeshEmitter> mesh_em(d.n_emitters); std::vector<float> mesh_tab;      // (all zero: no mesh emitter)
-    for (uint32_t i = 0; i < d.n_emitters; ++i) {
-        const lrt_emitter_desc &S = d.emitters[i]; DEmitter &o = em[i]; memset(&o, 0, sizeof(o));
-        o.type = S.type; o.shape = S.shape; o.scale = S.scale; for (int k = 0; k < 3; ++k) o.radiance[k] = S.radiance[k];
-        if (S.type == LRT_EMITTER_AREA) {
-            D->has_area_emitter = true;
-            const lrt_shape_desc &sd = d.shapes[S.shape];
-            if (sd.kind == LRT_SHAPE_SPHERE) throw std::runtime_error("unsupported: an area emitter on a sphere (area emitters are supported on rectangles and triangle meshes)");
-            if (sd.kind == LRT_SHAPE_MESH) {                   // src/render/mesh.cpp:449-482: the area table and its CDF (host_scene.h)
-                MeshEmitterTable T; mesh_emitter_table(d.positions, d.faces, sd.first_face, sd.n_faces, "shapes[" + std::to_string(S.shape) + "]", T);
-                DMeshEmitter &M = mesh_em[i];
-                M.first_face = sd.first_face; M.n_faces = sd.n_faces; M.sum = T.sum; M.normalization = T.normalization;
-                M.has_normals = sd.has_normals; M.flip_normals = sd.flip_normals; M.mesh = 1;
-                M.pmf_offset = (uint32_t) mesh_tab.size(); mesh_tab.insert(mesh_tab.end(), T.pmf.begin(), T.pmf.end());
-                M.cdf_offset = (uint32_t) mesh_tab.size(); mesh_tab.insert(mesh_tab.end(), T.cdf.begin(), T.cdf.end());
-                continue;
-            }
-            memcpy(o.to_world, sd.to_world, sizeof(float) * 12);
-            auto xv = [&](float x, float y, float z, float *r) { const float *m = sd.to_world; for (int a = 0; a < 3; ++a) r[a] = fmaf(m[4 * a + 2], z, fmaf(m[4 * a + 1], y, m[4 * a] * x)); };
-            float du[3], dv[3]; xv(2.f, 0.f, 0.f, du); xv(0.f, 2.f, 0.f, dv);
-            float cx = fmaf(du[1], dv[2], -(du[2] * dv[1])), cy = fmaf(du[2], dv[0], -(du[0] * dv[2])), cz = fmaf(du[0], dv[1], -(du[1] * dv[0]));
-            o.inv_area = 1.f / sqrtf(fmaf(cz, cz, fmaf(cy, cy, cx * cx)));
-            uint32_t v0 = d.faces[3 * sd.first_face];
-            for (int a = 0; a < 3; ++a) o.n[a] = sd.flip_normals ? -d.normals[3 * v0 + a] : d.normals[3 * v0 + a];
-        } else if (S.type == LRT_EMITTER_POINT) {             // src/emitters/point.cpp: position and intensity (radiance[])
-            memcpy(o.to_world, S.to_world, sizeof(float) * 12);
-        } else {
-            E.type = S.type; E.emitter = (int) i; E.scale = S.scale; for (int k = 0; k < 3; ++k) E.radiance[k] = S.radiance[k];
-            if (S.type == LRT_EMITTER_ENVMAP) {             // src/emitters/envmap.cpp:139-236
-                uint32_t w = (uint32_t) S.width, h = (uint32_t) S.height; E.w = w + 1; E.h = h;
-                env_rgbx.assign((size_t) E.w * h * 4, 0.f); std::vector<float> lum((size_t) E.w * h);
-                float theta_scale = 1.f / (float) (h - 1) * 3.14159265358979323846f;
-                const float *in = S.data;
-                for (uint32_t y = 0; y < h; ++y) {
-                    float sin_theta = (float) sin((double) ((float) y * theta_scale));
-                    for (uint32_t x = 0; x < w; ++x) {
-                        float l = fmaxf((in[0] * 0.212671f + in[1] * 0.715160f + in[2] * 0.072169f) - 0.f, 0.f);
-                        lum[(size_t) y * E.w + x] = l * sin_theta;
-                        float *o4 = &env_rgbx[((size_t) y * E.w + x) * 4]; o4[0] = in[0]; o4[1] = in[1]; o4[2] = in[2];
-                        in += 3;
-                    }
-                    lum[(size_t) y * E.w + w] = lum[(size_t) y * E.w];
-                    for (int k = 0; k < 3; ++k) env_rgbx[((size_t) y * E.w + w) * 4 + k] = env_rgbx[((size_t) y * E.w) * 4 + k];
-                }
-                build_hierarchy(lum, E.w, h, E, hier);
-                env_interior_positive = true;          // rows 1..h-2 of the sampling density strictly positive?
-                for (uint32_t y = 1; y + 1 < h && env_interior_positive; ++y)
-                    for (uint32_t x = 0; x < E.w; ++x) if (!(lum[(size_t) y * E.w + x] > 0.f)) { env_interior_positive = false; break; }
-                for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) E.to_world[3 * a + b] = S.to_world[4 * a + b];
-                inverse3(S.to_world, E.to_local);
-            }
-        }
-    }
-    sc.nee_fast_reject = (d.n_emitters == 1 && !sc.has_null_bsdf && !D->has_het && !getenv("LRT_NO_NEE_REJECT") &&
-                          (E.type == LRT_EMITTER_CONSTANT || (E.type == LRT_EMITTER_ENVMAP && env_interior_positive))) ? 1 : 0;
-    sc.emitters = D->track(dev_upload(em.data(), em.size(), st));
-    sc.mesh_emitters = D->track(dev_upload(mesh_em.data(), mesh_em.size(), st));
-    sc.mesh_emitter_tab = D->track(dev_upload(mesh_tab.data(), mesh_tab.size(), st));
-    sc.env_data = (const float4 *) D->track(dev_upload(env_rgbx.data(), env_rgbx.size(), st));
-    sc.env_hier = D->track(dev_upload(hier.data(), hier.size(), st));
-    build_camera(d, sc.cam, sc.film);
+    sc.emitters = up(P.emitters);
+    sc.mesh_emitters = up(P.mesh_emitters);
+    sc.mesh_emitter_tab = up(P.mesh_emitter_tab);
+    sc.env_data = (const float4 *) up(P.env_data);
+    sc.env_hier = up(P.env_hier);
     HIP_CHECK(hipMalloc((void **) &D->d_sc, sizeof(DScene))); D->track(D->d_sc);
-    HIP_CHECK(hipMemcpyAsync(D->d_sc, &sc, sizeof(DScene), hipMemcpyHostToDevice, st));
+    D->sc = sc;
+    HIP_CHECK(hipMemcpyAsync(D->d_sc, &D->sc, sizeof(DScene), hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMalloc((void **) &D->d_launch, LRT_LAUNCH_SLOTS * sizeof(DLaunch))); D->track(D->d_launch);
     HIP_CHECK(hipHostMalloc((void **) &D->h_launch, LRT_LAUNCH_SLOTS * sizeof(DLaunch)));
     HIP_CHECK(hipMalloc((void **) &D->counters, sizeof(DCounters))); D->track(D->counters);
@@ -700,79 +372,23 @@ static hipEvent_t get_event(DeviceScene *D, size_t i) {
     return D->ev_pool[i];
 }
 
-// spp: samples of ONE pass; spp_total = n_passes * spp (integrator.cpp:176-184,275-293)
-struct ResolvedOpts { int integrator, max_depth, rr_depth, hide_emitters; uint32_t spp, seed, tile_rank, tile_count; uint32_t spp_total = 0, n_passes = 1, pass = 0; };
-static ResolvedOpts resolve(const lrt_scene_desc &d, const lrt_render_opts *o) {
-    ResolvedOpts r;
-    if (o && o->integrator > LRT_INTEGRATOR_VOLPATHMIS) throw std::invalid_argument("lrt_render_opts.integrator " + std::to_string(o->integrator) + " is not an integrator (LRT_INTEGRATOR_PATH .. LRT_INTEGRATOR_VOLPATHMIS, or -1 for the scene's own)");
-    r.integrator = (o && o->integrator >= 0) ? o->integrator : d.integrator.type;
-    r.max_depth = (o && o->max_depth != -2) ? o->max_depth : d.integrator.max_depth;
-    // A path's depth lives in 16 bits of its record, and -1 ("unbounded") has no end at all when Russian roulette cannot stop a path (the ld sampler's 1-D
-    // sample takes `sample_count` values per pixel: for a fifth of the pixels none of them reaches 0.95; found by a fuzz scene whose path had left a leaky
-    // mesh with its medium flag set).  -1 and anything above mean 65535 here and in the oracle; the reference would go on.
-    if (r.max_depth < 0 || r.max_depth > 65535) r.max_depth = 65535;
-    r.rr_depth = (o && o->rr_depth >= 0) ? o->rr_depth : d.integrator.rr_depth;
-    r.hide_emitters = (o && o->hide_emitters >= 0) ? (o->hide_emitters != 0) : (d.integrator.hide_emitters != 0);
-    r.spp = (o && o->spp) ? o->spp : d.sample_count;
-    if (d.sampler_type == LRT_SAMPLER_LD) {            // integrator.cpp:169-171 + ldsampler.cpp:83-93: a square power of two
-        uint32_t res = 2;
-        while (res * res < r.spp) { ++res; uint32_t p2 = 1; while (p2 < res) p2 <<= 1; res = p2; }
-        r.spp = res * res;
-    }
-    r.seed = o ? o->seed : 0;
-    r.tile_rank = o ? o->tile_rank : 0; r.tile_count = (o && o->tile_count) ? o->tile_count : 1;
-    if (r.tile_rank >= r.tile_count) throw std::runtime_error("tile_rank must be smaller than tile_count");
-    if (r.spp == 0) throw std::runtime_error("spp must be positive");
-    // passes: the integrator's `samples_per_pass`, then the 2^32 - 1 limit of a wavefront (whole image, not this rank's share)
-    r.spp_total = r.spp; r.n_passes = 1; r.pass = 0;
-    if (r.integrator != LRT_INTEGRATOR_PRBVOLPATH) {
-        uint32_t per = d.samples_per_pass ? std::min(d.samples_per_pass, r.spp) : r.spp;
-        if (r.spp % per != 0) throw std::runtime_error("sample_count (" + std::to_string(r.spp) + ") must be a multiple of spp_per_pass (" + std::to_string(per) + ").");
-        const uint64_t wavefront = (uint64_t) d.film.crop_width * d.film.crop_height * per, limit = 0xffffffffull;
-        if (wavefront > limit) per /= (uint32_t) ((wavefront + limit - 1) / limit);
-        if (per == 0) throw std::runtime_error("film too large: a single sample per pixel exceeds 2^32 lanes");
-        r.n_passes = r.spp_total / per; r.spp = per;
-    }
-    return r;
-}
-
 // 32x32 pixel tiles in row-major tile order, tile k -> rank k % tile_count
 static void ensure_pixel_list(DeviceScene *D, const ResolvedOpts &O) {
     const DFilm &F = D->sc.film;
     if (O.tile_count == 1) { D->n_owned_pixels = (uint32_t) F.width * F.height; return; }
     if (D->pixel_list && D->pixel_list_rank == O.tile_rank && D->pixel_list_count == O.tile_count) return;
-    std::vector<uint32_t> px;
-    uint32_t tx = (F.width + 31) / 32, ty = (F.height + 31) / 32;
-    for (uint32_t t = O.tile_rank; t < tx * ty; t += O.tile_count) {
-        uint32_t x0 = (t % tx) * 32, y0 = (t / tx) * 32;
-        for (uint32_t y = y0; y < std::min<uint32_t>(y0 + 32, F.height); ++y)
-            for (uint32_t x = x0; x < std::min<uint32_t>(x0 + 32, F.width); ++x) px.push_back(y * F.width + x);
-    }
+    const TilePixels T = tile_pixel_list(F, O.tile_rank, O.tile_count);
     D->release(D->pixel_list); D->release(D->pixel_slot); D->pixel_list = nullptr; D->pixel_slot = nullptr;
-    D->pixel_list = D->track(dev_upload(px.data(), px.size(), D->stream));
-    std::vector<uint32_t> inv((size_t) F.width * F.height, 0u);
-    for (size_t k = 0; k < px.size(); ++k) inv[px[k]] = (uint32_t) k;
-    D->pixel_slot = D->track(dev_upload(inv.data(), inv.size(), D->stream));
-    D->pixel_list_rank = O.tile_rank; D->pixel_list_count = O.tile_count; D->n_owned_pixels = (uint32_t) px.size();
+    D->pixel_list = D->track(dev_upload(T.list.data(), T.list.size(), D->stream));
+    D->pixel_slot = D->track(dev_upload(T.slot.data(), T.slot.size(), D->stream));
+    D->pixel_list_rank = O.tile_rank; D->pixel_list_count = O.tile_count; D->n_owned_pixels = (uint32_t) T.list.size();
 }
 
-// The rank's tiles dilated by `halo` pixels, as a pixel list (row-major order inside the dilated tiles, every pixel once).  The PRB
-// adjoint normalises by the per-pixel sum of reconstruction-filter weights (common.py:730-746): a rank reads that sum at the pixels its
-// own lanes' footprints touch (own tiles + fn pixels), and those sums are complete once every lane within fn of them has been added:
-// halo = 2 fn.  Without this every rank would walk all W H spp lanes of the image.
+// The rank's tiles dilated by `halo` pixels (scene_prep.cpp, halo_pixel_list: the PRB weight film's lanes)
 static void ensure_halo_list(DeviceScene *D, const ResolvedOpts &O, uint32_t halo) {
     const DFilm &F = D->sc.film;
     if (D->halo_list && D->halo_rank == O.tile_rank && D->halo_count == O.tile_count && D->halo_width == halo) return;
-    std::vector<uint8_t> mark((size_t) F.width * F.height, 0);
-    const uint32_t tx = (F.width + 31) / 32, ty = (F.height + 31) / 32;
-    for (uint32_t t = O.tile_rank; t < tx * ty; t += O.tile_count) {
-        const int x0 = (int) (t % tx) * 32 - (int) halo, y0 = (int) (t / tx) * 32 - (int) halo;
-        const int x1 = std::min<int>((int) (t % tx) * 32 + 32, F.width) + (int) halo, y1 = std::min<int>((int) (t / tx) * 32 + 32, F.height) + (int) halo;
-        for (int y = std::max(y0, 0); y < std::min(y1, (int) F.height); ++y)
-            for (int x = std::max(x0, 0); x < std::min(x1, (int) F.width); ++x) mark[(size_t) y * F.width + x] = 1;
-    }
-    std::vector<uint32_t> px;
-    for (size_t k = 0; k < mark.size(); ++k) if (mark[k]) px.push_back((uint32_t) k);
+    const std::vector<uint32_t> px = halo_pixel_list(F, O.tile_rank, O.tile_count, halo);
     D->release(D->halo_list); D->halo_list = nullptr;
     D->halo_list = D->track(dev_upload(px.data(), px.size(), D->stream));
     D->halo_rank = O.tile_rank; D->halo_count = O.tile_count; D->halo_width = halo; D->n_halo_pixels = (uint32_t) px.size();
@@ -881,58 +497,6 @@ static void check_integrator_media(DeviceScene *D, int integrator) {
     if (integrator == LRT_INTEGRATOR_VOLPATHMIS) D->need_mis = true;          // its wider path record is allocated on first use
 }
 
-// 64-byte path records (kernels.h, MODE 4; instances k_render<LRT_INTEGRATOR_VOLPATH_CLOSED, ...>): volpath on a scene where only a path's last
-// trip can add radiance, so that a record carries no radiance and no last-scatter pdf.  Called for every render with the current scene
-// description (lrt_param_set may have changed sigma_t since the load); the caller also requires compact records (no area emitter, no EXT
-// scene, BVH in LDS) and the volpath integrator.  Conditions:
-//   (a) no medium is heterogeneous, every medium has sigma_t * scale finite and >= 1e-30 in every channel, the sensor sits in no medium and no shape has an
-//       exterior medium (every medium is the inside of a shape);
-//   (b) every shape has a delta-only BSDF: dielectric, or a bumpmap over a dielectric (no F_SMOOTH lobe, no null BSDF);
-//   (c) the only emitter is one envmap or constant emitter.
-// Proof that a record's radiance is +0 and last_pdf is never read (volpath_iteration):
-//   1. surface NEE needs F_SMOOTH (b): it never runs;
-//   2. in-medium NEE is +0: the shadow ray's free-flight draw -log(1 - u) / sigma_t is finite (a 24-bit uniform gives 1 - u >= 2^-24, so at
-//      most 16.7 / 1e-30 < the largest float, (a)).  Either it lands inside the medium, a real collision (sigma_n = 0 in a homogeneous
-//      medium) that zeroes the transmittance, or beyond the medium's boundary, a non-null surface (b) whose null transmission is 0; the
-//      emitter sample lies at distance >= 2 r, beyond every surface;
-//   3. the only emitter hit is the escape to the infinite emitter (c), and it ends the path.  A lane inside a medium never escapes (its
-//      free flight is finite, (a)), so the escape follows a surface event, a delta bounce (b), which sets specular_chain; or it happens
-//      at depth 0.  Either way count_direct holds and last_pdf / the last scatter position are not read.
-// What the closed instances no longer compile (volpath_iteration<false, CLOSED = true>; each branch below is dead by the clause it names):
-//   4. the surface emitter sampling (a second inlined volpath_sample_emitter, bsdf_eval, bsdf_pdf): 1., (b).  Its not-taken rng.skip(1) stays;
-//   5. the hide_emitters skip loop at depth 0: it runs only when the first hit is a shape that is an emitter; no shape is one, (c).  The
-//      `active_e` test after it still reads hide_emitters (the escape at depth 0 is hidden);
-//   6. the in-medium shadow march beyond its observable part.  Its value is +0 by 2. and is not added, so what remains is the emitter sample
-//      (two draws; a zero density ends it there), the march's single free-flight draw (or the skipped one when the segment is empty) and
-//      the count of the shadow query the reference needs: exactly when that free flight leaves the segment (`!elide`: no null BSDF (b),
-//      no heterogeneous medium (a)).  The march has no second trip: a valid collision multiplies the transmittance by sigma_n / combined
-//      = 0 (a), an escape meets a non-null surface (b) or nothing.  The query itself is not traced: its result fed the discarded value only;
-//   7. the BSDF dispatch of bsdf_sample: every leaf is a dielectric, under a bumpmap or not (b); the diffuse and null branches go;
-//   8. emitters on shapes: si_emitter of a hit is -1 and emitter_eval is the infinite emitter's value on a miss, (c).
-//      Since then the guard's "emitter hit without count_direct" sees the escape only: an emitting shape on a scene that got past this function
-//      would lose its radiance without tripping n_closed_guard.  Clause (c) is tested below on the host for every render and is what rules it out.
-//   (target_medium keeps its exterior branch although (a) makes it dead: removing it did not make the kernels smaller)
-// So every queued record's radiance is +0 and a path's radiance is its last trip's: 0 + ... + 0 + c = c, bit for bit.  The kernels check 3. on every
-// trip (DCounters::n_closed_guard: nonzero radiance on a lane that goes on, an emitter hit without count_direct) and the render fails instead of
-// returning a wrong image.  2. is not checked (that check cost 2.5 % on C3): it rests on the conditions above alone.
-static bool closed_records(const DeviceScene *D, const lrt_scene_desc &d) {
-    if (d.n_emitters != 1 || (d.emitters[0].type != LRT_EMITTER_ENVMAP && d.emitters[0].type != LRT_EMITTER_CONSTANT)) return false;
-    if (D->sc.cam.medium >= 0) return false;
-    for (uint32_t i = 0; i < d.n_media; ++i) {
-        const lrt_medium_desc &M = d.media[i];
-        if (M.type == LRT_MEDIUM_HETEROGENEOUS) return false;           // (volpath reads the bio media as homogeneous ones: sigma_t * scale)
-        for (int k = 0; k < 3; ++k) { const float st = M.sigma_t[k] * M.scale; if (!(std::isfinite(st) && st >= 1e-30f)) return false; }   // as upload_media forms it
-    }
-    for (uint32_t i = 0; i < d.n_shapes; ++i) {
-        const lrt_shape_desc &S = d.shapes[i];
-        if (S.exterior_medium >= 0 || S.bsdf < 0 || (uint32_t) S.bsdf >= d.n_bsdfs) return false;
-        const lrt_bsdf_desc *B = &d.bsdfs[S.bsdf];
-        if (B->type == LRT_BSDF_BUMPMAP) { if (B->nested < 0 || (uint32_t) B->nested >= d.n_bsdfs) return false; B = &d.bsdfs[B->nested]; }
-        if (B->type != LRT_BSDF_DIELECTRIC) return false;
-    }
-    return true;
-}
-
 // The render-kernel instance of a forward render: the row of kernels().render for an integrator on this scene.  compact / closed: run_wavefront's predicates.
 static const RenderRow &select_render_kernel(int integrator, bool has_het, bool spectral_mis, bool lds, bool ld, bool ext, bool compact, bool closed) {
     int mode;
@@ -977,7 +541,7 @@ static void run_wavefront(DeviceScene *D, const lrt_scene_desc &d, const Resolve
         const bool compact = D->use_lds && !D->has_area_emitter && !D->ext && !getenv("LRT_WIDE_RECORDS") && O.integrator != LRT_INTEGRATOR_VOLPATHMIS && !(O.integrator == LRT_INTEGRATOR_VOLPATH && D->has_het);
         // 64-byte records (volpath only; LRT_NO_CLOSED_RECORDS: developer switch back to the 80-byte layout): decided per render, since
         // lrt_param_set can change sigma_t after the scene was loaded
-        const bool closed = compact && O.integrator == LRT_INTEGRATOR_VOLPATH && closed_records(D, d) && !getenv("LRT_NO_CLOSED_RECORDS");
+        const bool closed = compact && O.integrator == LRT_INTEGRATOR_VOLPATH && closed_records(d, D->sc.cam.medium) && !getenv("LRT_NO_CLOSED_RECORDS");
         a.rp.compact = compact ? 1u : 0u;
 #ifdef LRT_DEV_VOLPATH_ONLY
         if (D->ext) throw std::runtime_error("developer build: no EXT instances (spheres / point emitters)");

@@ -1,0 +1,77 @@
+// Host half of the scene upload: everything device.hip copies to the device, computed from an lrt_scene_desc with plain
+// host arithmetic.  No HIP runtime call and no DeviceScene here, so the unit builds and runs without a GPU
+// (tests/host/scene_prep_main.cpp); device.hip uploads the result and patches the device pointers in.
+#pragma once
+#include "device_types.h"
+#include "bvh.h"
+#include "host_scene.h"
+#include <utility>
+
+namespace lrt {
+
+// The environment switches read while the device image is built, and what the upload side knows about the device.
+struct PrepOptions {
+    int bvh_leaf = 0;              // LRT_BVH_LEAF=n forces a leaf size (>= 1); 0: the search below
+    bool no_lds_bvh = false;       // LRT_NO_LDS_BVH
+    bool no_dist_grid = false;     // LRT_NO_DIST_GRID
+    int dist_grid_res = 0;         // LRT_DIST_GRID_RES clamped to 8 .. 256; 0: by the face count
+    bool no_nee_reject = false;    // LRT_NO_NEE_REJECT
+    size_t lds_limit = 0;          // LDS bytes a workgroup may ask for (device.hip: the opt-in maximum minus the kernels' static words)
+    int n_cus = 256;               // compute units of the device: the upload side sets it and takes it back for the launch geometry; the preparation does not use it
+    static PrepOptions from_env(); // reads the five switches; lds_limit and n_cus stay at their defaults
+};
+
+// BSDF leaf flags as DBsdf::flags stores them (dshade.h names the same values F_DELTA, F_SMOOTH, F_NULL; device.hip asserts that they agree)
+enum { PREP_F_DELTA = 1, PREP_F_SMOOTH = 2, PREP_F_NULL = 4 };
+
+struct PreparedScene {
+    std::vector<DSphere> spheres;
+    HostBVH bvh;                                       // nodes, triangle slots, root leaf
+    std::vector<unsigned char> lds_blob; DLdsInfo lds{};   // the LDS image (use_lds) and its offsets; lds.blob is the upload side's
+    std::vector<float> vattr;                          // 8 floats per vertex
+    std::vector<DShape> shapes;
+    std::vector<DTexture> textures; std::vector<float> tex_data;
+    std::vector<DBsdf> bsdfs;
+    std::vector<DEmitter> emitters;
+    std::vector<DMeshEmitter> mesh_emitters; std::vector<float> mesh_emitter_tab;
+    std::vector<float> env_data, env_hier;             // (w+1) x h RGBx texels, sampling hierarchy
+    // The scalar part of the scene record: counts, root leaf, one_shape, has_null_bsdf, nee_fast_reject, env (with the bounding sphere),
+    // cam, film and the distance field's geometry (grid.enabled set, grid.d null: the upload side builds the field).  Every pointer is null.
+    DScene sc{};
+    float grid_abs_margin = 0.f;                       // k_build_dist_grid's margin
+    bool env_interior_positive = false;                // envmap: rows 1..h-2 of the sampling density strictly positive
+    bool ext = false, has_area_emitter = false, has_het = false, has_non_bio = false, prb_null = false, use_lds = false;   // DeviceScene's flags of the same names
+    int bvh_leaf = 4;
+};
+// The two halves of prepare_scene, for a caller that has work to start in between (device.hip launches k_build_dist_grid after the first, so that
+// the kernel runs while the host prepares the rest, as it always did).  prepare_geometry: spheres, `ext`, the BVH with its leaf-size search,
+// the LDS image, the root leaf and counts, the distance field's geometry.  prepare_shading: everything else; it reads P.spheres for the bounds.
+void prepare_geometry(const lrt_scene_desc &d, const PrepOptions &opt, PreparedScene &P);
+void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedScene &P);
+PreparedScene prepare_scene(const lrt_scene_desc &d, const PrepOptions &opt);
+
+// bytes of the LDS image of a BVH: nodes, float4 vertices, 8-byte triangle slots, 16-bit traversal stacks of 1024 threads
+size_t lds_image_bytes(const HostBVH &b, uint32_t n_vertices);
+// the image's 16-bit indices hold the scene (faces, vertices, nodes, slots), it fits `opt.lds_limit`, and LRT_NO_LDS_BVH is not set
+bool lds_image_fits(const lrt_scene_desc &d, const HostBVH &b, const PrepOptions &opt);
+
+// a medium's extinction as the device sees it: property * scale (homogeneous.cpp:121-126 eval_sigmat; liver.cpp:204-209)
+inline float medium_sigma_t(const lrt_medium_desc &M, int k) { return M.sigma_t[k] * M.scale; }
+// The media tables (max(n_media, 1) entries each).  DBioMedium::log10_hep and DMedium::w_spec / w_plain are the device's to fill
+// (k_bio_prepare, k_medium_prepare); DHetMedium::data is the upload side's.  bsphere_r: DEnv::bsphere_r of the scene.
+void prepare_media(const lrt_scene_desc &d, float bsphere_r, std::vector<DMedium> &media, std::vector<DBioMedium> &bio, std::vector<DHetMedium> &het);
+
+// spp: samples of ONE pass; spp_total = n_passes * spp (integrator.cpp:176-184,275-293)
+struct ResolvedOpts { int integrator, max_depth, rr_depth, hide_emitters; uint32_t spp, seed, tile_rank, tile_count; uint32_t spp_total = 0, n_passes = 1, pass = 0; };
+ResolvedOpts resolve(const lrt_scene_desc &d, const lrt_render_opts *o);
+
+// 32x32 pixel tiles in row-major tile order, tile k -> rank k % count: the rank's pixels, and pixel -> index in that list
+struct TilePixels { std::vector<uint32_t> list, slot; };
+TilePixels tile_pixel_list(const DFilm &film, uint32_t rank, uint32_t count);
+// the rank's tiles dilated by `halo` pixels, as a pixel list (row-major order, every pixel once)
+std::vector<uint32_t> halo_pixel_list(const DFilm &film, uint32_t rank, uint32_t count, uint32_t halo);
+
+// 64-byte path records: does the scene prove that only a path's last trip adds radiance?  (scene_prep.cpp has the proof.)
+bool closed_records(const lrt_scene_desc &d, int sensor_medium);
+
+} // namespace lrt
