@@ -63,8 +63,8 @@ enum { LRT_EMITTER_AREA = 0, LRT_EMITTER_ENVMAP = 1, LRT_EMITTER_CONSTANT = 2,
        LRT_EMITTER_POINT = 3          /* [v106] src/emitters/point.cpp: `intensity` in radiance[3], position = to_world * 0 */ };
 enum { LRT_SHAPE_MESH = 0, LRT_SHAPE_RECTANGLE = 1,
        LRT_SHAPE_SPHERE = 2           /* [v106] src/shapes/sphere.cpp: n_faces = 0, analytic intersection (see lrt_shape_desc) */ };
-/* The CPU oracle under oracle/ knows neither LRT_SHAPE_SPHERE nor LRT_EMITTER_POINT: it must never be handed a scene
-   that contains them (it renders triangles and the three emitter kinds above only). */
+/* The CPU oracle under oracle/ renders LRT_SHAPE_SPHERE and LRT_EMITTER_POINT too; it refuses LRT_EMITTER_AREA on an
+   LRT_SHAPE_MESH with a message. */
 enum { LRT_RFILTER_BOX = 0, LRT_RFILTER_GAUSSIAN = 1, LRT_RFILTER_TENT = 2 };
 
 /* ------------------------------------------------- scene description (POD)

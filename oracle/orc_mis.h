@@ -227,7 +227,7 @@ static void volpathmis_sample(Ctx &C, Ray ray, int medium, V3 *out, bool *out_va
                     bool a = true; Hit h; h.prim = 0xffffffffu; h.t = kInf;
                     while (a) {
                         h = S.intersect(r2, false, false);
-                        a = h.valid() && S.shapes[S.face_shape[h.prim]].emitter >= 0;
+                        a = S.hit_on_emitter(h);
                         if (a) { SI s2 = S.compute_si(r2, h); r2 = spawn_ray(s2.p, s2.n, r2.d); }
                     }
                     si = S.compute_si(r2, h);

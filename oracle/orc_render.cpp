@@ -400,6 +400,15 @@ static V3 sample_emitter_direction(const Scene &S, V3 ref_p, float sx, float sy,
         bool active = dot(ds->d, ds->n) < 0.f && ds->pdf != 0.f;
         V3 rad(E.radiance[0], E.radiance[1], E.radiance[2]);
         spec = active ? rad / ds->pdf : V3(0.f);
+    } else if (E.type == LRT_EMITTER_POINT) {
+        /* src/emitters/point.cpp:119-148 sample_direction: a delta position (pdf 1, no MIS partner, nothing hits it), intensity / dist^2 */
+        ds->p = V3(E.to_world[3], E.to_world[7], E.to_world[11]);
+        ds->n = V3(0.f); ds->pdf = 1.f; ds->delta = true;
+        ds->d = ds->p - ref_p;
+        float dist2 = squared_norm(ds->d), inv_dist = rsqrt(dist2);
+        ds->dist = sqrtf(dist2);
+        ds->d = ds->d * inv_dist;
+        spec = V3(E.radiance[0], E.radiance[1], E.radiance[2]) * sqr(inv_dist);
     } else if (E.type == LRT_EMITTER_ENVMAP) {
         /* src/emitters/envmap.cpp:415-459 */
         float u, v, pdf; S.env_warp.sample(sx, sy, &u, &v, &pdf);
@@ -766,7 +775,7 @@ static void volpath_sample(Ctx &C, Ray ray, int medium, V3 *out, bool *out_valid
                     bool a = true; Hit h; h.prim = 0xffffffffu; h.t = kInf;
                     while (a) {
                         h = S.intersect(r2, false, false);
-                        a = h.valid() && S.shapes[S.face_shape[h.prim]].emitter >= 0;
+                        a = S.hit_on_emitter(h);
                         if (a) { SI s2 = S.compute_si(r2, h); r2 = spawn_ray(s2.p, s2.n, r2.d); }
                     }
                     si = S.compute_si(r2, h);
@@ -831,14 +840,14 @@ static void path_sample(Ctx &C, Ray ray, V3 *out, bool *out_valid) {
     const uint32_t max_depth = (uint32_t) C.max_depth;
     Hit pi = S.intersect(ray, false, false);
     if (C.hide_emitters) {                        /* path.cpp:178-192 */
-        bool skip = pi.valid() && S.shapes[S.face_shape[pi.prim]].emitter >= 0;
+        bool skip = S.hit_on_emitter(pi);
         if (skip) {
             SI s0 = S.compute_si(ray, pi);
             Ray r2 = spawn_ray(s0.p, s0.n, ray.d);
             bool a = true; Hit h; h.prim = 0xffffffffu; h.t = kInf;
             while (a) {
                 h = S.intersect(r2, false, false);
-                a = h.valid() && S.shapes[S.face_shape[h.prim]].emitter >= 0;
+                a = S.hit_on_emitter(h);
                 if (a) { SI s2 = S.compute_si(r2, h); r2 = spawn_ray(s2.p, s2.n, r2.d); }
             }
             pi = h; ray = r2;   /* NB: reference keeps ls.ray; si is recomputed from pi with ls.ray */
@@ -1103,7 +1112,7 @@ static void prb_sample(Ctx &C, Ray ray, bool adjoint, V3 delta_L, V3 L_in, V3 *L
             bool a = true; Hit h; h.prim = 0xffffffffu; h.t = kInf;
             while (a) {
                 h = S.intersect(r2, false, false);
-                a = h.valid() && S.shapes[S.face_shape[h.prim]].emitter >= 0;
+                a = S.hit_on_emitter(h);
                 if (a) { SI s2 = S.compute_si(r2, h); r2 = spawn_ray(s2.p, s2.n, r2.d); }
             }
             si = S.compute_si(r2, h);
@@ -1326,9 +1335,20 @@ using namespace orc;
 static thread_local std::string g_err;
 extern "C" const char *orc_last_error(void) { return g_err.c_str(); }
 
+/* What a render entry point refuses: a scene the oracle cannot render (Scene::unsupported), and the PRB integrator on a scene with sphere
+   shapes or point emitters (its adjoint is written for triangles and rectangle / infinite emitters, as on the device). */
+static bool refuse(const Scene &S, int integrator) {
+    if (!S.unsupported.empty()) { g_err = S.unsupported; return true; }
+    bool ext = !S.spheres.empty();
+    for (const lrt_emitter_desc &E : S.emitters) ext = ext || E.type == LRT_EMITTER_POINT;
+    if (ext && integrator == LRT_INTEGRATOR_PRBVOLPATH) { g_err = "unsupported: prbvolpath on a scene with sphere shapes or point emitters"; return true; }
+    return false;
+}
+
 extern "C" int orc_render_samples(orc_scene *s, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n,
                                   int n_threads, float *out, orc_stats *stats) {
     const Scene &S = s->s; Opts O = resolve_opts(S, opts);
+    if (refuse(S, O.integrator)) return 1;
     int nt = hw_threads(n_threads);
     std::vector<orc_stats> st(nt); for (auto &x : st) memset(&x, 0, sizeof(x));
     parallel_for(n, nt, [&](uint64_t b, uint64_t e, int t) {
@@ -1343,6 +1363,7 @@ extern "C" int orc_render_samples(orc_scene *s, const lrt_render_opts *opts, uin
 
 extern "C" int orc_render(orc_scene *s, const lrt_render_opts *opts, int n_threads, float *film_raw, float *image, orc_stats *stats) {
     const Scene &S = s->s; Opts O = resolve_opts(S, opts);
+    if (refuse(S, O.integrator)) return 1;
     const lrt_film_desc &F = S.d.film;
     int C = F.has_alpha ? 5 : 4;
     size_t np = (size_t) F.crop_width * F.crop_height;
@@ -1374,6 +1395,7 @@ extern "C" int orc_render(orc_scene *s, const lrt_render_opts *opts, int n_threa
 /* src/render/integrator.cpp:190-273,399-434: scalar-variant tiling (CPU baseline workload) */
 extern "C" int orc_render_scalar(orc_scene *s, const lrt_render_opts *opts, int n_threads, float *film_raw, float *image, orc_stats *stats) {
     const Scene &S = s->s; Opts O = resolve_opts(S, opts);
+    if (refuse(S, O.integrator)) return 1;
     const lrt_film_desc &F = S.d.film;
     int C = F.has_alpha ? 5 : 4, W = F.crop_width, H = F.crop_height;
     size_t np = (size_t) W * H;
@@ -1478,7 +1500,7 @@ extern "C" void orc_square_to_cosine_hemisphere(float u1, float u2, float o[3]) 
 extern "C" void orc_square_to_uniform_sphere(float u1, float u2, float o[3]) { V3 v = square_to_uniform_sphere(u1, u2); o[0] = v.x; o[1] = v.y; o[2] = v.z; }
 extern "C" void orc_fresnel(float c, float eta, float out[4]) { fresnel(c, eta, &out[0], &out[1], &out[2], &out[3]); }
 /* The oracle's side of lrt_bsdf_probe (include/liverrt.h): closest hit along (o, d) without a ray offset, the surface interaction,
-   bsdf_sample as path_iteration draws it, bsdf_eval / bsdf_pdf at the world direction wo_query.  The oracle holds no spheres. */
+   bsdf_sample as path_iteration draws it, bsdf_eval / bsdf_pdf at the world direction wo_query.  Triangles and spheres (Scene::intersect, Scene::compute_si). */
 extern "C" void orc_bsdf_probe(orc_scene *s, const float *o, const float *d, const float *sample, const float *wo_query, uint32_t n, float *out) {
     const Scene &S = s->s;
     for (uint32_t i = 0; i < n; ++i) {
@@ -1533,6 +1555,7 @@ extern "C" void orc_sample_ray(orc_scene *s, float px, float py, float o[3], flo
    (1) primal pass, (2) adjoint replay with the same sampler state. */
 extern "C" int orc_render_backward(orc_scene *s, const lrt_render_opts *opts, int n_threads, const float *grad_image, lrt_param_grads *out) {
     const Scene &S = s->s; Opts O = resolve_opts(S, opts);
+    if (refuse(S, LRT_INTEGRATOR_PRBVOLPATH)) return 1;
     const lrt_film_desc &F = S.d.film;
     const int T = F.has_alpha ? 4 : 3, W = F.crop_width, H = F.crop_height;
     const size_t np = (size_t) W * H; const uint64_t N = (uint64_t) np * O.spp;

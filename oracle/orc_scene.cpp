@@ -218,7 +218,68 @@ static inline void test_tri(const Scene &S, const Ray &r, uint32_t f, Hit &best)
     if (t < best.t || (t == best.t && f < best.prim)) { best.t = t; best.u = u; best.v = v; best.prim = f; }
 }
 
-Hit Scene::intersect(const Ray &r, bool any_hit, bool brute) const {
+/* ---------------------------------------------------------------- spheres
+   src/shapes/sphere.cpp in float32: llvm_ad_rgb takes the `is_diff_v` branch (Value = float32). */
+
+/* include/mitsuba/core/math.h:360-402 solve_quadratic */
+static bool solve_quadratic(float a, float b, float c, float *x0, float *x1) {
+    bool linear_case = a == 0.f, valid_linear = linear_case && b != 0.f;
+    *x0 = *x1 = -c / b;
+    float discrim = fmaf(b, b, -(4.f * a * c));                    /* dr::fmsub(b, b, 4 a c) */
+    bool valid_quadratic = !linear_case && discrim >= 0.f;
+    float sqrt_discrim = sqrtf(discrim);
+    float temp = -0.5f * (b + copysignf(sqrt_discrim, b));
+    float x0p = temp / a, x1p = c / temp;
+    if (!linear_case) { *x0 = fminf(x0p, x1p); *x1 = fmaxf(x0p, x1p); }
+    return valid_linear || valid_quadratic;
+}
+
+/* sphere.cpp:516-579 ray_intersect_preliminary_impl: the distance of the hit, +inf when there is none */
+static float sphere_intersect(const Sphere &sp, const Ray &r) {
+    V3 l = r.o - sp.c, dir = r.d;
+    float plane_t = dot(-l, dir) / norm(dir);                      /* the plane through the centre, perpendicular to the ray */
+    V3 o = fma3(dir, plane_t, r.o) - sp.c;                         /* ray(plane_t) - center: the new origin */
+    float A = squared_norm(dir), B = 2.f * dot(o, dir), C = squared_norm(o) - sqr(sp.radius);
+    float near_t, far_t;
+    bool found = solve_quadratic(A, B, C, &near_t, &far_t);
+    near_t += plane_t; far_t += plane_t;
+    bool out_bounds = !(near_t <= r.maxt && far_t >= 0.f);         /* NaN-aware */
+    bool in_bounds = near_t < 0.f && far_t > r.maxt;
+    float t = near_t < 0.f ? far_t : near_t;
+    return (found && !out_bounds && !in_bounds) ? t : kInf;
+}
+
+/* sphere.cpp:581-622 ray_test_impl: the ray's own origin, no plane shift */
+static bool sphere_test(const Sphere &sp, const Ray &r) {
+    V3 o = r.o - sp.c, dir = r.d;
+    float A = squared_norm(dir), B = 2.f * dot(o, dir), C = squared_norm(o) - sqr(sp.radius);
+    float near_t, far_t;
+    bool found = solve_quadratic(A, B, C, &near_t, &far_t);
+    bool out_bounds = !(near_t <= r.maxt && far_t >= 0.f);
+    bool in_bounds = near_t < 0.f && far_t > r.maxt;
+    return found && !out_bounds && !in_bounds;
+}
+
+/* Spheres are tested before the triangles.  Closest hit: the nearest sphere (equal t: the lower index) bounds the triangle search, and a
+   triangle found within that bound wins, at equal t too.  Any hit: a sphere that meets the segment answers the query. */
+Hit Scene::intersect(const Ray &ray, bool any_hit, bool brute) const {
+    Hit best; best.t = kInf; best.u = best.v = 0.f; best.prim = 0xffffffffu;
+    Hit sph = best;
+    Ray r = ray;
+    if (any_hit) {
+        for (const Sphere &sp : spheres) if (sphere_test(sp, ray)) { sph.t = 0.f; sph.prim = d.n_faces; return sph; }
+    } else {
+        for (uint32_t k = 0; k < spheres.size(); ++k) {
+            float t = sphere_intersect(spheres[k], ray);
+            if (t < sph.t) { sph.t = t; sph.prim = d.n_faces + k; }
+        }
+        r.maxt = fminf(ray.maxt, sph.t);
+    }
+    const Hit tri = intersect_triangles(r, any_hit, brute);
+    return tri.valid() ? tri : sph;
+}
+
+Hit Scene::intersect_triangles(const Ray &r, bool any_hit, bool brute) const {
     Hit best; best.t = kInf; best.u = best.v = 0.f; best.prim = 0xffffffffu;
     if (d.n_faces == 0) return best;
     if (brute) {
@@ -252,6 +313,7 @@ SI Scene::compute_si(const Ray &r, const Hit &h) const {
         si.t = kInf; si.wi = -r.d; si.shape = 0xffffffffu; si.prim = 0xffffffffu;
         return si;
     }
+    if (h.prim >= d.n_faces) return compute_si_sphere(r, h);
     uint32_t f = h.prim, shp = face_shape[f];
     const lrt_shape_desc &sd = shapes[shp];
     const uint32_t *fi = &faces[3 * f];
@@ -286,6 +348,39 @@ SI Scene::compute_si(const Ray &r, const Hit &h) const {
     } else si.sh.n = si.n;
     if (sd.flip_normals) { si.n = -si.n; si.sh.n = -si.sh.n; }
     /* initialize_sh_frame */
+    si.sh.s = normalize(fma3(si.sh.n, -dot(si.sh.n, si.dp_du), si.dp_du));
+    if (si.dp_du.x == 0.f && si.dp_du.y == 0.f && si.dp_du.z == 0.f) { V3 tmp; coordinate_system(si.sh.n, &si.sh.s, &tmp); }
+    si.sh.t = cross(si.sh.n, si.sh.s);
+    si.wi = si.sh.to_local(-r.d);
+    return si;
+}
+
+/* include/mitsuba/core/vector.h:148-151 dir_to_sph -> dr::unit_angle_z (Dr.Jit: 2 asin(|v - (0, 0, sign z)| / 2), pi minus that for z < 0) */
+static float unit_angle_z(V3 v) {
+    float temp = 2.f * m_asin(.5f * norm(V3(v.x, v.y, v.z - signf(v.z))));
+    return v.z >= 0.f ? temp : kPi - temp;
+}
+
+/* src/shapes/sphere.cpp:626-740 compute_surface_interaction, the IsDiff / !follow_shape branch (what llvm_ad_rgb runs): the point stays on
+   the ray, p = ray(t), without the re-projection of the non-differentiable branch; then initialize_sh_frame as for a mesh. */
+SI Scene::compute_si_sphere(const Ray &r, const Hit &h) const {
+    const Sphere &sp = spheres[h.prim - d.n_faces];
+    SI si; memset((void *) &si, 0, sizeof(si));
+    si.valid = true; si.t = h.t; si.prim = h.prim; si.shape = sp.shape;
+    si.p = fma3(r.d, h.t, r.o);
+    V3 n = normalize(si.p - sp.c);
+    V3 local = xform_point(sp.to_object, si.p);
+    float theta = unit_angle_z(local), phi = m_atan2(local.y, local.x);
+    if (phi < 0.f) phi += 2.f * kPi;
+    si.uv = { phi * kInvTwoPi, theta * kInvPi };
+    V3 dp_du(-local.y, local.x, 0.f);
+    float rd = sqrtf(sqr(local.x) + sqr(local.y)), inv_rd = rcp(rd), cos_phi = local.x * inv_rd, sin_phi = local.y * inv_rd;
+    V3 dp_dv(local.z * cos_phi, local.z * sin_phi, -rd);
+    if (rd == 0.f) dp_dv = V3(1.f, 0.f, 0.f);                      /* the poles */
+    si.dp_du = xform_vec(sp.to_world, dp_du) * (2.f * kPi);
+    si.dp_dv = xform_vec(sp.to_world, dp_dv) * kPi;
+    if (sp.flip_normals) n = -n;
+    si.n = n; si.sh.n = n;
     si.sh.s = normalize(fma3(si.sh.n, -dot(si.sh.n, si.dp_du), si.dp_du));
     if (si.dp_du.x == 0.f && si.dp_du.y == 0.f && si.dp_du.z == 0.f) { V3 tmp; coordinate_system(si.sh.n, &si.sh.s, &tmp); }
     si.sh.t = cross(si.sh.n, si.sh.s);
@@ -338,6 +433,19 @@ void Scene::finalize() {
     }
     /* ---- acceleration + bounds (src/render/scene.cpp:49, include/mitsuba/core/bbox.h:343-346) */
     bvh_build(*this);
+    /* ---- sphere shapes (src/shapes/sphere.cpp:146-165): radius = |to_world * (1, 0, 0)|, center = to_world * 0 */
+    spheres.clear(); unsupported.clear();
+    for (uint32_t i = 0; i < d.n_shapes; ++i) {
+        const lrt_shape_desc &sd = shapes[i];
+        if (sd.kind != LRT_SHAPE_SPHERE) continue;
+        Sphere sp;
+        memcpy(sp.to_world.m, sd.to_world, sizeof(sp.to_world.m));
+        sp.radius = norm(xform_vec(sp.to_world, V3(1.f, 0.f, 0.f)));
+        sp.c = V3(sd.to_world[3], sd.to_world[7], sd.to_world[11]);
+        sp.to_object = m4_inverse_affine(sp.to_world);
+        sp.shape = i; sp.flip_normals = sd.flip_normals != 0;
+        spheres.push_back(sp);
+    }
     {
         V3 lo(kInf), hi(-kInf);
         for (uint32_t i = 0; i < d.n_vertices; ++i) {
@@ -345,7 +453,12 @@ void Scene::finalize() {
             lo = V3(fminf(lo.x, p.x), fminf(lo.y, p.y), fminf(lo.z, p.z));
             hi = V3(fmaxf(hi.x, p.x), fmaxf(hi.y, p.y), fmaxf(hi.z, p.z));
         }
-        if (d.n_vertices) {
+        for (const Sphere &sp : spheres) {                        /* Sphere::bbox, sphere.cpp:192-197: center -/+ radius */
+            V3 a = sp.c - V3(sp.radius), b = sp.c + V3(sp.radius);
+            lo = V3(fminf(lo.x, a.x), fminf(lo.y, a.y), fminf(lo.z, a.z));
+            hi = V3(fmaxf(hi.x, b.x), fmaxf(hi.y, b.y), fmaxf(hi.z, b.z));
+        }
+        if (d.n_vertices || !spheres.empty()) {
             V3 c = (hi + lo) * 0.5f;
             bsphere_c = c; bsphere_r = norm(c - hi);
             /* src/emitters/envmap.cpp:337-351 set_scene */
@@ -356,9 +469,14 @@ void Scene::finalize() {
     env = -1; area.assign(d.n_emitters, AreaInfo{ V3(0.f), 0.f });
     for (uint32_t e = 0; e < d.n_emitters; ++e) {
         const lrt_emitter_desc &E = emitters[e];
+        if (E.type == LRT_EMITTER_POINT) continue;   /* src/emitters/point.cpp: a position and an intensity, nothing derived; not an environment */
         if (E.type == LRT_EMITTER_AREA) {
             /* src/shapes/rectangle.cpp:108-119: frame + inverse surface area */
             const lrt_shape_desc &sd = shapes[E.shape];
+            if (sd.kind != LRT_SHAPE_RECTANGLE) {
+                unsupported = "unsupported by the oracle: an area emitter on a triangle mesh or a sphere (emitter " + std::to_string(e) + "); it knows area emitters on rectangles only";
+                continue;
+            }
             M4 tw; memcpy(tw.m, sd.to_world, sizeof(tw.m));
             V3 dp_du = xform_vec(tw, V3(2.f, 0.f, 0.f)), dp_dv = xform_vec(tw, V3(0.f, 2.f, 0.f));
             uint32_t v0 = faces[3 * sd.first_face];

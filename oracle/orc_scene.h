@@ -39,6 +39,9 @@ struct SI {                /* SurfaceInteraction3f subset (include/mitsuba/rende
     bool valid; float t; V3 p, n; Frame sh; V2 uv; V3 dp_du, dp_dv, wi; uint32_t prim, shape;
 };
 
+/* src/shapes/sphere.cpp:146-165 update(): centre, radius, the transform and its inverse */
+struct Sphere { V3 c; float radius; M4 to_world, to_object; uint32_t shape; bool flip_normals; };
+
 struct Scene {
     lrt_scene_desc d;                         /* deep copy (arrays owned below) */
     std::vector<float> positions, normals, texcoords;
@@ -56,6 +59,10 @@ struct Scene {
     M4 sample_to_camera, cam_to_world;
     /* acceleration */
     std::vector<BVHNode> nodes; std::vector<uint32_t> prim_ids;
+    /* sphere shapes, in the order of shapes[]: outside the BVH, a hit on spheres[k] is primitive n_faces + k */
+    std::vector<Sphere> spheres;
+    /* what the oracle cannot render (area emitters on triangle meshes): the render entry points fail with this text */
+    std::string unsupported;
     /* environment */
     int env = -1;                             /* emitter index of the environment, -1: none */
     V3 bsphere_c; float bsphere_r;
@@ -74,7 +81,11 @@ struct Scene {
 
     void finalize();
     Hit intersect(const Ray &r, bool any_hit, bool brute) const;
+    Hit intersect_triangles(const Ray &r, bool any_hit, bool brute) const;
     SI  compute_si(const Ray &r, const Hit &h) const;
+    SI  compute_si_sphere(const Ray &r, const Hit &h) const;
+    /* does this hit lie on a shape that carries an area emitter (spheres carry none) */
+    bool hit_on_emitter(const Hit &h) const { return h.valid() && h.prim < d.n_faces && shapes[face_shape[h.prim]].emitter >= 0; }
     float rfilter_eval(float x) const;
 };
 

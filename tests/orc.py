@@ -144,7 +144,8 @@ class OrcScene:
         o = _lib.make_opts(kw.get("integrator"), kw.get("max_depth"), kw.get("rr_depth"), kw.get("hide_emitters"),
                            kw.get("spp", 0), kw.get("seed", 0))
         st = OrcStats()
-        self._L.orc_render_samples(self._h, C.byref(o), int(lane_begin), int(n), threads, out.ctypes.data, C.byref(st))
+        if self._L.orc_render_samples(self._h, C.byref(o), int(lane_begin), int(n), threads, out.ctypes.data, C.byref(st)) != 0:
+            raise RuntimeError(self._L.orc_last_error().decode())
         self.last_stats = {k: getattr(st, k) for k, _ in OrcStats._fields_}
         return out
 
@@ -154,7 +155,7 @@ class OrcScene:
                            kw.get("spp", 0), kw.get("seed", 0), grad_medium=kw.get("medium", -1))
         out = _lib.ParamGrads()
         if self._L.orc_render_backward(self._h, C.byref(o), threads, g.ctypes.data, C.byref(out)) != 0:
-            raise RuntimeError("orc_render_backward failed")
+            raise RuntimeError(self._L.orc_last_error().decode() or "orc_render_backward failed")
         return {"sigma_t": np.array(out.d_sigma_t[:], np.float32), "albedo": np.array(out.d_albedo[:], np.float32), "g": float(out.d_g)}
 
     def trace(self, o, d, tmax=None, any_hit=False, brute_force=False):
@@ -191,7 +192,7 @@ class OrcScene:
         return rgb
 
     def bsdf_probe(self, o, d, sample, wo_query):
-        """orc_bsdf_probe: the oracle's twin of Scene.bsdf_probe, the same dict of arrays (triangle shapes only)"""
+        """orc_bsdf_probe: the oracle's twin of Scene.bsdf_probe, the same dict of arrays"""
         a = [np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (o, d, sample, wo_query)]
         n = a[0].shape[0]
         assert all(x.shape[0] == n for x in a)

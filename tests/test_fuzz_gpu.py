@@ -247,3 +247,21 @@ def test_random_scene_prb_het(mi, orc, tmp_path, seed):
     for k in ("sigma_t", "albedo"):
         assert np.abs(gg[k] - gc[k]).max() <= 3e-4 * max(np.abs(gc[k]).max(), 1e-7), (k, gg[k], gc[k])
     assert abs(gg["g"] - gc["g"]) <= 3e-4 * max(abs(gc["g"]), 1e-6) + 1e-9
+
+
+# The sphere family (scene_gen.sphere_fuzz_xml): every seed here loads, and the oracle renders it to a finite film that is not black
+# (checked on the CPU when the list was made; tests/test_sphere_oracle.py::test_sphere_fuzz_seeds_render_on_the_oracle repeats that).
+SPHERE_SEEDS = list(range(24))
+
+
+@pytest.mark.parametrize("seed", SPHERE_SEEDS)
+def test_random_sphere_scene_bit_exact(mi, orc, seed):
+    from scene_gen import sphere_fuzz_xml
+    xml, integrator = sphere_fuzz_xml(seed, ASSETS)
+    sc = mi.load_string(xml)
+    o = orc.OrcScene(sc)
+    h, w, _ = sc.film_shape()
+    assert_lanes_equal(sc, o, 0, w * h * sc.spp, seed=seed)
+    if seed % 3 == 0:
+        raw = sc.render(return_raw=True, seed=seed)[1]
+        assert film_close(raw, o.render(return_raw=True, seed=seed)[1]).all()

@@ -37,6 +37,18 @@ def test_dielectric_sweep(mi, orc, tmp_path):
     sc.check_dielectric(prober, surf[len(names)], len(names), 1.5, "oracle cube eta 1.5", seed=30)
 
 
+def test_dielectric_sweep_on_the_sphere(mi, orc, tmp_path):
+    """b on the sphere, from outside and inside (sphere.cpp's far root): the oracle's sphere interaction against float64"""
+    scene, surf = sc.build(mi, tmp_path, [("sphere", ("dielectric", "1.5"))])
+    sc.check_dielectric(sc.Prober(orc.OrcScene(scene).bsdf_probe), surf[0], 0, 1.5, "oracle sphere eta 1.5", seed=31)
+
+
+def test_checkerboard_on_the_sphere(mi, orc, tmp_path):
+    """c on the sphere: its uv (dir_to_sph of the local point) picks the checkerboard's colour"""
+    scene, surf = sc.build(mi, tmp_path, [("sphere", ("checker",))])
+    sc.check_diffuse(sc.Prober(orc.OrcScene(scene).bsdf_probe), surf[0], 0, "oracle sphere checker", True, seed=44)
+
+
 def test_diffuse_and_checkerboard(mi, orc, tmp_path):
     """c"""
     items = [("rectangle", ("diffuse",)), ("rectangle", ("checker",)), ("quad", ("checker",))]
@@ -72,9 +84,24 @@ def test_bump_map(mi, orc, tmp_path, shape, name, to_uv):
     run_bump_case(mi, tmp_path, shape, name, to_uv, lambda scene: sc.Prober(orc.OrcScene(scene).bsdf_probe), "oracle")
 
 
+@pytest.mark.parametrize("shape,name,to_uv", [("sphere", "field", "scaled"), ("sphere", "ramp_v", "id")])
+def test_bump_map_on_the_sphere(mi, orc, tmp_path, shape, name, to_uv):
+    """d on the sphere: the bump map perturbs the frame built from the sphere's dp_du / dp_dv"""
+    run_bump_case(mi, tmp_path, shape, name, to_uv, lambda scene: sc.Prober(orc.OrcScene(scene).bsdf_probe), "oracle")
+
+
 @pytest.mark.parametrize("integrator", ["path", "volpath"])
 def test_plate_transport(mi, orc, tmp_path, integrator):
     """f, scene 1: a tilted glass plate in front of a smooth environment map, per pixel R_tot L(mirror d) + T_tot L(d)"""
     scene = sc.transport_scene(mi, tmp_path, "plate", integrator)
     o = orc.OrcScene(scene)
     sc.check_transport(lambda spp, seed: o.render(spp=spp, seed=seed), ec.reference_of(scene), "plate", f"oracle plate {integrator}", power=0.03)
+
+
+@pytest.mark.parametrize("integrator", ["path", "volpath"])
+def test_sphere_transport(mi, orc, tmp_path, integrator):
+    """f, scene 2: a glass sphere in front of the same map, the series of its internal reflections: every bounce past the first starts
+    inside the sphere, takes the far root, and carries the frame and wi of the hit before it"""
+    scene = sc.transport_scene(mi, tmp_path, "sphere", integrator)
+    o = orc.OrcScene(scene)
+    sc.check_transport(lambda spp, seed: o.render(spp=spp, seed=seed), ec.reference_of(scene), "sphere", f"oracle sphere {integrator}", power=0.01)

@@ -1,6 +1,6 @@
 """Surface scattering on the device through lrt_bsdf_probe (k_bsdf_probe, csrc/kernels.h): the checks of tests/test_surface.py run on
-the HIP kernel's output, every probe on triangle shapes compared with the oracle's bit for bit (check e), the sphere (which the oracle
-does not know) held to the float64 reference alone, and the two transport closed forms of check f through the render kernels."""
+the HIP kernel's output, every probe on triangle shapes compared with the oracle's bit for bit (check e), the sphere held to the float64
+reference here (its probes are compared with the oracle's bit for bit in tests/test_sphere_parity_gpu.py), and the two transport closed forms of check f through the render kernels."""
 import numpy as np
 import pytest
 
@@ -54,7 +54,7 @@ def test_dielectric_sweep(mi, orc, tmp_path):
 
 
 def test_dielectric_sweep_on_the_sphere(mi, tmp_path):
-    """b on the sphere, from outside and inside: device only (the oracle knows no spheres), against float64 alone"""
+    """b on the sphere, from outside and inside: the device against float64 (the oracle runs the same check in tests/test_surface.py)"""
     scene, surf = sc.build(mi, tmp_path, [("sphere", ("dielectric", "1.5"))])
     sc.check_dielectric(sc.Prober(scene.bsdf_probe), surf[0], 0, 1.5, "device sphere eta 1.5", seed=31)
 
@@ -71,7 +71,7 @@ def test_diffuse_and_checkerboard(mi, orc, tmp_path):
 
 
 def test_checkerboard_on_the_sphere(mi, tmp_path):
-    """c on the sphere: device only"""
+    """c on the sphere: the device against float64"""
     scene, surf = sc.build(mi, tmp_path, [("sphere", ("checker",))])
     sc.check_diffuse(sc.Prober(scene.bsdf_probe), surf[0], 0, "device sphere checker", True, seed=44)
 
