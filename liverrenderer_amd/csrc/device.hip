@@ -95,9 +95,9 @@ struct DeviceScene {
     std::vector<hipEvent_t> ev_pool;
     std::vector<DMedium> h_media; DMedium *d_media = nullptr;
     std::vector<DBioMedium> h_bio; DBioMedium *d_bio = nullptr;
-    std::vector<DHetMedium> h_het; DHetMedium *d_het = nullptr; std::vector<float *> het_data; bool has_het = false, has_non_bio = false, need_mis = false, mis_alloc = false;
+    std::vector<DHetMedium> h_het; DHetMedium *d_het = nullptr; std::vector<float *> het_data; bool has_het = false, has_non_bio = false, need_mis = false; uint32_t ws_layouts = 0;   // ws_layouts: the record layouts the workspace is allocated for (layout_bit mask)
     bool ext = false;                      // spheres, point emitters or area emitters on meshes: the EXT kernel instances (ExtTracer, point- / mesh-emitter sampling), wide records
-    bool has_area_emitter = false;         // decides the record layout: only an area emitter's pdf reads the last scatter position (kernels.h, store_state)
+    bool has_area_emitter = false;         // decides the record layout: only an area emitter's pdf reads the last scatter position (record_layout.h)
     float *dgrid = nullptr; size_t dgrid_floats = 0;   // lrt_render_backward_grid with a host result: the device-side gradient grid
     bool prb_null = false;                 // prbvolpath.py:84-91 `handle_null_scattering`: a heterogeneous medium is attached to a shape
     DLdsInfo lds{}; bool use_lds = false; int n_cus = 256; int bvh_leaf = 4;
@@ -172,16 +172,9 @@ typedef void (*RenderFn)(ScenePtr, LaunchPtr);
 // One k_render<mode, block, lds, ld, compact, ext>.  mode: the kernel selector (an LRT_INTEGRATOR_* value of the API or of device_types.h).
 struct RenderRow { int mode; bool lds, ld, compact, ext; uint32_t block, record_bytes; RenderFn fn; };
 
-// bytes per queued path record of a mode's layout, as lrt_render_stats reports them
-static constexpr uint32_t record_bytes(int mode, bool compact) {
-    return mode == LRT_INTEGRATOR_VOLPATH_CLOSED ? LRT_STATE_BYTES_CLOSED
-         : mode == LRT_INTEGRATOR_BIOVOLPATH || mode == LRT_INTEGRATOR_BIOVOLPATH06 ? (compact ? LRT_STATE_BYTES_BIO - 8 : LRT_STATE_BYTES_BIO)
-         : compact ? LRT_STATE_BYTES_COMPACT
-         : mode == LRT_INTEGRATOR_VOLPATH_HET ? LRT_STATE_BYTES_HET
-         : mode == LRT_INTEGRATOR_VOLPATHMIS || mode == LRT_INTEGRATOR_VOLPATHMIS_PLAIN ? LRT_STATE_BYTES_MIS : LRT_STATE_BYTES;
-}
 template <int MODE, int BLOCK, bool LDS, bool LD, bool COMPACT = false, bool EXT = false> static void add_row(std::vector<RenderRow> &t) {
-    t.push_back({ MODE, LDS, LD, COMPACT, EXT, BLOCK, record_bytes(MODE, COMPACT), k_render<MODE, BLOCK, LDS, LD, COMPACT, EXT> });
+    static_assert(record_form_exists(record_layout(MODE), COMPACT), "this layout has no such form (record_layout.h, kRecordForms)");
+    t.push_back({ MODE, LDS, LD, COMPACT, EXT, BLOCK, record_bytes(record_layout(MODE), COMPACT), k_render<MODE, BLOCK, LDS, LD, COMPACT, EXT> });
 }
 // a mode's wide-record instances: {LDS BVH (LDS_BLOCK threads), global BVH (LRT_BLOCK)} x {independent, ld} x {plain, EXT}
 template <int MODE, int LDS_BLOCK> static void add_mode(std::vector<RenderRow> &t) {
@@ -214,10 +207,12 @@ static const KernelTable &kernels() {
 #ifndef LRT_DEV_BLOCK
 #define LRT_DEV_BLOCK 1024
 #endif
-        // the 64-byte-record instance stands in for "the C3 kernel" of a volpath developer build (any other integrator: its compact instance again)
+        // the 64-byte-record instance stands in for "the C3 kernel" of a volpath developer build (any other integrator: its compact instance again, if its layout has a compact form)
 #define LRT_DEV_CLOSED (LRT_DEV_INTEGRATOR == LRT_INTEGRATOR_VOLPATH ? LRT_INTEGRATOR_VOLPATH_CLOSED : LRT_DEV_INTEGRATOR)
-        add_row<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD>(r); add_row<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD, true>(r);
-        add_row<LRT_DEV_CLOSED, LRT_DEV_BLOCK, true, LRT_DEV_LD, true>(r);
+        add_row<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD>(r);
+        if constexpr (record_form_exists(record_layout(LRT_DEV_INTEGRATOR), true)) {
+            add_row<LRT_DEV_INTEGRATOR, LRT_DEV_BLOCK, true, LRT_DEV_LD, true>(r); add_row<LRT_DEV_CLOSED, LRT_DEV_BLOCK, true, LRT_DEV_LD, true>(r);
+        }
 #else
         add_mode<LRT_INTEGRATOR_PATH, 1024>(r); add_mode<LRT_INTEGRATOR_VOLPATH, 1024>(r); add_mode<LRT_INTEGRATOR_BIOVOLPATH, 1024>(r); add_mode<LRT_INTEGRATOR_BIOVOLPATH06, 1024>(r);
         // (the wide-record integrators run 768-thread workgroups on the LDS BVH: 3 waves per SIMD, 168 VGPRs instead of 128 + 200 - 430 B of scratch per lane;
@@ -344,27 +339,23 @@ void device_scene_update_params(DeviceScene *D, const lrt_scene_desc &d, bool gr
 }
 
 static void ensure_workspace(DeviceScene *D, uint32_t capacity) {
-    if (D->capacity >= capacity && D->mis_alloc == D->need_mis) return;
+    const uint32_t layouts = workspace_layouts(D->has_het, D->need_mis);
+    if (D->capacity >= capacity && D->ws_layouts == layouts) return;
     HIP_CHECK(hipStreamSynchronize(D->stream));
-    // Exception safety: the old streams are released and every pointer cleared BEFORE anything is allocated, and capacity / mis_alloc are
+    // Exception safety: the old streams are released and every pointer cleared BEFORE anything is allocated, and capacity / ws_layouts are
     // set only after every allocation succeeded: a failed hipMalloc (out of memory) leaves capacity = 0, so the next render allocates again
     // instead of launching on freed memory.
-    const bool want_mis = D->need_mis;
     D->capacity = 0;
-    for (DPathStreams *q : { &D->q[0], &D->q[1] }) {
-        for (void *p : { (void *) q->o_maxt, (void *) q->d_eta, (void *) q->tp_pdf, (void *) q->res_flags, (void *) q->lp_lane, (void *) q->rng, (void *) q->tdepth,
-                         (void *) q->hit, (void *) q->w1, (void *) q->w2, (void *) q->w3, (void *) q->w4 }) D->release(p);
-        *q = DPathStreams{};
-    }
-    auto alloc = [&](size_t bytes) { void *p = nullptr; HIP_CHECK(hipMalloc(&p, bytes)); D->track(p); return p; };
-    for (DPathStreams *q : { &D->q[0], &D->q[1] }) {
-        q->o_maxt = (float4 *) alloc((size_t) capacity * 16); q->d_eta = (float4 *) alloc((size_t) capacity * 16); q->tp_pdf = (float4 *) alloc((size_t) capacity * 16);
-        q->res_flags = (float4 *) alloc((size_t) capacity * 16); q->lp_lane = (float4 *) alloc((size_t) capacity * 16);
-        q->rng = (uint2 *) alloc((size_t) capacity * 16); q->tdepth = (float2 *) alloc((size_t) capacity * 8);     // rng: 16 B per entry (compact records keep state | lane | sampler word there)
-        if (D->has_het || want_mis) q->hit = (float4 *) alloc((size_t) capacity * 16);
-        if (want_mis) for (float4 **w : { &q->w1, &q->w2, &q->w3, &q->w4 }) *w = (float4 *) alloc((size_t) capacity * 16);
-    }
-    D->capacity = capacity; D->mis_alloc = want_mis;
+    // (a row's pointer inside a DPathStreams: the members are pointers of different types, so it is read and written as bytes)
+    auto get = [](const DPathStreams *q, const RecordStream &r) { void *p; memcpy(&p, (const char *) q + r.member, sizeof p); return p; };
+    auto set = [](DPathStreams *q, const RecordStream &r, void *p) { memcpy((char *) q + r.member, &p, sizeof p); };
+    for (DPathStreams *q : { &D->q[0], &D->q[1] })
+        for (const RecordStream &r : kRecordStreams) if (r.member != kNoMember) { D->release(get(q, r)); set(q, r, nullptr); }
+    for (DPathStreams *q : { &D->q[0], &D->q[1] })             // one allocation per stream the layouts use, at its widest entry (rng: 16 bytes)
+        for (size_t k = 0; k < std::size(kRecordStreams); ++k) if (const uint32_t bytes = workspace_stream_bytes(k, layouts)) {
+            void *p = nullptr; HIP_CHECK(hipMalloc(&p, (size_t) capacity * bytes)); D->track(p); set(q, kRecordStreams[k], p);
+        }
+    D->capacity = capacity; D->ws_layouts = layouts;
 }
 
 static hipEvent_t get_event(DeviceScene *D, size_t i) {
@@ -532,17 +523,16 @@ static void run_wavefront(DeviceScene *D, const lrt_scene_desc &d, const Resolve
     const bool count_iter = !(O.integrator == LRT_INTEGRATOR_PATH && O.max_depth == 0);
     hipEvent_t a = get_event(D, log.ev++), b = get_event(D, log.ev++);
     HIP_CHECK(hipEventRecord(a, st));
-    if (prb) launch_prb<false>(D, rp, g, pixel_list, lane_begin, nullptr, nullptr, nullptr, film, sample_out);
+    if (prb) { stats.record_bytes = 0; launch_prb<false>(D, rp, g, pixel_list, lane_begin, nullptr, nullptr, nullptr, film, sample_out); }   // (not reported for the PRB kernels; not the last forward render's either)
     else {
         DLaunch a{}; a.rp = rp; a.li = D->lds; a.q0 = D->q[0]; a.q1 = D->q[1]; a.P = g.P; a.cnt = D->counters; a.pixel_list = pixel_list;
         a.lane_begin = lane_begin; a.n = n_lanes; a.film = film; a.sample_out = sample_out; a.sample_base = lane_begin;
-        // Compact records (kernels.h, store_state): only an area emitter's pdf reads the last scatter position, so a scene without one does not queue it.
+        // Compact records (record_layout.h): only an area emitter's pdf reads the last scatter position, so a scene without one does not queue it.
         // Instances exist for the 1024-thread LDS kernels of path / volpath (homogeneous media) / biovolpath / biovolpath06.  LRT_WIDE_RECORDS: developer switch.
         const bool compact = D->use_lds && !D->has_area_emitter && !D->ext && !getenv("LRT_WIDE_RECORDS") && O.integrator != LRT_INTEGRATOR_VOLPATHMIS && !(O.integrator == LRT_INTEGRATOR_VOLPATH && D->has_het);
         // 64-byte records (volpath only; LRT_NO_CLOSED_RECORDS: developer switch back to the 80-byte layout): decided per render, since
         // lrt_param_set can change sigma_t after the scene was loaded
         const bool closed = compact && O.integrator == LRT_INTEGRATOR_VOLPATH && closed_records(d, D->sc.cam.medium) && !getenv("LRT_NO_CLOSED_RECORDS");
-        a.rp.compact = compact ? 1u : 0u;
 #ifdef LRT_DEV_VOLPATH_ONLY
         if (D->ext) throw std::runtime_error("developer build: no EXT instances (spheres / point emitters)");
         if (!(D->use_lds && (O.integrator == LRT_DEV_INTEGRATOR || (LRT_DEV_INTEGRATOR == LRT_INTEGRATOR_VOLPATH_HET && D->has_het)) && (rp.ld_count != 0) == LRT_DEV_LD)) throw std::runtime_error("developer build: one integrator / sampler / LDS BVH only");
@@ -927,7 +917,7 @@ void device_render_backward(DeviceScene *D, const lrt_scene_desc &d, const lrt_r
     HIP_CHECK(hipMemcpyAsync(D->h_counters, D->counters, sizeof(DCounters), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     log.n_iter = D->h_counters->n_iter; log.n_records = D->h_counters->n_records;
-    finish_stats(D, log, e_begin, e_end, n_lanes, stats);
+    finish_stats(D, log, e_begin, e_end, n_lanes, stats); stats.record_bytes = 0;
     double h[7];
     HIP_CHECK(hipMemcpy(h, D->d_grads, sizeof(h), hipMemcpyDeviceToHost));
     for (int k = 0; k < 3; ++k) { out->d_sigma_t[k] = (float) h[k]; out->d_albedo[k] = (float) h[3 + k]; }

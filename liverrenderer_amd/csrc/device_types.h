@@ -169,7 +169,7 @@ struct DRenderParams {
     uint32_t tile_rank, tile_count;
     int32_t grad_medium;       // PRB adjoint: medium whose parameters are differentiated, -1: all media into one set
     uint32_t tiles_x, tiles_y, profile;   // profile: per-region tile timing into DCounters (developer aid, LRT_DEBUG_LAUNCH)
-    uint32_t compact;          // 80-byte records (scenes without area emitters: the last scatter position is never read): see store_state
+    uint32_t pad2;             // (keeps n_lanes at byte 72)
     uint64_t n_lanes;          // lanes this launch renders
     const uint32_t *pixel_slot; // tile-sharded renders: pixel -> index in the rank's pixel list (rank-local lane index), else null
     // multi-pass renders (integrator.cpp:176-184,275-293,343-353): spp above is the samples of ONE pass
@@ -178,25 +178,20 @@ struct DRenderParams {
     unsigned long long *pass_out;        // ... and where finished paths leave it for the next pass (null: last / only pass)
 };
 
-// Path-state streams (SoA, one float4 / uint2 per path and stream)
+// Path-state streams (SoA, one entry per path and stream)
 struct DPathStreams {
     float4 *o_maxt;            // ray origin, maxt
     float4 *d_eta;             // ray direction, eta
     float4 *tp_pdf;            // throughput rgb, last_scatter_direction_pdf
     float4 *res_flags;         // result rgb, packed flags (bits)
     float4 *lp_lane;           // last scatter position, lane id (bits)
-    uint2  *rng;               // PCG32 state
+    uint2  *rng;               // PCG32 state; the compact forms reinterpret it as uint4: state | lane | sampler word (the workspace allocates 16 bytes per entry)
     float2 *tdepth;            // biovolpath / biovolpath06 only: the loop state `tissueDepth` (sign bit: the cached competition was won by the hepatocytes), and the
                                // free-flight distance the look-ahead already drew for the next trip (NaN: none)
     float4 *hit;               // volpath with heterogeneous media / volpathmis: the surface interaction a null collision keeps (t, u, v, prim)
     float4 *w1, *w2, *w3, *w4; // volpathmis only: with tp_pdf, the 18 floats of p_over_f and p_over_f_nee
 };
-#define LRT_STATE_BYTES 88     // bytes per path record across all streams (path / volpath)
-#define LRT_STATE_BYTES_MIS 168 // volpathmis: o, d, res, lp, rng, hit + five float4 of MIS weights
-#define LRT_STATE_BYTES_HET 104 // volpath with heterogeneous media: + the kept surface hit (float4)
-#define LRT_STATE_BYTES_COMPACT 80 // path / volpath / biovolpath* without area emitters: the lane id and the sampler word ride with the generator state (store_state)
-#define LRT_STATE_BYTES_CLOSED 64 // volpath where only the last trip adds radiance: no radiance, no last-scatter pdf, the flags in the throughput's .w
-#define LRT_STATE_BYTES_BIO 96 // biovolpath*: + tissueDepth and the look-ahead's free-flight distance; the maxt slot carries the previous ray query's distance
+// (which layout uses which stream, and the bytes per record: record_layout.h)
 
 #define LRT_INTEGRATOR_VOLPATHMIS_PLAIN 102   // kernel selector: volpathmis with use_spectral_mis = false
 #define LRT_INTEGRATOR_VOLPATH_HET 101   // kernel selector (not an API value): volpath on a scene with heterogeneous media

@@ -12,6 +12,7 @@
 //   k_trace[_lds]     SoA ray queries (test hook, src/render/scene_native.inl:135-202)
 #pragma once
 #include "dshade.h"
+#include "record.h"
 
 namespace lrt {
 
@@ -25,89 +26,6 @@ struct StampClock {
     DEV void start(unsigned long long *a, bool enable) { acc = a; on = enable; t = on ? __builtin_amdgcn_s_memtime() : 0ull; }
     DEV void at(int k) { if (on) { const unsigned long long now = __builtin_amdgcn_s_memtime(); if ((threadIdx.x & 63u) == 0) atomicAdd(&acc[k], now - t); t = now; } }
 };
-
-struct PathState {
-    V3 o, d, tp, res, lp; float maxt, eta, last_pdf; uint32_t flags, lane; uint64_t rng_state;
-    uint32_t rng_word;         // compact records: the TEA word behind the lane's sampler stream (independent: v1, ld: v0), kept instead of recomputed every trip
-    float tdepth, si_t;        // biovolpath / biovolpath06: `tissueDepth`, distance returned by the previous trip's ray query
-    float ff_t;                // volpath (homogeneous media): the free-flight distance the look-ahead already drew for this trip (NaN: none); rides in the maxt slot
-    float bio_dist; bool bio_hep;   // biovolpath: the element competition the look-ahead already ran for this trip (distance, NaN = none; hepatocytes won)
-    float4 hit;                // volpath, heterogeneous media: the surface hit (t, u, v, prim) a null collision keeps (PF_HAVE_SI)
-    float W[2][3][3];          // volpathmis: p_over_f, p_over_f_nee
-};
-
-// BIO: a queued path's ray always comes from spawn_ray (maxt = largest float), so its maxt slot carries si_t instead, and
-// the seventh stream holds tissueDepth and the element competition the look-ahead already ran (96 B records)
-// MODE: 0 path / volpath (88 B), 1 biovolpath* (96 B), 2 volpath with heterogeneous media (104 B), 3 volpathmis (168 B),
-// 4 volpath where only a path's last trip adds radiance (64 B, always compact: o | ff_t, d | eta, tp | flags, state | lane | sampler word; no
-// radiance and no last-scatter pdf: see closed_records in device.hip)
-// A record as the stream loads return it.  Fetching (the loads) and unpacking (the first use of their results) are apart so that the
-// render kernel can ask for a tile's records while the previous tile is still being compacted and stored.
-struct RawState { float4 a, b, c, d, e; uint2 r; uint4 r4; float2 td; float4 hit, w1, w2, w3, w4; };
-template <int MODE = 0, typename QS>
-DEV void fetch_state(const QS &q, size_t i, RawState &w, bool compact = false) {
-    w.a = q.o_maxt[i]; w.b = q.d_eta[i]; w.c = q.tp_pdf[i];
-    if (MODE == 4) { w.r4 = reinterpret_cast<const uint4 *>(q.rng)[i]; return; }
-    w.d = q.res_flags[i];
-    if (compact) w.r4 = reinterpret_cast<const uint4 *>(q.rng)[i];                       // state | lane | sampler word: no last-scatter-position stream
-    else { w.e = q.lp_lane[i]; w.r = q.rng[i]; }
-    if (MODE == 1) w.td = q.tdepth[i];
-    if (MODE == 2 || MODE == 3) w.hit = q.hit[i];
-    if (MODE == 3) { w.w1 = q.w1[i]; w.w2 = q.w2[i]; w.w3 = q.w3[i]; w.w4 = q.w4[i]; }
-}
-template <int MODE = 0>
-DEV void unpack_state(const RawState &w, PathState &s, bool compact = false) {
-    if (MODE == 4) {
-        const float4 a = w.a, b = w.b, c = w.c; const uint4 r4 = w.r4;
-        s.o = V3(a.x, a.y, a.z); s.ff_t = a.w; s.maxt = kLargest; s.d = V3(b.x, b.y, b.z); s.eta = b.w;
-        s.tp = V3(c.x, c.y, c.z); s.flags = f2u(c.w); s.res = V3(0.f); s.lp = V3(0.f); s.last_pdf = 1.f;      // (last_pdf, lp: never read)
-        s.lane = r4.z; s.rng_word = r4.w; s.rng_state = ((uint64_t) r4.y << 32) | r4.x;
-        return;
-    }
-    const float4 a = w.a, b = w.b, c = w.c, d = w.d;
-    s.o = V3(a.x, a.y, a.z); s.maxt = a.w; s.d = V3(b.x, b.y, b.z); s.eta = b.w;
-    s.tp = V3(c.x, c.y, c.z); s.last_pdf = c.w; s.res = V3(d.x, d.y, d.z); s.flags = f2u(d.w);
-    if (compact) { const uint4 r4 = w.r4; s.lp = V3(0.f); s.lane = r4.z; s.rng_word = r4.w; s.rng_state = ((uint64_t) r4.y << 32) | r4.x; }
-    else { const float4 e = w.e; const uint2 r = w.r; s.lp = V3(e.x, e.y, e.z); s.lane = f2u(e.w); s.rng_state = ((uint64_t) r.y << 32) | r.x; }
-    if (MODE == 0) { s.ff_t = a.w; s.maxt = kLargest; }          // a queued ray always comes from spawn_ray: maxt = largest float
-    if (MODE == 1) { s.si_t = a.w; s.maxt = kLargest; const float2 td = w.td; s.tdepth = __builtin_fabsf(td.x); s.bio_hep = (f2u(td.x) >> 31) != 0u; s.bio_dist = td.y; }
-    if (MODE == 2 || MODE == 3) s.hit = w.hit;
-    if (MODE == 3) {
-        const float4 w1 = w.w1, w2 = w.w2, w3 = w.w3, w4 = w.w4;
-        float *W = &s.W[0][0][0];
-        W[0] = c.x; W[1] = c.y; W[2] = c.z; W[3] = c.w; W[4] = w1.x; W[5] = w1.y; W[6] = w1.z; W[7] = w1.w; W[8] = w2.x;
-        W[9] = w2.y; W[10] = w2.z; W[11] = w2.w; W[12] = w3.x; W[13] = w3.y; W[14] = w3.z; W[15] = w3.w; W[16] = w4.x; W[17] = w4.y;
-    }
-}
-template <int MODE = 0, typename QS>
-DEV void load_state(const QS &q, size_t i, PathState &s, bool compact = false) { RawState w; fetch_state<MODE>(q, i, w, compact); unpack_state<MODE>(w, s, compact); }
-template <int MODE = 0, typename QS>
-DEV void store_state(const QS &q, size_t i, const PathState &s, bool compact = false) {
-    if (MODE == 4) {
-        q.o_maxt[i] = make_float4(s.o.x, s.o.y, s.o.z, s.ff_t); q.d_eta[i] = make_float4(s.d.x, s.d.y, s.d.z, s.eta);
-        q.tp_pdf[i] = make_float4(s.tp.x, s.tp.y, s.tp.z, u2f(s.flags));
-        reinterpret_cast<uint4 *>(q.rng)[i] = make_uint4((uint32_t) s.rng_state, (uint32_t) (s.rng_state >> 32), s.lane, s.rng_word);
-        return;
-    }
-    q.o_maxt[i] = make_float4(s.o.x, s.o.y, s.o.z, MODE == 1 ? s.si_t : (MODE == 0 ? s.ff_t : s.maxt));
-    q.d_eta[i] = make_float4(s.d.x, s.d.y, s.d.z, s.eta);
-    if (MODE == 3) {
-        const float *W = &s.W[0][0][0];
-        q.tp_pdf[i] = make_float4(W[0], W[1], W[2], W[3]); q.w1[i] = make_float4(W[4], W[5], W[6], W[7]); q.w2[i] = make_float4(W[8], W[9], W[10], W[11]);
-        q.w3[i] = make_float4(W[12], W[13], W[14], W[15]); q.w4[i] = make_float4(W[16], W[17], 0.f, 0.f);
-    } else q.tp_pdf[i] = make_float4(s.tp.x, s.tp.y, s.tp.z, s.last_pdf);
-    q.res_flags[i] = make_float4(s.res.x, s.res.y, s.res.z, u2f(s.flags));
-    // Compact records (DRenderParams::compact: the scene has no area emitter, so pdf_emitter_direction never reads the last scatter position): the
-    // lane id and the sampler's TEA word ride with the generator state in one 16-byte word and the position stream is not touched: 80 B
-    // instead of 88, five memory instructions each way instead of six, and no TEA rounds at the start of a trip.
-    if (compact) reinterpret_cast<uint4 *>(q.rng)[i] = make_uint4((uint32_t) s.rng_state, (uint32_t) (s.rng_state >> 32), s.lane, s.rng_word);
-    else {
-        q.lp_lane[i] = make_float4(s.lp.x, s.lp.y, s.lp.z, u2f(s.lane));
-        q.rng[i] = make_uint2((uint32_t) s.rng_state, (uint32_t) (s.rng_state >> 32));
-    }
-    if (MODE == 1) q.tdepth[i] = make_float2(s.bio_hep ? -s.tdepth : s.tdepth, s.bio_dist);
-    if (MODE == 2 || MODE == 3) q.hit[i] = s.hit;
-}
 
 // Sampler::seed in the JIT branch of SamplingIntegrator::render (integrator.cpp:308-311): independent: TEA4(base + seed,
 // lane) seeds the PCG32 stream (sampler.cpp:129-148); ld: the sequence is the lane's pixel, scramble seed =
@@ -323,7 +241,7 @@ struct WaveCount {
 // of a camera lane's first trip), on the lane's own generator: same draws in the same order.  A queued record therefore holds a path
 // that is known to run its next trip, with the throughput already divided by the survival probability, the free-flight distance
 // in the record (ff_t) and, when the distance field proves that distance free of surfaces, PF_NOHIT.
-// CLOSED (64-byte records, MODE 4): the host has proven that only a path's last trip adds radiance (closed_records in device.hip): `result`
+// CLOSED (64-byte records, RecordLayout::Closed): the host has proven that only a path's last trip adds radiance (closed_records in device.hip): `result`
 // starts at 0 every trip and leaves in s.res for the film only; in-medium NEE, which the proof makes +0, is reduced to its draws and its
 // shadow-ray count; last_pdf and the last scatter position are never read.  The branches the same proof makes dead (surface NEE, the
 // hide_emitters skip, BSDFs other than a dielectric, emitters on shapes) are not compiled: closed_records, steps 4 to 8.  A trip that breaks the premise (nonzero radiance on a lane that
@@ -699,13 +617,8 @@ namespace lrt {
 //                          (Liver-MultiMesh with both kinds in one region: 17 of 64 lanes busy in an average traversal step)
 // n_a + n_b + n_c + n_l <= P, so the regions never collide.  No cross-workgroup dependency exists besides the lane ticket and the
 // film atomics; every wave leaves its loops once the ticket is exhausted and its pool is empty.
-template <typename QS> DEV DPathStreams offset_streams(const QS &q, size_t off) {
-    DPathStreams r; r.o_maxt = q.o_maxt + off; r.d_eta = q.d_eta + off; r.tp_pdf = q.tp_pdf + off; r.res_flags = q.res_flags + off; r.lp_lane = q.lp_lane + off; r.rng = q.rng + off; r.tdepth = q.tdepth + off; r.hit = q.hit + off; r.w1 = q.w1 + off; r.w2 = q.w2 + off; r.w3 = q.w3 + off; r.w4 = q.w4 + off;
-    return r;
-}
-
 // READLANE: how the three regions' slot bases reach the lanes (see below)
-template <int MODE = 0, bool READLANE = true, bool COMPACT = false, bool LONGQ = false>
+template <RecordLayout LAYOUT = RecordLayout::Wide, bool READLANE = true, bool COMPACT = false, bool LONGQ = false>
 DEV void retire_and_compact_wave(SceneRef sc, RpRef rp, bool had_path, bool alive, const PathState &s,
                                  float *__restrict__ film, float *__restrict__ sample_out, uint64_t sample_base,
                                  const LRT_CONST DPathStreams &qout, size_t pool, uint32_t P, uint32_t *s_out /* LDS [3] */, StampClock *clk = nullptr) {
@@ -734,7 +647,7 @@ DEV void retire_and_compact_wave(SceneRef sc, RpRef rp, bool had_path, bool aliv
     if (alive) {
         const unsigned long long mine = region == 0 ? m0 : (region == 1 ? m1 : ((!LONGQ || region == 2) ? m2 : m3));
         const uint32_t slot = b + (uint32_t) __popcll(mine & ((1ull << lane_in_wave) - 1ull));
-        store_state<MODE>(qout, pool + (region == 0 ? slot : (region == 1 ? P + slot : ((!LONGQ || region == 2) ? 2u * P - 1u - slot : P - 1u - slot))), s, COMPACT);
+        store_state<LAYOUT, COMPACT>(qout, pool + (region == 0 ? slot : (region == 1 ? P + slot : ((!LONGQ || region == 2) ? 2u * P - 1u - slot : P - 1u - slot))), s);
     }
     if (clk) clk->at(6);                                                // (stores issued)
     if (rp.pass_out && had_path && !alive) rp.pass_out[lane_local_index(rp, s.lane)] = s.rng_state;       // next pass continues this stream
@@ -743,7 +656,7 @@ DEV void retire_and_compact_wave(SceneRef sc, RpRef rp, bool had_path, bool aliv
 
 // 4 waves per SIMD (128 VGPRs): one 1024-thread workgroup per CU, or four 256-thread ones.  BLOCK = 512 (one workgroup per CU, 2 waves per
 // SIMD, 256 VGPRs): the wide-record integrators (volpathmis: 18 weights per path), which at 128 registers spill 430 B per lane
-// COMPACT: 80-byte records (store_state): the host launches these instances for scenes without area emitters (DRenderParams::compact)
+// COMPACT: the compact form of the layout (record_layout.h): the host launches these instances for scenes without area emitters
 // EXT: the scene holds spheres, point emitters or area emitters on meshes (ExtTracer, point- and mesh-emitter sampling, the mesh emitter's
 // pdf on the shading normal); the instances for triangles with rectangle / infinite emitters are unchanged
 template <int INTEGRATOR, int BLOCK, bool LDS_BVH, bool LD, bool COMPACT = false, bool EXT = false>
@@ -764,8 +677,8 @@ k_render(ScenePtr scp, LaunchPtr lp) {
     const uint32_t tid = threadIdx.x, lane_in_wave = tid & 63u;
     constexpr bool READLANE = INTEGRATOR != LRT_INTEGRATOR_PATH && INTEGRATOR != LRT_INTEGRATOR_BIOVOLPATH06;
     constexpr bool LONGQ = INTEGRATOR == LRT_INTEGRATOR_BIOVOLPATH;          // fourth queue region (retire_and_compact_wave)
-    constexpr bool CLOSED = INTEGRATOR == LRT_INTEGRATOR_VOLPATH_CLOSED;   // 64-byte records (MODE 4; the host launches these instances with COMPACT set)
-    constexpr int MODE = (INTEGRATOR == LRT_INTEGRATOR_BIOVOLPATH || INTEGRATOR == LRT_INTEGRATOR_BIOVOLPATH06) ? 1 : (INTEGRATOR == LRT_INTEGRATOR_VOLPATH_HET ? 2 : ((INTEGRATOR == LRT_INTEGRATOR_VOLPATHMIS || INTEGRATOR == LRT_INTEGRATOR_VOLPATHMIS_PLAIN) ? 3 : (CLOSED ? 4 : 0)));
+    constexpr bool CLOSED = INTEGRATOR == LRT_INTEGRATOR_VOLPATH_CLOSED;   // 64-byte records (the host launches these instances with COMPACT set)
+    constexpr RecordLayout LAYOUT = record_layout(INTEGRATOR);
     if (tid < 8) s_prof[tid] = 0;
     const unsigned long long t_wg_start = (rp.profile & 1u) ? wall_clock64() : 0ull;
     unsigned long long t_loop_start = 0ull, t_barrier = 0ull;
@@ -831,7 +744,7 @@ k_render(ScenePtr scp, LaunchPtr lp) {
                 else if (t < ta + tc) { i = ((t - ta) << 6) + lane_in_wave; had_path = i < n_c; i += P; }
                 else if (LONGQ && t < ta + tcl) { i = ((t - ta - tc) << 6) + lane_in_wave; had_path = i < n_l; i = P - 1u - i; }
                 else { i = ((t - ta - tcl) << 6) + lane_in_wave; had_path = i < n_b; i = 2u * P - 1u - i; }
-                if (had_path) { load_state<MODE>(parity ? A.q1 : A.q0, pool + i, s, COMPACT); if (!VP_LDS_COUNT) n_loaded += 1; }
+                if (had_path) { load_state<LAYOUT, COMPACT>(parity ? A.q1 : A.q0, pool + i, s); if (!VP_LDS_COUNT) n_loaded += 1; }
             } else {
                 const uint32_t i = ((t - ta - tcl - tb) << 6) + lane_in_wave;
                 had_path = i < fresh;
@@ -870,11 +783,11 @@ k_render(ScenePtr scp, LaunchPtr lp) {
                 if (!VP_LDS_COUNT) n_trips += 1;
             }
 #ifdef LRT_STAMP
-            retire_and_compact_wave<MODE, READLANE, COMPACT, LONGQ>(sc, rp, had_path, alive, s, A.film, A.sample_out, A.sample_base, parity ? A.q0 : A.q1, pool, P, s_out, &clk);
+            retire_and_compact_wave<LAYOUT, READLANE, COMPACT, LONGQ>(sc, rp, had_path, alive, s, A.film, A.sample_out, A.sample_base, parity ? A.q0 : A.q1, pool, P, s_out, &clk);
             clk.at(7);                                                  // film sums + atomics
             if (clk.on && lane_in_wave == 0) atomicAdd(&s_stamp[15], 1ull);
 #else
-            retire_and_compact_wave<MODE, READLANE, COMPACT, LONGQ>(sc, rp, had_path, alive, s, A.film, A.sample_out, A.sample_base, parity ? A.q0 : A.q1, pool, P, s_out);
+            retire_and_compact_wave<LAYOUT, READLANE, COMPACT, LONGQ>(sc, rp, had_path, alive, s, A.film, A.sample_out, A.sample_base, parity ? A.q0 : A.q1, pool, P, s_out);
 #endif
             if ((rp.profile & 1u) && lane_in_wave == 0) {
                 const int region = t < ta ? 0 : (t < ta + tcl ? 1 : (t < ta + tcl + tb ? 2 : 3));

@@ -1,6 +1,6 @@
 // The body of k_render_prb and k_render_prb_grid (kernels_prb.h), included inside each kernel: no include guard, not a header of its own.
 // In scope: scp, lp and the constants ADJOINT, BLOCK, LDS_BVH, LD, HET, GRID.
-    constexpr int MODE = HET ? 2 : 0;
+    constexpr RecordLayout LAYOUT = record_layout(HET ? LRT_INTEGRATOR_VOLPATH_HET : LRT_INTEGRATOR_PRBVOLPATH);      // + the delta_L stream (record_layout.h)
     SceneRef sc = *scp;
     const LRT_CONST DLaunch &A = *lp;
     RpRef rp = A.rp;
@@ -59,7 +59,7 @@
                 if (t < ta) { i = (t << 6) + lane_in_wave; had_path = i < n_a; }
                 else if (t < tm) { i = ((t - ta) << 6) + lane_in_wave; had_path = i < n_c; i += P; }
                 else { i = ((t - tm) << 6) + lane_in_wave; had_path = i < n_s; i = 2u * P - 1u - i; }
-                if (had_path) { load_state<MODE>(parity ? A.q1 : A.q0, pool + i, s); dl = (parity ? A.dl1 : A.dl0)[pool + i]; n_loaded += 1; }
+                if (had_path) { load_state<LAYOUT>(parity ? A.q1 : A.q0, pool + i, s); dl = (parity ? A.dl1 : A.dl0)[pool + i]; n_loaded += 1; }
             } else {
                 const uint32_t i = ((t - tm - ts) << 6) + lane_in_wave;
                 had_path = i < fresh;
@@ -101,7 +101,7 @@
             if (alive) {
                 const uint32_t slot = b + (uint32_t) __popcll((region == 0 ? m0 : (region == 1 ? m1 : m2)) & ((1ull << lane_in_wave) - 1ull));
                 const uint32_t rec = region == 0 ? slot : (region == 1 ? P + slot : 2u * P - 1u - slot);
-                store_state<MODE>(parity ? A.q0 : A.q1, pool + rec, s); (parity ? A.dl0 : A.dl1)[pool + rec] = dl;
+                store_state<LAYOUT>(parity ? A.q0 : A.q1, pool + rec, s); (parity ? A.dl0 : A.dl1)[pool + rec] = dl;
             }
         }
         __syncthreads();

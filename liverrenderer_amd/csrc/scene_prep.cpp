@@ -480,7 +480,7 @@ std::vector<uint32_t> halo_pixel_list(const DFilm &F, uint32_t rank, uint32_t co
     return px;
 }
 
-// 64-byte path records (kernels.h, MODE 4; instances k_render<LRT_INTEGRATOR_VOLPATH_CLOSED, ...>): volpath on a scene where only a path's last
+// 64-byte path records (record_layout.h, RecordLayout::Closed; instances k_render<LRT_INTEGRATOR_VOLPATH_CLOSED, ...>): volpath on a scene where only a path's last
 // trip can add radiance, so that a record carries no radiance and no last-scatter pdf.  Called for every render with the current scene
 // description (lrt_param_set may have changed sigma_t since the load); the caller also requires compact records (no area emitter, no EXT
 // scene, BVH in LDS) and the volpath integrator.  Conditions:

@@ -1,4 +1,4 @@
-"""The 64-byte-record volpath kernels (kernels.h MODE 4) compile only what closed_records() in device.hip leaves reachable (DESIGN.md section
+"""The 64-byte-record volpath kernels (record_layout.h, RecordLayout::Closed) compile only what closed_records() in device.hip leaves reachable (DESIGN.md section
 6d): read from the built library's gfx950 code object, no GPU needed.
 
 Both instances must hold every value of the trip in registers (no scratch, no spilled VGPR) at 4 waves per SIMD (at most 128 VGPRs), and

@@ -1,4 +1,4 @@
-"""64-byte path records (kernels.h MODE 4, closed_records() in device.hip): volpath on a scene where only a path's last trip adds
+"""64-byte path records (record_layout.h, RecordLayout::Closed; closed_records() in device.hip): volpath on a scene where only a path's last trip adds
 radiance queues no radiance and no last-scatter pdf.  Liver-SingleMesh qualifies (one dielectric-bounded homogeneous medium, one envmap).
 The layout must change nothing but speed: lanes bit-identical to the 80-byte layout (LRT_NO_CLOSED_RECORDS) and to the oracle, the same
 trips, shadow rays and records, the film equal up to the order of the float atomics.  Scenes that do not qualify keep 80 / 88 B."""

@@ -1,4 +1,4 @@
-"""Register budget of the 64-byte-record C3 kernels (kernels.h MODE 4), read from the built library's gfx950 code object (no GPU needed).
+"""Register budget of the 64-byte-record C3 kernels (record_layout.h, RecordLayout::Closed), read from the built library's gfx950 code object (no GPU needed).
 
 k_render<LRT_INTEGRATOR_VOLPATH_CLOSED, 1024, LDS BVH, {independent, ld} sampler, compact> must keep 4 waves per SIMD (at most 128 VGPRs)
 and the scratch area the smaller record leaves (the 80-byte C3 kernel needs 80 B): spills that come back show up

@@ -125,7 +125,7 @@ def test_liver_volpath_hg_and_params_bit_exact(mi, orc):
 
 def test_compact_and_wide_records_agree(mi, monkeypatch):
     """A scene without area emitters queues 80-byte records (no last scatter position, the sampler's TEA word kept instead of recomputed:
-    kernels.h, store_state); LRT_WIDE_RECORDS forces the 88-byte layout.  Same lanes, trips and shadow rays either way, for the independent
+    record.h, store_state); LRT_WIDE_RECORDS forces the 88-byte layout.  Same lanes, trips and shadow rays either way, for the independent
     and the ld sampler, volpath / path / the bio integrators; a scene WITH an area emitter (Cornell) is not affected by the switch."""
     import os
     cases = [(LIVER_XML, dict(integrator="volpath", spp=16, res_width=128, res_height=72)), (LIVER_XML, dict(integrator="path", spp=16, res_width=128, res_height=72)),
