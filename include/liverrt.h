@@ -56,7 +56,7 @@ enum { LRT_INTEGRATOR_PATH = 0, LRT_INTEGRATOR_VOLPATH = 1, LRT_INTEGRATOR_PRBVO
 /* medium plugins: src/media/homogeneous.cpp, liver.cpp, parenchyma.cpp, glissonCapsule.cpp (docs/BIO_TRANSPORT_SPEC.md) */
 enum { LRT_MEDIUM_HOMOGENEOUS = 0, LRT_MEDIUM_LIVER = 1, LRT_MEDIUM_PARENCHYMA = 2, LRT_MEDIUM_GLISSON = 3,
        LRT_MEDIUM_HETEROGENEOUS = 4   /* src/media/heterogeneous.cpp: sigma_t from a grid volume, delta tracking */ };
-enum { LRT_BSDF_DIFFUSE = 0, LRT_BSDF_DIELECTRIC = 1, LRT_BSDF_BUMPMAP = 2, LRT_BSDF_NULL = 3 };
+enum { LRT_BSDF_DIFFUSE = 0, LRT_BSDF_DIELECTRIC = 1, LRT_BSDF_BUMPMAP = 2, LRT_BSDF_NULL = 3, LRT_BSDF_ROUGHDIELECTRIC = 4 };
 enum { LRT_TEX_RGB = 0, LRT_TEX_CHECKERBOARD = 1, LRT_TEX_BITMAP = 2 };
 enum { LRT_PHASE_ISOTROPIC = 0, LRT_PHASE_HG = 1 };
 enum { LRT_EMITTER_AREA = 0, LRT_EMITTER_ENVMAP = 1, LRT_EMITTER_CONSTANT = 2,
@@ -106,10 +106,16 @@ typedef struct {
 typedef struct {
     int32_t type;             /* LRT_BSDF_*                                        */
     int32_t reflectance;      /* texture index (diffuse)                           */
-    float   eta;              /* int_ior / ext_ior (dielectric)                    */
+    float   eta;              /* int_ior / ext_ior (dielectric, roughdielectric)   */
     int32_t nested;           /* bumpmap: nested bsdf index                        */
     int32_t texture;          /* bumpmap: height texture index                     */
     float   scale;            /* bumpmap scale                                     */
+    /* [v114] roughdielectric (src/bsdfs/roughdielectric.cpp); ignored by the other types */
+    float   alpha_u, alpha_v; /* roughness along the tangent / bitangent; values below 1e-4 are raised to it (microfacet.h:425-428) */
+    int32_t distribution;     /* 0: beckmann, 1: ggx                               */
+    int32_t sample_visible;   /* visible-normal sampling (Heitz and d'Eon)         */
+    int32_t specular_reflectance;    /* texture index (rgb or checkerboard), -1: none */
+    int32_t specular_transmittance;  /* texture index (rgb or checkerboard), -1: none */
 } lrt_bsdf_desc;
 
 typedef struct {
@@ -255,7 +261,7 @@ typedef struct {
 typedef struct lrt_scene lrt_scene;
 
 LRT_API const char *lrt_last_error(void);
-LRT_API int         lrt_version(void);   /* 113: lrt_bsdf_probe; 112:lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
+LRT_API int         lrt_version(void);   /* 114: the roughdielectric BSDF (LRT_BSDF_ROUGHDIELECTRIC, the fields after `scale` of lrt_bsdf_desc), lrt_math_eval fn 9 / 10; 113: lrt_bsdf_probe; 112:lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
 
 LRT_API lrt_status lrt_scene_load_xml(const char *path, const char *const *defines,
                                       int n_defines, lrt_scene **out);
@@ -324,7 +330,8 @@ LRT_API lrt_status lrt_render_backward_multi(lrt_scene *scene, const lrt_render_
 
 /* Test hook [v104]: the device's own log / exp / sincos / atan2 / acos / log2 kernels (csrc/dmath.h: the arithmetic every path value
  * goes through, standing in for Dr.Jit's dr::log / dr::exp / ... of include/mitsuba/core/math.h users) and its division / sqrt / rcp,
- * one value per lane.  fn: 0 log(x), 1 exp(x), 2 sincos(x) -> out, out2, 3 atan2(y, x), 4 acos(x), 5 log2(x), 6 x / y, 7 sqrt(x), 8 1 / x. */
+ * one value per lane.  fn: 0 log(x), 1 exp(x), 2 sincos(x) -> out, out2, 3 atan2(y, x), 4 acos(x), 5 log2(x), 6 x / y, 7 sqrt(x), 8 1 / x,
+ * [v114] 9 erf(x), 10 erfinv(x) (Beckmann's visible-normal sampling, csrc/dshade.h). */
 LRT_API lrt_status lrt_math_eval(int fn, const float *x, const float *y, uint32_t n, float *out, float *out2, int device);
 
 /* Test hook [v107]: Scene::sample_emitter_direction of the render kernels that serve spheres, point emitters and mesh

@@ -118,7 +118,7 @@ _TAGS = {
     "biovolpath": "integrator", "biovolpath06": "integrator", "volpathmis": "integrator",
     "perspective": "sensor", "independent": "sampler", "ldsampler": "sampler", "hdrfilm": "film",
     "box": "rfilter", "gaussian": "rfilter", "tent": "rfilter",
-    "diffuse": "bsdf", "dielectric": "bsdf", "bumpmap": "bsdf", "null": "bsdf",
+    "diffuse": "bsdf", "dielectric": "bsdf", "bumpmap": "bsdf", "null": "bsdf", "roughdielectric": "bsdf",
     "bitmap": "texture", "checkerboard": "texture",
     "homogeneous": "medium", "liver": "medium", "parenchyma": "medium", "glissonCapsule": "medium", "heterogeneous": "medium",
     "gridvolume": "volume",

@@ -32,7 +32,9 @@ class TextureDesc(C.Structure):
 
 class BsdfDesc(C.Structure):
     _fields_ = [("type", C.c_int32), ("reflectance", C.c_int32), ("eta", C.c_float), ("nested", C.c_int32),
-                ("texture", C.c_int32), ("scale", C.c_float)]
+                ("texture", C.c_int32), ("scale", C.c_float),
+                ("alpha_u", C.c_float), ("alpha_v", C.c_float), ("distribution", C.c_int32), ("sample_visible", C.c_int32),
+                ("specular_reflectance", C.c_int32), ("specular_transmittance", C.c_int32)]      # [v114] roughdielectric
 
 
 class MediumDesc(C.Structure):

@@ -96,7 +96,7 @@ struct DeviceScene {
     std::vector<DMedium> h_media; DMedium *d_media = nullptr;
     std::vector<DBioMedium> h_bio; DBioMedium *d_bio = nullptr;
     std::vector<DHetMedium> h_het; DHetMedium *d_het = nullptr; std::vector<float *> het_data; bool has_het = false, has_non_bio = false, need_mis = false; uint32_t ws_layouts = 0;   // ws_layouts: the record layouts the workspace is allocated for (layout_bit mask)
-    bool ext = false;                      // spheres, point emitters or area emitters on meshes: the EXT kernel instances (ExtTracer, point- / mesh-emitter sampling), wide records
+    bool ext = false;                      // spheres, point emitters, area emitters on meshes or a roughdielectric on a shape: the EXT kernel instances (ExtTracer, point- / mesh-emitter sampling, the rough BSDF), wide records
     bool has_area_emitter = false;         // decides the record layout: only an area emitter's pdf reads the last scatter position (record_layout.h)
     float *dgrid = nullptr; size_t dgrid_floats = 0;   // lrt_render_backward_grid with a host result: the device-side gradient grid
     bool prb_null = false;                 // prbvolpath.py:84-91 `handle_null_scattering`: a heterogeneous medium is attached to a shape
@@ -484,7 +484,7 @@ static void check_integrator_media(DeviceScene *D, int integrator) {
     if ((integrator == LRT_INTEGRATOR_BIOVOLPATH || integrator == LRT_INTEGRATOR_BIOVOLPATH06) && D->has_non_bio)
         throw std::runtime_error("NotImplementedError: sample_interaction (the bio integrators need liver / parenchyma / glissonCapsule media)");
     if (integrator == LRT_INTEGRATOR_PRBVOLPATH && D->ext)
-        throw std::runtime_error("unsupported: prbvolpath on a scene with sphere shapes, point emitters or area emitters on meshes (its adjoint is built for triangles and rectangle / infinite emitters)");
+        throw std::runtime_error("unsupported: prbvolpath on a scene with sphere shapes, point emitters, area emitters on meshes or a roughdielectric BSDF (its adjoint is built for triangles, rectangle / infinite emitters and the diffuse / dielectric / null BSDFs)");
     if (integrator == LRT_INTEGRATOR_VOLPATHMIS) D->need_mis = true;          // its wider path record is allocated on first use
 }
 
@@ -1132,13 +1132,15 @@ __global__ void k_math_eval(int fn, const float *__restrict__ x, const float *__
         case 6: a = x[i] / y[i]; break;
         case 7: a = __builtin_sqrtf(x[i]); break;
         case 8: a = rcp(x[i]); break;
+        case 9: a = m_erf(x[i]); break;
+        case 10: a = m_erfinv(x[i]); break;
         default: break;
     }
     out[i] = a; out2[i] = b;
 }
 void device_math_eval(int fn, const float *x, const float *y, uint32_t n, float *out, float *out2, int device) {
     select_device(device);
-    if (fn < 0 || fn > 8) throw std::invalid_argument("lrt_math_eval: function 0 .. 8");
+    if (fn < 0 || fn > 10) throw std::invalid_argument("lrt_math_eval: function 0 .. 10");
     if (!n) return;
     DevTmp dx(n), dy(n), d1(n), d2(n);
     HIP_CHECK(hipMemcpy(dx.p, x, (size_t) n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dy.p, y ? y : x, (size_t) n * 4, hipMemcpyHostToDevice));

@@ -12,10 +12,21 @@ struct DShape {
     int32_t has_normals, has_texcoords, flip_normals, kind;
 };
 
+// 32 bytes, as before the roughdielectric: its fields live in the words it leaves unused (a diffuse reflectance, a bumpmap's nested
+// BSDF, height texture and scale), so the table stride and every other BSDF's loads stay what they were.
+#define LRT_MICRO_GGX 1        // DBsdf::micro: distribution (else beckmann)
+#define LRT_MICRO_VISIBLE 2    //               sample_visible
 struct DBsdf {
-    int32_t type, reflectance, nested, texture;
-    float eta, scale; int32_t flags, pad;
+    int32_t type;
+    union { int32_t reflectance; int32_t specular_reflectance; };     // texture index; roughdielectric: -1 = none
+    union { int32_t nested; int32_t micro; };                         // roughdielectric: LRT_MICRO_* bits
+    union { int32_t texture; int32_t specular_transmittance; };
+    float eta;
+    union { float scale; float alpha_u; };                            // roughdielectric: alphas, clamped to >= 1e-4 by the host
+    int32_t flags;
+    union { int32_t pad; float alpha_v; };
 };
+static_assert(sizeof(DBsdf) == 32, "DBsdf stride");
 
 struct DTexture {
     int32_t type, width, height, channels;

@@ -615,10 +615,241 @@ DEV float shadow_terminator(V3 pn, V3 wo) {       // src/bsdfs/normalmap_helpers
     return 2.f / (1.f + __builtin_sqrtf(1.f + alpha2 * tan_theta_2(wo)));
 }
 
-// Leaf BSDFs (diffuse / dielectric / null), evaluated in the frame `wi` is given in.
+// ------------------------------------------------- roughdielectric (src/bsdfs/roughdielectric.cpp)
+// Compiled into the EXT instances, k_bsdf_probe and k_math_eval alone (leaf_sample / leaf_eval / leaf_pdf below).
+// erf: |x| < 1 the odd polynomial of Cephes' single-precision erff (ndtrf.c, table T), beyond it Abramowitz & Stegun 7.1.26
+// (|error| <= 1.5e-7).  erfinv: M. Giles, "Approximating the erfinv function" (GPU Computing Gems, Jade edition, 2012), the
+// single-precision pair of polynomials in w = -log((1 - x)(1 + x)).  Both stand in for Dr.Jit's dr::erf / dr::erfinv
+// (microfacet.h:382-404); they are held to float64 through lrt_math_eval fn 9 / 10.
+DEV float m_erf(float x) {
+    const float a = __builtin_fabsf(x);
+    if (a < 1.f) {
+        const float z = x * x;
+        float p = 7.853861353153693E-5f;
+        p = fma_(p, z, -8.010193625184903E-4f);
+        p = fma_(p, z, 5.188327685732524E-3f);
+        p = fma_(p, z, -2.685381193529856E-2f);
+        p = fma_(p, z, 1.128358514861418E-1f);
+        p = fma_(p, z, -3.761262582423300E-1f);
+        p = fma_(p, z, 1.128379165726710E+0f);
+        return x * p;
+    }
+    const float t = rcp(fma_(0.3275911f, a, 1.f));
+    float q = 1.061405429f;
+    q = fma_(q, t, -1.453152027f);
+    q = fma_(q, t, 1.421413741f);
+    q = fma_(q, t, -0.284496736f);
+    q = fma_(q, t, 0.254829592f);
+    const float r = fma_(-(q * t), m_exp(-(a * a)), 1.f);
+    return mulsign(r, x);                        // (NaN stays NaN: the comparison above fails, t and r are NaN)
+}
+DEV float m_erfinv(float x) {
+    float w = -m_log((1.f - x) * (1.f + x)), p;
+    if (w < 5.f) {
+        w -= 2.5f;
+        p = 2.81022636e-08f;
+        p = fma_(p, w, 3.43273939e-07f);
+        p = fma_(p, w, -3.5233877e-06f);
+        p = fma_(p, w, -4.39150654e-06f);
+        p = fma_(p, w, 0.00021858087f);
+        p = fma_(p, w, -0.00125372503f);
+        p = fma_(p, w, -0.00417768164f);
+        p = fma_(p, w, 0.246640727f);
+        p = fma_(p, w, 1.50140941f);
+    } else {
+        w = __builtin_sqrtf(w) - 3.f;
+        p = -0.000200214257f;
+        p = fma_(p, w, 0.000100950558f);
+        p = fma_(p, w, 0.00134934322f);
+        p = fma_(p, w, -0.00367342844f);
+        p = fma_(p, w, 0.00573950773f);
+        p = fma_(p, w, -0.0076224613f);
+        p = fma_(p, w, 0.00943887047f);
+        p = fma_(p, w, 1.00167406f);
+        p = fma_(p, w, 2.83297682f);
+    }
+    return p * x;
+}
+
+// MicrofacetDistribution (include/mitsuba/render/microfacet.h:174-440).  One set-up (microfacet_of) serves sample, eval and pdf.
+struct Microfacet {
+    float au, av; bool ggx, visible;
+    DEV void scale_alpha(float v) { au *= v; av *= v; }                           // :174-177
+    DEV float eval(V3 m) const {                                                  // :185-207
+        const float alpha_uv = au * av, cos_theta = m.z, cos_theta_2 = sqr(cos_theta);
+        const float e = sqr(m.x / au) + sqr(m.y / av);
+        float result;
+        if (!ggx) result = m_exp(-e / cos_theta_2) / (kPi * alpha_uv * sqr(cos_theta_2));
+        else result = rcp(kPi * alpha_uv * sqr(e + sqr(m.z)));
+        return result * cos_theta > 1e-20f ? result : 0.f;
+    }
+    DEV float smith_g1(V3 v, V3 m) const {                                        // :341-365
+        const float xy_alpha_2 = sqr(au * v.x) + sqr(av * v.y), tan_theta_alpha_2 = xy_alpha_2 / sqr(v.z);
+        float result;
+        if (!ggx) {
+            const float a = rsqrt_(tan_theta_alpha_2), a_sqr = sqr(a);
+            result = a >= 1.6f ? 1.f : (3.535f * a + 2.181f * a_sqr) / (1.f + 2.276f * a + 2.577f * a_sqr);
+        } else result = 2.f / (1.f + __builtin_sqrtf(1.f + tan_theta_alpha_2));
+        if (xy_alpha_2 == 0.f) result = 1.f;
+        if (dot(v, m) * v.z <= 0.f) result = 0.f;
+        return result;
+    }
+    DEV float G(V3 wi, V3 wo, V3 m) const { return smith_g1(wi, m) * smith_g1(wo, m); }   // :329-331
+    DEV float pdf(V3 wi, V3 m) const {                                            // :219-228
+        float result = eval(m);
+        if (visible) result *= smith_g1(wi, m) * __builtin_fabsf(dot(wi, m)) / wi.z;
+        else result *= m.z;
+        return result;
+    }
+    // sin_theta_i: of the same direction, from the caller (formed as sqrt(x^2 + y^2), which keeps its relative accuracy near normal incidence where
+    // the reference's sqrt(1 - cos^2) cancels)
+    DEV V2 sample_visible_11(float cos_theta_i, float sin_theta_i, float sx, float sy) const {        // :368-421
+        if (!ggx) {
+            const float tan_theta_i = sin_theta_i / cos_theta_i, cot_theta_i = rcp(tan_theta_i);
+            const float maxval = m_erf(cot_theta_i);
+            sx = fmax_(fmin_(sx, 1.f - 1e-6f), 1e-6f); sy = fmax_(fmin_(sy, 1.f - 1e-6f), 1e-6f);
+            float x = maxval - (maxval + 1.f) * m_erf(__builtin_sqrtf(-m_log(sx)));
+            const float kInvSqrtPi = 0.56418958354775628695f;
+            sx *= 1.f + maxval + kInvSqrtPi * tan_theta_i * m_exp(-sqr(cot_theta_i));
+            for (int i = 0; i < 3; ++i) {                                         // three Newton steps
+                const float slope = m_erfinv(x);
+                const float value = 1.f + x + kInvSqrtPi * tan_theta_i * m_exp(-sqr(slope)) - sx, derivative = 1.f - slope * tan_theta_i;
+                x -= value / derivative;
+            }
+            return { m_erfinv(x), m_erfinv(fma_(2.f, sy, -1.f)) };
+        }
+        V2 p = square_to_uniform_disk_concentric(sx, sy);
+        const float s = .5f * (1.f + cos_theta_i);
+        p.y = lerpf(safe_sqrt(1.f - sqr(p.x)), p.y, s);
+        const float x = p.x, y = p.y, z = safe_sqrt(1.f - fma_(p.x, p.x, p.y * p.y));
+        const float nrm = rcp(fma_(sin_theta_i, y, cos_theta_i * z));
+        return { fma_(cos_theta_i, y, -(sin_theta_i * z)) * nrm, x * nrm };
+    }
+    DEV V3 sample(V3 wi, float sx, float sy, float *pdf_out) const {               // :244-326
+        if (!visible) {
+            float sin_phi, cos_phi, cos_theta, cos_theta_2, alpha_2, pdf, tan_theta_2;
+            if (au == av) {
+                m_sincos(kTwoPi * sy, &sin_phi, &cos_phi);
+                alpha_2 = au * au;
+            } else {
+                float st, ct; m_sincos(kTwoPi * sy, &st, &ct);                  // (dr::tan)
+                const float ratio = av / au, tmp = ratio * (st / ct);
+                cos_phi = rsqrt_(fma_(tmp, tmp, 1.f));
+                cos_phi = mulsign(cos_phi, __builtin_fabsf(sy - .5f) - .25f);
+                sin_phi = cos_phi * tmp;
+                alpha_2 = rcp(sqr(cos_phi / au) + sqr(sin_phi / av));
+            }
+            if (!ggx) {
+                const float lg = m_log(1.f - sx);
+                tan_theta_2 = -alpha_2 * lg;
+                cos_theta = rsqrt_(fma_(-alpha_2, lg, 1.f));
+                cos_theta_2 = sqr(cos_theta);
+                const float cos_theta_3 = fmax_(cos_theta_2 * cos_theta, 1e-20f);
+                pdf = (1.f - sx) / (kPi * au * av * cos_theta_3);
+            } else {
+                const float tan_theta_m_2 = alpha_2 * sx / (1.f - sx);
+                tan_theta_2 = tan_theta_m_2;
+                cos_theta = rsqrt_(1.f + tan_theta_m_2);
+                cos_theta_2 = sqr(cos_theta);
+                const float temp = 1.f + tan_theta_m_2 / alpha_2, cos_theta_3 = fmax_(cos_theta_2 * cos_theta, 1e-20f);
+                pdf = rcp(kPi * au * av * cos_theta_3 * sqr(temp));
+            }
+            // sin = tan cos, not the reference's sqrt(1 - cos^2): equal, but that one cancels for a small alpha (at the clamp 1e-4 float32 returns
+            // the surface normal itself while the pdf keeps its 1 - s_x: weight * pdf then misses eval at the sampled wo by orders of magnitude)
+            const float sin_theta = __builtin_sqrtf(tan_theta_2) * cos_theta;
+            *pdf_out = pdf;
+            return V3(cos_phi * sin_theta, sin_phi * sin_theta, cos_theta);
+        }
+        const V3 wi_p = normalize(V3(au * wi.x, av * wi.y, wi.z));               // stretch
+        const float sin_theta_2 = fma_(wi_p.x, wi_p.x, wi_p.y * wi_p.y), inv_sin_theta = rsqrt_(sin_theta_2);   // Frame3f::sincos_phi (frame.h:111-122); 1 - z^2 there: see sample_visible_11
+        float cos_phi = clampf(wi_p.x * inv_sin_theta, -1.f, 1.f), sin_phi = clampf(wi_p.y * inv_sin_theta, -1.f, 1.f);
+        if (__builtin_fabsf(sin_theta_2) <= 4.f * kEpsilon) { cos_phi = 1.f; sin_phi = 0.f; }
+        const V2 s11 = sample_visible_11(wi_p.z, __builtin_sqrtf(sin_theta_2), sx, sy);
+        const float slx = fma_(cos_phi, s11.x, -(sin_phi * s11.y)) * au, sly = fma_(sin_phi, s11.x, cos_phi * s11.y) * av;   // rotate, unstretch
+        const V3 m = normalize(V3(-slx, -sly, 1.f));
+        *pdf_out = eval(m) * smith_g1(wi, m) * __builtin_fabsf(dot(wi, m)) / wi.z;
+        return m;
+    }
+};
+DEV Microfacet microfacet_of(const DBsdf &B) { Microfacet d; d.au = B.alpha_u; d.av = B.alpha_v; d.ggx = (B.micro & LRT_MICRO_GGX) != 0; d.visible = (B.micro & LRT_MICRO_VISIBLE) != 0; return d; }
+
+// roughdielectric.cpp:242-358 sample(), radiance mode, both lobes enabled
+DEV BSDFSample rough_sample(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, float s1, float s2x, float s2y) {
+    BSDFSample bs;
+    bs.wo = V3(0.f); bs.pdf = 0.f; bs.eta = 0.f; bs.type = 0; bs.weight = V3(0.f);
+    const float cos_theta_i = wi.z;
+    bool active = cos_theta_i != 0.f;
+    const Microfacet distr = microfacet_of(B);
+    Microfacet sample_distr = distr;
+    if (!distr.visible) sample_distr.scale_alpha(1.2f - .2f * __builtin_sqrtf(__builtin_fabsf(cos_theta_i)));
+    float pdf;
+    const V3 m = sample_distr.sample(V3(mulsign(wi.x, cos_theta_i), mulsign(wi.y, cos_theta_i), mulsign(wi.z, cos_theta_i)), s2x, s2y, &pdf);
+    active = active && pdf != 0.f;
+    float F, cos_theta_t, eta_it, eta_ti;
+    const float wi_m = dot(wi, m);
+    fresnel(wi_m, B.eta, &F, &cos_theta_t, &eta_it, &eta_ti);
+    const bool selected_r = s1 <= F && active;
+    pdf *= selected_r ? F : 1.f - F;
+    bs.eta = selected_r ? 1.f : eta_it;
+    bs.type = F_SMOOTH;                                                         // GlossyReflection / GlossyTransmission: both smooth
+    V3 weight(1.f); float dwh_dwo;
+    if (selected_r) {
+        bs.wo = V3(fma_(m.x, 2.f * wi_m, -wi.x), fma_(m.y, 2.f * wi_m, -wi.y), fma_(m.z, 2.f * wi_m, -wi.z));      // reflect(wi, m), fresnel.h:282-284
+        if (B.specular_reflectance >= 0) weight = tex_eval(sc, B.specular_reflectance, si);
+        dwh_dwo = rcp(4.f * dot(bs.wo, m));
+    } else {
+        const float k = fma_(wi_m, eta_ti, cos_theta_t);                         // refract(wi, m, cos_theta_t, eta_ti), fresnel.h:311-314
+        bs.wo = V3(fma_(m.x, k, -(wi.x * eta_ti)), fma_(m.y, k, -(wi.y * eta_ti)), fma_(m.z, k, -(wi.z * eta_ti)));
+        weight = V3(sqr(eta_ti));
+        if (B.specular_transmittance >= 0) weight = weight * tex_eval(sc, B.specular_transmittance, si);
+        const float wo_m = dot(bs.wo, m);
+        dwh_dwo = (sqr(bs.eta) * wo_m) / sqr(wi_m + bs.eta * wo_m);
+    }
+    if (distr.visible) weight = weight * distr.smith_g1(bs.wo, m);
+    else weight = weight * (distr.G(wi, bs.wo, m) * wi_m / (cos_theta_i * m.z));
+    bs.pdf = pdf * __builtin_fabsf(dwh_dwo);
+    if (!active) { weight = V3(0.f); bs.wo = V3(0.f); bs.pdf = 0.f; }         // neither lobe is selected: wo and dwh_dwo stay 0 (:307-347)
+    bs.weight = weight;
+    return bs;
+}
+// roughdielectric.cpp:501-608 eval_pdf(): what eval() (:360-434) and pdf() (:436-499) return, from one half-vector and one distribution
+DEV void rough_eval_pdf(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, V3 wo, V3 *value_out, float *pdf_out) {
+    const float cos_theta_i = wi.z, cos_theta_o = wo.z;
+    bool active = cos_theta_i != 0.f;
+    const bool reflect = cos_theta_i * cos_theta_o > 0.f;
+    const float inv_m_eta = rcp(B.eta);
+    const float eta = cos_theta_i > 0.f ? B.eta : inv_m_eta, inv_eta = cos_theta_i > 0.f ? inv_m_eta : B.eta;
+    V3 m = normalize(wi + wo * (reflect ? 1.f : eta));
+    m = V3(mulsign(m.x, m.z), mulsign(m.y, m.z), __builtin_fabsf(m.z));
+    const float wi_m = dot(wi, m), wo_m = dot(wo, m);
+    Microfacet distr = microfacet_of(B);
+    const float D = distr.eval(m);
+    float F, ctt, e0, e1; fresnel(wi_m, B.eta, &F, &ctt, &e0, &e1);
+    const float G = distr.G(wi, wo, m);
+    V3 result(0.f);
+    if (active && reflect) {
+        result = V3(F * D * G / (4.f * __builtin_fabsf(cos_theta_i)));
+        if (B.specular_reflectance >= 0) result = result * tex_eval(sc, B.specular_reflectance, si);
+    } else if (active) {
+        const float scale = sqr(inv_eta);
+        result = V3(__builtin_fabsf((scale * (1.f - F) * D * G * eta * eta * wi_m * wo_m) / (cos_theta_i * sqr(wi_m + eta * wo_m))));
+        if (B.specular_transmittance >= 0) result = result * tex_eval(sc, B.specular_transmittance, si);
+    }
+    *value_out = result;
+    active = active && wi_m * cos_theta_i > 0.f && wo_m * cos_theta_o > 0.f;
+    if (!distr.visible) distr.scale_alpha(1.2f - .2f * __builtin_sqrtf(__builtin_fabsf(cos_theta_i)));
+    float pdf = distr.pdf(V3(mulsign(wi.x, cos_theta_i), mulsign(wi.y, cos_theta_i), mulsign(wi.z, cos_theta_i)), m);
+    pdf *= reflect ? F : 1.f - F;
+    const float dwh_dwo = reflect ? rcp(4.f * wo_m) : (eta * eta * wo_m) / sqr(wi_m + eta * wo_m);
+    *pdf_out = active ? pdf * __builtin_fabsf(dwh_dwo) : 0.f;
+}
+
+// Leaf BSDFs (diffuse / dielectric / null; EXT: roughdielectric too), evaluated in the frame `wi` is given in.
 // DIELECTRIC: the caller has proven that the leaf is a dielectric (the 64-byte-record kernels, closed_records (b) in device.hip): no dispatch.
-template <bool DIELECTRIC = false>
+// EXT: the scene may hold a roughdielectric (the EXT instances, k_bsdf_probe); without it the rough code is not compiled in.
+template <bool DIELECTRIC = false, bool EXT = false>
 DEV BSDFSample leaf_sample(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, float s1, float s2x, float s2y) {
+    if (EXT && !DIELECTRIC && B.type == LRT_BSDF_ROUGHDIELECTRIC) return rough_sample(sc, B, si, wi, s1, s2x, s2y);
     BSDFSample bs;
     bs.wo = V3(0.f); bs.pdf = 0.f; bs.eta = 0.f; bs.type = 0; bs.weight = V3(0.f);       // dr::zeros<BSDFSample3f>
     if (!DIELECTRIC && B.type == LRT_BSDF_DIFFUSE) {               // src/bsdfs/diffuse.cpp sample()
@@ -647,25 +878,29 @@ DEV BSDFSample leaf_sample(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, flo
     }
     return bs;
 }
+template <bool EXT = false>
 DEV V3 leaf_eval(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, V3 wo) {
+    if (EXT && B.type == LRT_BSDF_ROUGHDIELECTRIC) { V3 v; float p; rough_eval_pdf(sc, B, si, wi, wo, &v, &p); return v; }
     if (B.type == LRT_BSDF_DIFFUSE) {
         if (!(wi.z > 0.f && wo.z > 0.f)) return V3(0.f);
         return tex_eval(sc, B.reflectance, si) * kInvPi * wo.z;
     }
     return V3(0.f);
 }
-DEV float leaf_pdf(const DBsdf &B, V3 wi, V3 wo) {
+template <bool EXT = false>
+DEV float leaf_pdf(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, V3 wo) {
+    if (EXT && B.type == LRT_BSDF_ROUGHDIELECTRIC) { V3 v; float p; rough_eval_pdf(sc, B, si, wi, wo, &v, &p); return p; }
     if (B.type == LRT_BSDF_DIFFUSE) return (wi.z > 0.f && wo.z > 0.f) ? kInvPi * wo.z : 0.f;
     return 0.f;
 }
 
-template <bool DIELECTRIC = false>                 // (every leaf is a dielectric, see leaf_sample)
+template <bool DIELECTRIC = false, bool EXT = false>                 // (every leaf is a dielectric, see leaf_sample)
 DEV BSDFSample bsdf_sample(SceneRef sc, int b, const SI &si, float s1, float s2x, float s2y) {
     const DBsdf B = tab(sc.bsdfs, b, sc.one_shape);
     if (B.type == LRT_BSDF_BUMPMAP) {               // src/bsdfs/bumpmap.cpp:138-162
         Frame pf = bump_frame(sc, B, si);
         V3 pwi = pf.to_local(si.wi);
-        BSDFSample bs = leaf_sample<DIELECTRIC>(sc, tab(sc.bsdfs, B.nested, sc.one_shape), si, pwi, s1, s2x, s2y);
+        BSDFSample bs = leaf_sample<DIELECTRIC, EXT>(sc, tab(sc.bsdfs, B.nested, sc.one_shape), si, pwi, s1, s2x, s2y);
         bool active = any_nonzero(bs.weight);
         V3 pwo = pf.to_world(bs.wo);
         active = active && (bs.wo.z * pwo.z > 0.f);
@@ -674,27 +909,29 @@ DEV BSDFSample bsdf_sample(SceneRef sc, int b, const SI &si, float s1, float s2x
         bs.weight = active ? w : V3(0.f);
         return bs;
     }
-    return leaf_sample<DIELECTRIC>(sc, B, si, si.wi, s1, s2x, s2y);
+    return leaf_sample<DIELECTRIC, EXT>(sc, B, si, si.wi, s1, s2x, s2y);
 }
+template <bool EXT = false>
 DEV V3 bsdf_eval(SceneRef sc, int b, const SI &si, V3 wo) {
     const DBsdf B = tab(sc.bsdfs, b, sc.one_shape);
     if (B.type == LRT_BSDF_BUMPMAP) {               // src/bsdfs/bumpmap.cpp:164-183
         Frame pf = bump_frame(sc, B, si);
         V3 pwi = pf.to_local(si.wi), pwo = pf.to_local(wo);
         if (!(wo.z * pwo.z > 0.f)) return V3(0.f);
-        return leaf_eval(sc, tab(sc.bsdfs, B.nested, sc.one_shape), si, pwi, pwo) * shadow_terminator(pf.n, wo);
+        return leaf_eval<EXT>(sc, tab(sc.bsdfs, B.nested, sc.one_shape), si, pwi, pwo) * shadow_terminator(pf.n, wo);
     }
-    return leaf_eval(sc, B, si, si.wi, wo);
+    return leaf_eval<EXT>(sc, B, si, si.wi, wo);
 }
+template <bool EXT = false>
 DEV float bsdf_pdf(SceneRef sc, int b, const SI &si, V3 wo) {
     const DBsdf B = tab(sc.bsdfs, b, sc.one_shape);
     if (B.type == LRT_BSDF_BUMPMAP) {
         Frame pf = bump_frame(sc, B, si);
         V3 pwi = pf.to_local(si.wi), pwo = pf.to_local(wo);
         if (!(wo.z * pwo.z > 0.f)) return 0.f;
-        return leaf_pdf(tab(sc.bsdfs, B.nested, sc.one_shape), pwi, pwo);
+        return leaf_pdf<EXT>(sc, tab(sc.bsdfs, B.nested, sc.one_shape), si, pwi, pwo);
     }
-    return leaf_pdf(B, si.wi, wo);
+    return leaf_pdf<EXT>(sc, B, si, si.wi, wo);
 }
 DEV float bsdf_null_transmission(SceneRef sc, int b) { return tab(sc.bsdfs, b, sc.one_shape).type == LRT_BSDF_NULL ? 1.f : 0.f; }
 

@@ -453,13 +453,13 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
             DirSample ds;
             V3 emitted = volpath_sample_emitter<HET>(sc, rng, si.p, si.n, true, si.shape, si.n, medium, channel, &ds, tr, n_shadow);
             V3 wo = si.sh.to_local(ds.d);
-            V3 bsdf_val = bsdf_eval(sc, b, si, wo);
-            float bpdf = bsdf_pdf(sc, b, si, wo);
+            V3 bsdf_val = bsdf_eval<TR::kExt>(sc, b, si, wo);
+            float bpdf = bsdf_pdf<TR::kExt>(sc, b, si, wo);
             V3 c = throughput * bsdf_val * mis_weight(ds.pdf, ds.delta ? 0.f : bpdf) * emitted;
             result = result + c;
         }
         float s1 = rng.next(), s2x, s2y; rng.next2(s2x, s2y);
-        const BSDFSample bs = bsdf_sample<CLOSED>(sc, b, si, s1, s2x, s2y);    // (CLOSED: dielectric, or bumpmap over dielectric, (b))
+        const BSDFSample bs = bsdf_sample<CLOSED, TR::kExt>(sc, b, si, s1, s2x, s2y);    // (CLOSED: dielectric, or bumpmap over dielectric, (b))
         throughput = throughput * bs.weight;
         eta *= bs.eta;
         ray = spawn_ray(si.p, si.n, si.sh.to_world(bs.wo));
@@ -572,9 +572,9 @@ DEV bool path_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const TR 
         wo = si.sh.to_local(ds.d);
     }
     float s1 = rng.next(), s2x, s2y; rng.next2(s2x, s2y);
-    V3 bsdf_val = bsdf_eval(sc, b, si, wo);
-    float bpdf = bsdf_pdf(sc, b, si, wo);
-    const BSDFSample bs = bsdf_sample(sc, b, si, s1, s2x, s2y);
+    V3 bsdf_val = bsdf_eval<TR::kExt>(sc, b, si, wo);
+    float bpdf = bsdf_pdf<TR::kExt>(sc, b, si, wo);
+    const BSDFSample bs = bsdf_sample<false, TR::kExt>(sc, b, si, s1, s2x, s2y);
     const V3 bsdf_weight = bs.weight;
     if (active_em) {
         float mis_em = ds.delta ? 1.f : mis_weight(ds.pdf, bpdf);
@@ -1071,11 +1071,11 @@ k_bsdf_probe(ScenePtr scp, const float *__restrict__ ro, const float *__restrict
         return;
     }
     const int b = tab(sc.shapes, si.shape, sc.one_shape).bsdf;
-    const BSDFSample bs = bsdf_sample(sc, b, si, smp[k], smp[k + 1], smp[k + 2]);
+    const BSDFSample bs = bsdf_sample<false, true>(sc, b, si, smp[k], smp[k + 1], smp[k + 2]);
     const V3 wow = si.sh.to_world(bs.wo);
     const V3 wo = si.sh.to_local(V3(woq[k], woq[k + 1], woq[k + 2]));
-    const V3 ev = bsdf_eval(sc, b, si, wo);
-    const float pdf = bsdf_pdf(sc, b, si, wo);
+    const V3 ev = bsdf_eval<true>(sc, b, si, wo);
+    const float pdf = bsdf_pdf<true>(sc, b, si, wo);
     o[0] = (float) si.shape; o[1] = si.t; o[2] = si.p.x; o[3] = si.p.y; o[4] = si.p.z; o[5] = si.n.x; o[6] = si.n.y; o[7] = si.n.z;
     o[8] = si.sh.n.x; o[9] = si.sh.n.y; o[10] = si.sh.n.z; o[11] = si.uv.x; o[12] = si.uv.y; o[13] = si.wi.x; o[14] = si.wi.y; o[15] = si.wi.z;
     o[16] = wow.x; o[17] = wow.y; o[18] = wow.z; o[19] = bs.wo.z; o[20] = bs.pdf; o[21] = bs.eta; o[22] = (float) bs.type;

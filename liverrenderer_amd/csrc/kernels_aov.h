@@ -39,6 +39,8 @@ DEV int aov_bsdf(SceneRef sc, const SI &si) {
 }
 
 // One AOV of one lane (aov.cpp:222-343).  A miss is the zero interaction (aov.cpp:216), so every value is 0 there.
+// EXT: the scene may hold a roughdielectric (the EXT instances)
+template <bool EXT = false>
 DEV void aov_eval(SceneRef sc, AovSpecPtr A, int type, const SI &si, float v[3]) {
     v[0] = v[1] = v[2] = 0.f;
     if (!si.valid) return;
@@ -50,6 +52,10 @@ DEV void aov_eval(SceneRef sc, AovSpecPtr A, int type, const SI &si, float v[3])
             if (B.type == LRT_BSDF_BUMPMAP) B = sc.bsdfs[B.nested];        // bumpmap.cpp:259: the nested BSDF's, at the unperturbed si
             if (B.type == LRT_BSDF_DIFFUSE) {                               // diffuse.cpp:181; dielectric / null: eval(wo = +z) * pi = 0 (bsdf.cpp:38-43)
                 const V3 r = tex_eval(sc, B.reflectance, si);
+                v[0] = r.x; v[1] = r.y; v[2] = r.z;
+            }
+            if (EXT && B.type == LRT_BSDF_ROUGHDIELECTRIC) {                // the BSDF base class: eval(si with wi as it is, wo = +z) * pi (bsdf.cpp:38-43)
+                const V3 r = leaf_eval<true>(sc, B, si, si.wi, V3(0.f, 0.f, 1.f)) * kPi;
                 v[0] = r.x; v[1] = r.y; v[2] = r.z;
             }
             break;
@@ -135,7 +141,7 @@ k_aov(ScenePtr scp, LaunchPtr lp, AovSpecPtr A) {
             if (have) {
                 float *o = sample_out + i * (uint64_t) n_ch;
                 for (int k = 0; k < n_aovs; ++k) {
-                    float v[3]; aov_eval(sc, A, A->type[k], si, v);
+                    float v[3]; aov_eval<EXT>(sc, A, A->type[k], si, v);
                     const int w = aov_width(A->type[k]), off = A->offset[k];
 #pragma unroll
                     for (int c = 0; c < 3; ++c) if (c < w) o[off + c] = v[c];     // constant indices: v stays in registers
@@ -149,7 +155,7 @@ k_aov(ScenePtr scp, LaunchPtr lp, AovSpecPtr A) {
             float *p = film + (size_t) run.pixel * C;
             for (int k = 0; k < n_aovs; ++k) {
                 const int type = A->type[k], w = aov_width(type), off = A->offset[k];
-                float v[3]; aov_eval(sc, A, type, si, v);
+                float v[3]; aov_eval<EXT>(sc, A, type, si, v);
                 wave_segmented_sums(v, head);
                 if (tail) {
 #pragma unroll
@@ -165,7 +171,7 @@ k_aov(ScenePtr scp, LaunchPtr lp, AovSpecPtr A) {
         const FilmFootprint fp = film_footprint(F, px, py, jx, jy);         // (lanes without a sample: zeros, not read)
         for (int k = 0; k < n_aovs; ++k) {
             const int type = A->type[k], w = aov_width(type), off = A->offset[k];
-            float v[3]; aov_eval(sc, A, type, si, v);
+            float v[3]; aov_eval<EXT>(sc, A, type, si, v);
             film_walk<3, -1>(F, have, fp, v, [&](int c) { return c < w; }, [&](int x, int y, const float (&t)[3]) {
                 float *p = film + ((size_t) y * F.width + x) * C + off;
 #pragma unroll

@@ -283,13 +283,13 @@ DEV bool biovolpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, con
             DirSample ds;
             V3 emitted = bio_sample_emitter(sc, rng, si.p, si.n, si.shape, medium, channel, tissue_depth, &ds, tr, n_shadow);
             V3 wo = si.sh.to_local(ds.d);
-            V3 bsdf_val = bsdf_eval(sc, b, si, wo);
-            float bpdf = bsdf_pdf(sc, b, si, wo);
+            V3 bsdf_val = bsdf_eval<TR::kExt>(sc, b, si, wo);
+            float bpdf = bsdf_pdf<TR::kExt>(sc, b, si, wo);
             V3 c = throughput * bsdf_val * mis_weight(ds.pdf, ds.delta ? 0.f : bpdf) * emitted;
             result = result + c;
         }
         float s1 = rng.next(), s2x, s2y; rng.next2(s2x, s2y);
-        const BSDFSample bs = bsdf_sample(sc, b, si, s1, s2x, s2y);
+        const BSDFSample bs = bsdf_sample<false, TR::kExt>(sc, b, si, s1, s2x, s2y);
         throughput = throughput * bs.weight;
         eta *= bs.eta;
         ray = spawn_ray(si.p, si.n, si.sh.to_world(bs.wo));
@@ -375,7 +375,7 @@ DEV bool biovolpath06_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, c
         const DShape sd = tab(sc.shapes, si.shape, sc.one_shape);
         const int b = sd.bsdf;
         float s1 = rng.next(), s2x, s2y; rng.next2(s2x, s2y);
-        const BSDFSample bs = bsdf_sample(sc, b, si, s1, s2x, s2y);
+        const BSDFSample bs = bsdf_sample<false, TR::kExt>(sc, b, si, s1, s2x, s2y);
         if (!any_nonzero(bs.weight)) { commit(); return false; }
         const bool new_full = depth + 1 < max_depth && type_full;       // :243-247 IndirectSurfaceRadiance
         bool new_emit = false;

@@ -278,14 +278,14 @@ DEV bool volpathmis_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, con
             DirSample ds; MisW<SMIS> nee_end, uni_end;
             V3 emitted = mis_sample_emitter<SMIS>(sc, rng, si.p, si.n, true, si.shape, medium, p_over_f, channel, &ds, nee_end, uni_end, tr, n_shadow);
             V3 wo = si.sh.to_local(ds.d);
-            V3 bsdf_val = bsdf_eval(sc, b, si, wo);
-            float bpdf = bsdf_pdf(sc, b, si, wo);
+            V3 bsdf_val = bsdf_eval<TR::kExt>(sc, b, si, wo);
+            float bpdf = bsdf_pdf<TR::kExt>(sc, b, si, wo);
             mis_update(nee_end, V3(1.f), bsdf_val, channel, true);
             mis_update(uni_end, V3(ds.delta ? 0.f : bpdf), bsdf_val, channel, true);
             result = result + mis_weight2(nee_end, uni_end) * emitted;
         }
         float s1 = rng.next(), s2x, s2y; rng.next2(s2x, s2y);
-        const BSDFSample bs = bsdf_sample(sc, b, si, s1, s2x, s2y);
+        const BSDFSample bs = bsdf_sample<false, TR::kExt>(sc, b, si, s1, s2x, s2y);
         const bool invalid_bsdf_sample = bs.pdf == 0.f;
         active_surface = bs.pdf > 0.f;
         if (active_surface) {

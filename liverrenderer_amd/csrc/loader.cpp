@@ -4,7 +4,7 @@
 // reference's src/core/parser.cpp + Properties + PluginManager instantiation.
 // Supported plugins: integrator {path, volpath, prbvolpath, biovolpath, biovolpath06, aov, moment}; sensor perspective;
 // sampler {independent, ldsampler}; film hdrfilm; rfilter {box,
-// gaussian, tent}; bsdf {diffuse, dielectric, bumpmap, null}; texture {bitmap,
+// gaussian, tent}; bsdf {diffuse, dielectric, roughdielectric, bumpmap, null}; texture {bitmap,
 // checkerboard}; medium {homogeneous, liver, parenchyma, glissonCapsule} (the
 // bio media carry both the homogeneous parameters that path / volpath /
 // prbvolpath see through the 4-argument sample_interaction() and the element
@@ -370,7 +370,7 @@ struct Loader {
     }
     int make_bsdf(const ObjP &o) {
         auto it = bsdf_ix.find(o.get()); if (it != bsdf_ix.end()) return it->second;
-        lrt_bsdf_desc B{}; B.reflectance = B.nested = B.texture = -1; B.eta = 1.f; B.scale = 1.f;
+        lrt_bsdf_desc B{}; B.reflectance = B.nested = B.texture = -1; B.eta = 1.f; B.scale = 1.f; B.specular_reflectance = B.specular_transmittance = -1;
         if (o->type == "diffuse") {
             B.type = LRT_BSDF_DIFFUSE; B.reflectance = texture_or_rgb(*o, "reflectance", .5f);
             if (S.textures[B.reflectance].type == LRT_TEX_BITMAP) fail("unsupported: a bitmap texture as diffuse reflectance (bitmaps are supported as bump-map heights only)");
@@ -388,6 +388,30 @@ struct Loader {
             B.nested = make_bsdf(nb); B.texture = make_texture(nt);
             if (S.bsdfs[B.nested].type == LRT_BSDF_BUMPMAP) fail("nested bump maps are not supported");
         } else if (o->type == "null") B.type = LRT_BSDF_NULL;
+        else if (o->type == "roughdielectric") {     // src/bsdfs/roughdielectric.cpp:165-220
+            B.type = LRT_BSDF_ROUGHDIELECTRIC;
+            auto spec_tex = [&](const char *k) {
+                if (!has(*o, k) && !child(*o, "texture", k)) return -1;
+                int t = texture_or_rgb(*o, k, 1.f);
+                if (S.textures[t].type == LRT_TEX_BITMAP) fail("unsupported: a bitmap texture as roughdielectric " + std::string(k) + " (bitmaps are supported as bump-map heights only)");
+                return t;
+            };
+            B.specular_reflectance = spec_tex("specular_reflectance"); B.specular_transmittance = spec_tex("specular_transmittance");
+            float ii = lookup_ior(*o, "int_ior", "bk7"), ei = lookup_ior(*o, "ext_ior", "air");
+            if (ii < 0 || ei < 0 || ii == ei) fail("The interior and exterior indices of refraction must be positive and differ!");
+            B.eta = ii / ei;
+            std::string distr = get_string(*o, "distribution", "beckmann"); for (auto &c : distr) c = (char) tolower((unsigned char) c);
+            if (distr == "beckmann") B.distribution = 0; else if (distr == "ggx") B.distribution = 1;
+            else fail("Specified an invalid distribution \"" + distr + "\", must be \"beckmann\" or \"ggx\"!");
+            B.sample_visible = get_bool(*o, "sample_visible", true) ? 1 : 0;
+            for (const char *k : { "alpha", "alpha_u", "alpha_v" })
+                if (child(*o, "texture", k)) fail("unsupported: a texture as roughdielectric \"" + std::string(k) + "\" (a textured roughness is not built)");
+            if (has(*o, "alpha_u") || has(*o, "alpha_v")) {
+                if (!has(*o, "alpha_u") || !has(*o, "alpha_v")) fail("Microfacet model: both 'alpha_u' and 'alpha_v' must be specified.");
+                if (has(*o, "alpha")) fail("Microfacet model: please specifyeither 'alpha' or 'alpha_u'/'alpha_v'.");   // (the reference's two literals, joined as its compiler joins them)
+                B.alpha_u = get_float(*o, "alpha_u", .1f); B.alpha_v = get_float(*o, "alpha_v", .1f);
+            } else B.alpha_u = B.alpha_v = get_float(*o, "alpha", .1f);
+        }
         else if (o->type == "twosided") { ObjP nb = child(*o, "bsdf"); if (!nb) fail("twosided: missing nested bsdf"); fail("twosided BSDFs are not supported"); }
         else fail("unsupported bsdf type \"" + o->type + "\"");
         S.bsdfs.push_back(B); int ix = (int) S.bsdfs.size() - 1; bsdf_ix[o.get()] = ix; return ix;
@@ -872,9 +896,15 @@ struct Loader {
         bool ext = false;                       // spheres / point / mesh emitters: prbvolpath's adjoint is built for triangles and rectangle / infinite emitters
         for (auto &sh : S.shapes) ext = ext || sh.kind == LRT_SHAPE_SPHERE;
         for (auto &e : S.emitters) ext = ext || e.type == LRT_EMITTER_POINT || (e.type == LRT_EMITTER_AREA && S.shapes[e.shape].kind == LRT_SHAPE_MESH);
+        bool rough = false;                     // a roughdielectric on a shape, nested or not: it runs on the EXT instances too (scene_prep.cpp)
+        for (auto &sh : S.shapes) if (sh.bsdf >= 0) {
+            const lrt_bsdf_desc &B = S.bsdfs[sh.bsdf];
+            rough = rough || B.type == LRT_BSDF_ROUGHDIELECTRIC || (B.type == LRT_BSDF_BUMPMAP && S.bsdfs[B.nested].type == LRT_BSDF_ROUGHDIELECTRIC);
+        }
         bool prb = S.desc.integrator.type == LRT_INTEGRATOR_PRBVOLPATH;
         for (int k = 0; S.has_aov && k < S.aov.n_integrators; ++k) prb = prb || S.aov.integrators[k].type == LRT_INTEGRATOR_PRBVOLPATH;
         if (ext && prb) fail("unsupported: prbvolpath on a scene with sphere shapes, point emitters or area emitters on meshes");
+        if (rough && prb) fail("unsupported: prbvolpath on a scene with a roughdielectric BSDF (no adjoint is built for it)");
         S.fix_pointers();
     }
 };

@@ -203,6 +203,13 @@ void prepare_geometry(const lrt_scene_desc &d, const PrepOptions &opt, PreparedS
         if (e.type == LRT_EMITTER_POINT || (e.type == LRT_EMITTER_AREA && e.shape >= 0 && (uint32_t) e.shape < d.n_shapes && d.shapes[e.shape].kind == LRT_SHAPE_MESH)) P.ext = true;
     }
     if (!spheres.empty()) P.ext = true;
+    // A roughdielectric on a shape, nested or not, runs on the EXT instances (an unreferenced one changes nothing: the scene keeps its kernels)
+    for (uint32_t i = 0; i < d.n_shapes; ++i) {
+        const int32_t b = d.shapes[i].bsdf;
+        if (b < 0 || (uint32_t) b >= d.n_bsdfs) continue;
+        const lrt_bsdf_desc &B = d.bsdfs[b];
+        if (B.type == LRT_BSDF_ROUGHDIELECTRIC || (B.type == LRT_BSDF_BUMPMAP && B.nested >= 0 && (uint32_t) B.nested < d.n_bsdfs && d.bsdfs[B.nested].type == LRT_BSDF_ROUGHDIELECTRIC)) P.ext = true;
+    }
     // ---- acceleration structure
     // Leaf size: the smallest of 2, 3, 4, 6, 8, 12, 16 triangles whose BVH image fits the LDS next to the traversal stacks (fatter
     // leaves = fewer nodes: more triangle tests per leaf, but every fetch of the traversal stays in LDS; Liver-MultiMesh's two meshes
@@ -277,10 +284,11 @@ void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedSc
     }
     // ---- BSDFs
     std::vector<DBsdf> &bsdfs = P.bsdfs; bsdfs.resize(d.n_bsdfs); sc.has_null_bsdf = 0;
-    auto leaf_flags = [](int type) { return type == LRT_BSDF_DIFFUSE ? PREP_F_SMOOTH : type == LRT_BSDF_DIELECTRIC ? PREP_F_DELTA : PREP_F_NULL; };
+    auto leaf_flags = [](int type) { return (type == LRT_BSDF_DIFFUSE || type == LRT_BSDF_ROUGHDIELECTRIC) ? PREP_F_SMOOTH : type == LRT_BSDF_DIELECTRIC ? PREP_F_DELTA : PREP_F_NULL; };   // (roughdielectric: both lobes are glossy)
     for (uint32_t i = 0; i < d.n_bsdfs; ++i) {
         const lrt_bsdf_desc &B = d.bsdfs[i];
-        bsdfs[i] = { B.type, B.reflectance, B.nested, B.texture, B.eta, B.scale, 0, 0 };
+        DBsdf &o = bsdfs[i]; memset(&o, 0, sizeof(o));
+        o.type = B.type; o.reflectance = B.reflectance; o.nested = B.nested; o.texture = B.texture; o.eta = B.eta; o.scale = B.scale;
         if (B.type == LRT_BSDF_BUMPMAP) {
             if (B.nested < 0 || (uint32_t) B.nested >= d.n_bsdfs || d.bsdfs[B.nested].type == LRT_BSDF_BUMPMAP) throw std::runtime_error("bumpmap: invalid nested BSDF");
             bsdfs[i].flags = leaf_flags(d.bsdfs[B.nested].type);
@@ -288,6 +296,16 @@ void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedSc
         if (B.type == LRT_BSDF_DIFFUSE && (B.reflectance < 0 || (uint32_t) B.reflectance >= d.n_textures || d.textures[B.reflectance].type == LRT_TEX_BITMAP))
             throw std::runtime_error("unsupported: a bitmap texture as diffuse reflectance (bitmaps are supported as bump-map heights only)");
         if (B.type == LRT_BSDF_NULL) sc.has_null_bsdf = 1;
+        if (B.type == LRT_BSDF_ROUGHDIELECTRIC) {     // the fields share the words a roughdielectric leaves unused (device_types.h)
+            for (int32_t t : { B.specular_reflectance, B.specular_transmittance }) {
+                if (t < -1 || t >= (int32_t) d.n_textures) throw std::runtime_error("roughdielectric references an invalid texture");
+                if (t >= 0 && d.textures[t].type == LRT_TEX_BITMAP)
+                    throw std::runtime_error("unsupported: a bitmap texture as roughdielectric specular_reflectance / specular_transmittance");
+            }
+            bsdfs[i].specular_reflectance = B.specular_reflectance; bsdfs[i].specular_transmittance = B.specular_transmittance;
+            bsdfs[i].alpha_u = std::max(B.alpha_u, 1e-4f); bsdfs[i].alpha_v = std::max(B.alpha_v, 1e-4f);      // MicrofacetDistribution::configure (microfacet.h:425-428)
+            bsdfs[i].micro = (B.distribution == 1 ? LRT_MICRO_GGX : 0) | (B.sample_visible ? LRT_MICRO_VISIBLE : 0);
+        }
     }
     // ---- bounds (src/render/scene.cpp:49; include/mitsuba/core/bbox.h:343-346; envmap.cpp:337-351)
     DEnv &E = sc.env; memset(&E, 0, sizeof(E)); E.type = -1; E.emitter = -1;
