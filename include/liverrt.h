@@ -247,6 +247,8 @@ typedef struct {
                                  0 for the PRB adjoint  [v108] */
     uint64_t n_closed_guard;  /* 64-byte records: trips that broke the layout's premise (nonzero radiance on a path that
                                  goes on, an emitter hit that needs its MIS weight); the render then fails  [v108] */
+    uint64_t n_proven;        /* 64-byte records: records read whose segment was proven free of surfaces (by the distance
+                                 field or the per-face cone table) and ran without a ray query; 0 for every other kernel  [v115] */
 } lrt_render_stats;
 
 typedef struct {
@@ -261,7 +263,7 @@ typedef struct {
 typedef struct lrt_scene lrt_scene;
 
 LRT_API const char *lrt_last_error(void);
-LRT_API int         lrt_version(void);   /* 114: the roughdielectric BSDF (LRT_BSDF_ROUGHDIELECTRIC, the fields after `scale` of lrt_bsdf_desc), lrt_math_eval fn 9 / 10; 113: lrt_bsdf_probe; 112:lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
+LRT_API int         lrt_version(void);   /* 115: lrt_render_stats.n_proven appended (lrt_render_stats_get writes 8 bytes more: rebuild hosts against this header); 114: the roughdielectric BSDF (LRT_BSDF_ROUGHDIELECTRIC, the fields after `scale` of lrt_bsdf_desc), lrt_math_eval fn 9 / 10; 113: lrt_bsdf_probe; 112:lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
 
 LRT_API lrt_status lrt_scene_load_xml(const char *path, const char *const *defines,
                                       int n_defines, lrt_scene **out);

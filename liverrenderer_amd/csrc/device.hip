@@ -62,7 +62,7 @@ static lrt_render_opts default_opts() { return lrt_render_opts{ -1, -2, -1, -1, 
 static void add_stats(lrt_render_stats &total, const lrt_render_stats &s) {
     total.n_samples += s.n_samples; total.n_iter += s.n_iter; total.n_shadow += s.n_shadow; total.n_launches += s.n_launches;
     total.n_records += s.n_records; total.kernel_ms += s.kernel_ms; total.total_ms += s.total_ms;
-    total.record_bytes = s.record_bytes; total.n_closed_guard += s.n_closed_guard;
+    total.record_bytes = s.record_bytes; total.n_closed_guard += s.n_closed_guard; total.n_proven += s.n_proven;
 }
 
 #define LRT_LAUNCH_SLOTS 64
@@ -314,6 +314,7 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
     sc.emitters = up(P.emitters);
     sc.mesh_emitters = up(P.mesh_emitters);
     sc.mesh_emitter_tab = up(P.mesh_emitter_tab);
+    sc.cone_tab = P.cone_tab.empty() ? nullptr : (const uint2 *) up(P.cone_tab);      // (sc.cone_enabled: set by the preparation with the table)
     sc.env_data = (const float4 *) up(P.env_data);
     sc.env_hier = up(P.env_hier);
     HIP_CHECK(hipMalloc((void **) &D->d_sc, sizeof(DScene))); D->track(D->d_sc);
@@ -551,6 +552,7 @@ static void run_wavefront(DeviceScene *D, const lrt_scene_desc &d, const Resolve
     log.n_records = D->h_counters->n_records;
     finish_stats(D, log, e_begin, e_end, n_lanes, stats);
     stats.n_closed_guard = D->h_counters->n_closed_guard;
+    stats.n_proven = D->h_counters->n_proven;
     if (stats.n_closed_guard)
         throw std::runtime_error("64-byte path records: " + std::to_string(stats.n_closed_guard) + " trips broke the premise of the layout (radiance before a path's last trip, "
                                  "or an emitter hit that needs its MIS weight); the scene test in closed_records() is wrong for this scene: LRT_NO_CLOSED_RECORDS=1 renders it with 80-byte records");
@@ -1048,7 +1050,7 @@ void device_render_multi(std::vector<DeviceScene *> &devs, MultiContext *&ctx, c
     develop_and_download(D0, films[0], film_raw, image, film_floats, image_floats, on_device);
     lrt_render_stats total{};
     for (auto &x : st) { total.n_samples += x.n_samples; total.n_iter += x.n_iter; total.n_shadow += x.n_shadow; total.n_launches += x.n_launches; total.n_records += x.n_records;
-                         total.kernel_ms = std::max(total.kernel_ms, x.kernel_ms); total.lds_resident = x.lds_resident; total.record_bytes = x.record_bytes; total.n_closed_guard += x.n_closed_guard; }
+                         total.kernel_ms = std::max(total.kernel_ms, x.kernel_ms); total.lds_resident = x.lds_resident; total.record_bytes = x.record_bytes; total.n_closed_guard += x.n_closed_guard; total.n_proven += x.n_proven; }
     total.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     stats = total;
 }

@@ -159,7 +159,16 @@ struct DScene {
     uint32_t n_spheres, pad_sph;
     const DMeshEmitter *mesh_emitters;   // n_emitters entries (the EXT instances only read them)
     const float *mesh_emitter_tab;       // every mesh emitter's pmf and cdf
+    const uint2 *cone_tab;               // per face and side (2 * face + side): the free lengths of LRT_CONE_BINS direction cones as binary16, rounded down (scene_prep.cpp: build_cone_table); null: none
+    int32_t cone_enabled, pad_cone;      // the closed-records volpath kernels only read the table
 };
+
+// Direction bins of DScene::cone_tab: bin k holds the directions whose cosine to the side's geometric normal is at least LRT_CONE_COSk
+#define LRT_CONE_BINS 4
+#define LRT_CONE_COS0 0.95f
+#define LRT_CONE_COS1 0.85f
+#define LRT_CONE_COS2 0.70f
+#define LRT_CONE_COS3 0.50f
 
 // The scene record lives in device memory and is read through the CONSTANT address space: every `sc.field` is a scalar
 // load (s_load_dword*) issued where the value is used, instead of ~190 kernarg SGPRs that stay live through the whole
@@ -232,6 +241,7 @@ struct DCounters {             // device-resident queue / statistics words
     unsigned long long prof_cycles[4], prof_tiles[4];   // per tile kind (A, C, B, fresh): wall_clock64 ticks and tiles (LRT_DEBUG_LAUNCH)
     unsigned long long prof_wg[6];   // LRT_DEBUG_LAUNCH: workgroup timeline, 100 MHz ticks: sum of start, sum of (loop start - start), sum of end, max end, min start + 2^62 trick see kernels.h, sum of barrier waits of thread 0
     unsigned long long n_closed_guard;   // 64-byte-record kernels: trips that broke the layout's premise (radiance before the last trip, an emitter hit that needs MIS)
+    unsigned long long n_proven;   // path records loaded from region A: their segment was proven free of surfaces (the 64-byte-record volpath kernels only)
 };
 
 // LDS image of the scene for the persistent traversal kernel: [nodes | verts (float4) | tris (4 x u16)] copied verbatim

@@ -267,8 +267,10 @@ DEV bool segment_proven_empty(GridRef g, V3 o, V3 d, float maxt) {
 // segment; the segment is free of surfaces when the balls around those points (radius = the bound) cover it end to end.  One memory round
 // trip instead of three (the dependent lookups were the largest stall of a medium trip: section timers of the proven-free tiles), and the
 // cover test uses the bounds actually found, so one large ball in the middle can do it alone.  Same margins as above.
+// `start` (the closed-records volpath kernels; 0 elsewhere: the code of every other caller is what it was): the stretch from the origin that
+// the caller has already proven free, in the lengthened units of L (the per-face cone table, scene_prep.cpp: build_cone_table).
 template <int K>
-DEV bool segment_covered_by_balls(GridRef g, V3 o, V3 d, float maxt) {
+DEV bool segment_covered_by_balls(GridRef g, V3 o, V3 d, float maxt, float start = 0.f) {
     if (!g.enabled || !(maxt < 1e30f)) return false;
     const float len = __builtin_amdgcn_sqrtf(dot(d, d));                 // hardware sqrt (1 ulp): inside the margins
     const float L = maxt * len * 1.01f;                                  // the segment, 1 % long
@@ -276,7 +278,7 @@ DEV bool segment_covered_by_balls(GridRef g, V3 o, V3 d, float maxt) {
     float lb[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) lb[k] = dist_grid_lower_bound(g, fma3(d, maxt * LRT_FRAC(k), o)) * .995f;
-    float covered = 0.f; bool ok = true;
+    float covered = start; bool ok = true;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const float c = L * LRT_FRAC(k);                                // the point's position along the (lengthened) segment
@@ -297,6 +299,31 @@ DEV bool segment_free_of_surfaces(GridRef g, V3 o, V3 d, float maxt) {
 #else
     return segment_covered_by_balls<2>(g, o, d, maxt);
 #endif
+}
+// The closed-records volpath kernels' form.  `cone`: what the per-face cone table says about a segment that starts on a surface, in the cover
+// test's lengthened units: > 0 the free stretch from the origin; < 0 the table holds nothing for it (an empty row, or a direction flatter than
+// the widest bin): the lookups are not made and the segment goes to its ray query.  That gives up, by choice, the proofs the balls alone would still
+// find: the first ball sits a quarter of the way along and has to reach back to an origin that spawn_ray lifted off its triangle by no more than
+// the ray epsilon, so only segments of a few hundred epsilons qualify (below about 0.7 units on the liver; 8 - 26 % of refracted-in segments in
+// DESIGN.md section 6e).  PF_NOHIT only elides a query that finds nothing, so no lane changes, and leaving those segments to the balls timed the same.
+// 0: the segment does not start on a surface.  A segment that the cone covers alone needs no lookup.
+DEV bool segment_free_of_surfaces_from(GridRef g, V3 o, V3 d, float maxt, float cone) {
+    if (cone < 0.f || !g.enabled || !(maxt < 1e30f)) return false;
+    if (cone > 0.f && cone >= maxt * __builtin_amdgcn_sqrtf(dot(d, d)) * 1.01f) return true;
+    return segment_covered_by_balls<2>(g, o, d, maxt, cone);
+}
+// A face's row of the cone table for a direction d leaving the face whose geometric normal (as the surface interaction holds it) is n:
+// `rows` = the face's two sides (cone_tab[2 f], cone_tab[2 f + 1]), binary16 lengths of the bins LRT_CONE_COS0 .. 3.  Returns the free length in the
+// cover test's lengthened units, or -1 when the row holds none or the direction's cosine is below LRT_CONE_COS3.
+DEV float cone_free_length(uint4 rows, V3 d, V3 n) {
+    const float cs = dot(d, n), c = __builtin_fabsf(cs) * __builtin_amdgcn_rsqf(dot(d, d));
+    const uint32_t lo = cs < 0.f ? rows.z : rows.x, hi = cs < 0.f ? rows.w : rows.y;
+    const uint32_t w = c >= LRT_CONE_COS1 ? lo : hi;
+    uint32_t h = (c >= LRT_CONE_COS0 || (c < LRT_CONE_COS1 && c >= LRT_CONE_COS2)) ? (w & 0xffffu) : (w >> 16);
+    if (!(c >= LRT_CONE_COS3)) h = 0u;
+    union { uint16_t u; _Float16 f; } cv; cv.u = (uint16_t) h;
+    const float r = (float) cv.f;
+    return r > 0.f ? r * 1.01f : -1.f;
 }
 
 // --------------------------------------------------- surface interaction

@@ -283,15 +283,21 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
     // PRE, inside a medium: the free-flight draw of the trip about to run, and the attempt to prove that distance free of surfaces
     uint32_t nohit = 0;
     float cache_t = u2f(0x7fc00000u);
+    // CLOSED: what the per-face cone table says about the segment that leaves a surface on this trip (segment_free_of_surfaces_from); 0: no surface left
+    float cone_free = 0.f;
     auto free_flight_stage = [&]() {
         if (medium < 0) return;
         const DMedium M = tab(sc.media, medium);
         cache_t = medium_sampled_t(M, rng.next(), channel);
-        if (sc.grid.enabled) { const MI m2 = medium_interaction_at(M, ray, cache_t); if (m2.valid() && segment_free_of_surfaces(sc.grid, ray.o, ray.d, m2.t)) nohit = PF_NOHIT; }
+        if (sc.grid.enabled) {
+            const MI m2 = medium_interaction_at(M, ray, cache_t);
+            if (m2.valid() && (CLOSED ? segment_free_of_surfaces_from(sc.grid, ray.o, ray.d, m2.t, cone_free) : segment_free_of_surfaces(sc.grid, ray.o, ray.d, m2.t))) nohit = PF_NOHIT;
+        }
     };
     bool active = true;
     if (!PRE) active = termination_stage();
-    else if (fresh) { active = termination_stage(); if (active) { free_flight_stage(); ff_t = cache_t; proven_empty = nohit != 0; nohit = 0; cache_t = u2f(0x7fc00000u); } }
+    // (CLOSED: the sensor lies outside every medium, closed_records (a): a camera lane has no free flight to draw, and the stage is not compiled a second time)
+    else if (fresh) { active = termination_stage(); if (active && !CLOSED) { free_flight_stage(); ff_t = cache_t; proven_empty = nohit != 0; nohit = 0; cache_t = u2f(0x7fc00000u); } }
     if (!active) { commit(); return false; }
 
     bool active_medium = medium >= 0, active_surface = !active_medium;
@@ -444,6 +450,9 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
     active_surface = active_surface && si.valid;
     if (!active_surface) rng.skip(3);                                   // volpath.cpp:407 (NEE), 366, 367
     if (active_surface) {
+        // CLOSED: the face's two rows of the cone table, asked for here so that the BSDF work hides the load
+        uint4 cone_rows = make_uint4(0u, 0u, 0u, 0u);
+        if (CLOSED && sc.cone_enabled) cone_rows = *reinterpret_cast<const uint4 *>(sc.cone_tab + 2u * (size_t) si.prim);
         const DShape sd = tab(sc.shapes, si.shape, sc.one_shape);
         int b = sd.bsdf;
         int flags = tab(sc.bsdfs, b, sc.one_shape).flags;
@@ -468,6 +477,7 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
         specular_chain = specular_chain || (non_null && (bs.type & F_DELTA));
         specular_chain = specular_chain && !(bs.type & F_SMOOTH);
         if (is_medium_transition(sd)) medium = target_medium(sd, ray.d, si.n);
+        if (CLOSED && sc.cone_enabled) cone_free = cone_free_length(cone_rows, ray.d, si.n);
     }
     active = active && (active_surface || active_medium);
     // ---- the first stage of the next trip.  PRE: for real (see above): a path that stops there is retired now and that trip is counted
@@ -708,6 +718,7 @@ k_render(ScenePtr scp, LaunchPtr lp) {
     if (VP_LDS_COUNT && tid < 2) s_cnt[tid] = 0;
     WaveCount wc_shadow{ &s_cnt[0] }, wc_extra{ &s_cnt[1] };
     uint32_t n_shadow = 0, n_extra = 0, n_trips = 0, n_loaded = 0;
+    uint32_t n_proven = 0;                                    // CLOSED: records loaded from region A, a per-wave sum of tile populations like n_loaded
     if (rp.profile & 1u) t_loop_start = wall_clock64();
     for (;;) {
         if (tid == 0) {
@@ -754,6 +765,7 @@ k_render(ScenePtr scp, LaunchPtr lp) {
                 const uint32_t n_had = (uint32_t) __popcll(__ballot(had_path));       // every path of the tile runs one trip
                 n_trips += n_had;
                 if (t < ta + tcl + tb) n_loaded += n_had;
+                if (CLOSED && t < ta) n_proven += n_had;
             }
 #ifdef LRT_STAMP
             clk.at(0);                                                  // ticket, index arithmetic, load issue
@@ -824,6 +836,7 @@ k_render(ScenePtr scp, LaunchPtr lp) {
         if (!VP_LDS_COUNT && n_shadow) atomicAdd(&A.cnt->n_shadow, (unsigned long long) n_shadow);
         if (n_trips) atomicAdd(&A.cnt->n_iter, (unsigned long long) n_trips);
         if (n_loaded) atomicAdd(&A.cnt->n_records, (unsigned long long) n_loaded);
+        if (CLOSED && n_proven) atomicAdd(&A.cnt->n_proven, (unsigned long long) n_proven);
     }
     if (VP_LDS_COUNT) {
         __syncthreads();

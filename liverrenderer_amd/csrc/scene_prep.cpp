@@ -17,6 +17,7 @@ PrepOptions PrepOptions::from_env() {
     o.no_dist_grid = getenv("LRT_NO_DIST_GRID") != nullptr;
     if (getenv("LRT_DIST_GRID_RES")) o.dist_grid_res = std::max(8, std::min(256, atoi(getenv("LRT_DIST_GRID_RES"))));
     o.no_nee_reject = getenv("LRT_NO_NEE_REJECT") != nullptr;
+    o.no_cone_proof = getenv("LRT_NO_CONE_PROOF") != nullptr;
     return o;
 }
 
@@ -172,6 +173,193 @@ static void vertex_bounds(const lrt_scene_desc &d, const std::vector<DSphere> &s
     for (const DSphere &o : spheres) for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], o.center[a] - o.radius); hi[a] = fmaxf(hi[a], o.center[a] + o.radius); }   // Sphere::bbox
 }
 
+// ---- the per-face cone table (scene_prep.h: build_cone_table).  Float64 throughout; the margins below are for the device's float32.
+// Face f, side normal nu (unit), h(x) = (x - a) . nu the height over f's plane, nu_e the in-plane unit normal of edge e pointing away from the face.
+// Origins.  The device interpolates the hit point in float32 (compute_si: b0 = 1 - b1 - b2, three fused products per coordinate: below 9 * 2^-24 * amax
+// from a point of the triangle, amax the face's largest |coordinate|) and moves it by mag = (1 + max|p|) * kRayEpsilon along its own float32 normal
+// (offset_p; one more rounding).  That normal is within 2^-22 / sin(angle at vertex 0) of nu; faces where that sine is below 2e-3 get no row, so the
+// normal is within 2.5e-4 rad: a lateral shift of mag * 2.5e-4, and a cosine off by less than the 1e-3 by which every bin is widened here.
+// tau = 2e-6 * amax + 1e-9 bounds all of it; mag lies in [mag_min, mag_max] computed from the face's coordinates.
+// Region.  A point o + t w, w within theta of nu, has h = h_o + t cos(angle) and has moved sideways by at most (h - h_o) tan(theta): all points
+// that segments of the bin can reach lie in Q = { h >= -tau } and { (x - p_e) . nu_e <= h tan(theta) + tau (1 + tan(theta)) for the three edges },
+// and a point at height h is reached only by t >= h - h_o.  So a triangle whose part inside Q stays at heights >= hmin bounds nothing shorter
+// than hmin - mag_max - 2 tau, and R is the minimum over all other triangles (clipped to Q with Sutherland-Hodgman; hmin over the polygon's vertices).
+// Neighbours touch Q at h = 0 and are decided exactly instead (vertices are matched by position, not by index: an OBJ splits a vertex by
+// its normals).  The reachable set itself keeps a margin mag_min * tan(theta) - tau > 0 inside the edge planes and mag_min - tau above the face's;
+// bins where tau reaches a quarter of the former get 0.
+//   shared edge e: the neighbour is the hull of the edge and its far vertex w, and phi_e(x) = (x - p_e) . nu_e - h(x) tan(theta) and h are linear
+//     and vanish on the edge: the neighbour stays out iff phi_e(w) > 0 or h(w) < 0.  Otherwise R = 0.
+//   shared vertex v: Q lies in the cone { h >= 0, phi <= 0 for the two edges at v } with apex v, and the neighbour is the hull of v and its far
+//     edge: it meets the cone away from v iff the far edge does.  Then R = 0.
+//   all three: R = 0.  A degenerate neighbour (two of its vertices at one position) that touches f: R = 0.
+// Triangles that come close without sharing a vertex (T-junctions, vertices that almost coincide) go through the clip and give R = 0.
+namespace {
+struct D3 { double x, y, z; };
+inline D3 operator-(D3 a, D3 b) { return { a.x - b.x, a.y - b.y, a.z - b.z }; }
+inline D3 operator+(D3 a, D3 b) { return { a.x + b.x, a.y + b.y, a.z + b.z }; }
+inline D3 operator*(D3 a, double s) { return { a.x * s, a.y * s, a.z * s }; }
+inline double dot3(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+inline D3 cross3(D3 a, D3 b) { return { a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x }; }
+inline double len3(D3 a) { return std::sqrt(dot3(a, a)); }
+struct ConePlane { D3 n; double c; };                  // inside: n . x <= c
+// the smallest `hn . x` over the part of polygon `poly` (n <= 3 vertices) inside the four planes; false: that part is empty
+bool clip_min_height(const D3 *tri, const ConePlane *pl, D3 hn, double &hmin) {
+    D3 a[8], b[8]; int n = 3; for (int i = 0; i < 3; ++i) a[i] = tri[i];
+    for (int p = 0; p < 4 && n > 0; ++p) {
+        int m = 0;
+        for (int i = 0; i < n; ++i) {
+            const D3 u = a[i], v = a[(i + 1) % n];
+            const double su = dot3(pl[p].n, u) - pl[p].c, sv = dot3(pl[p].n, v) - pl[p].c;
+            if (su <= 0.0) b[m++] = u;
+            if ((su <= 0.0) != (sv <= 0.0)) { const double t = su / (su - sv); b[m++] = u + (v - u) * t; }
+        }
+        n = m; for (int i = 0; i < n; ++i) a[i] = b[i];
+    }
+    if (n == 0) return false;
+    hmin = INFINITY; for (int i = 0; i < n; ++i) hmin = std::min(hmin, dot3(hn, a[i]));
+    return true;
+}
+uint16_t half_round_down(double v) {                   // the largest binary16 <= v; below the smallest normal number: 0
+    float f = (float) v; if ((double) f > v) f = std::nextafterf(f, 0.f);
+    if (!(f >= 6.103515625e-5f)) return 0;
+    if (f >= 65504.f) return 0x7bff;
+    uint32_t u; memcpy(&u, &f, 4);
+    return (uint16_t) ((((u >> 23) - 112u) << 10) | ((u >> 13) & 0x3ffu));
+}
+}
+float cone_table_value(uint16_t h) {
+    if (!h) return 0.f;
+    const uint32_t u = (((uint32_t) (h >> 10) + 112u) << 23) | ((uint32_t) (h & 0x3ffu) << 13); float f; memcpy(&f, &u, 4); return f;
+}
+
+void build_cone_table(const lrt_scene_desc &d, std::vector<uint16_t> &out) {
+    constexpr int K = LRT_CONE_BINS;
+    const uint32_t nf = d.n_faces;
+    out.assign((size_t) nf * 2 * K, 0);
+    if (!nf) return;
+    for (size_t i = 0; i < 3 * (size_t) d.n_vertices; ++i) if (!std::isfinite(d.positions[i])) return;
+    const double bin_cos[K] = { LRT_CONE_COS0, LRT_CONE_COS1, LRT_CONE_COS2, LRT_CONE_COS3 };
+    double tan_k[K], inv_cos_k[K];
+    for (int k = 0; k < K; ++k) { const double c = bin_cos[k] - 1e-3; tan_k[k] = std::sqrt(1.0 - c * c) / c; inv_cos_k[k] = 1.0 / c; }
+    // vertices at one position get one id
+    std::vector<uint32_t> cid(d.n_vertices), order(d.n_vertices);
+    for (uint32_t i = 0; i < d.n_vertices; ++i) order[i] = i;
+    auto pos = [&](uint32_t v, int a) { return d.positions[3 * (size_t) v + a]; };
+    std::sort(order.begin(), order.end(), [&](uint32_t u, uint32_t v) { for (int a = 0; a < 3; ++a) if (pos(u, a) != pos(v, a)) return pos(u, a) < pos(v, a); return false; });
+    for (uint32_t i = 0, id = 0; i < d.n_vertices; ++i) {
+        if (i && (pos(order[i], 0) != pos(order[i - 1], 0) || pos(order[i], 1) != pos(order[i - 1], 1) || pos(order[i], 2) != pos(order[i - 1], 2))) ++id;
+        cid[order[i]] = id;
+    }
+    struct Face { D3 v[3], cen; double rad; uint32_t c[3]; bool dup; };
+    std::vector<Face> F(nf);
+    double lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for (uint32_t f = 0; f < nf; ++f) {
+        Face &T = F[f];
+        for (int j = 0; j < 3; ++j) {
+            const uint32_t v = d.faces[3 * (size_t) f + j];
+            T.v[j] = { pos(v, 0), pos(v, 1), pos(v, 2) }; T.c[j] = cid[v];
+            const double q[3] = { T.v[j].x, T.v[j].y, T.v[j].z };
+            for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], q[a]); hi[a] = std::max(hi[a], q[a]); }
+        }
+        T.cen = (T.v[0] + T.v[1] + T.v[2]) * (1.0 / 3.0);
+        T.rad = std::max(len3(T.v[0] - T.cen), std::max(len3(T.v[1] - T.cen), len3(T.v[2] - T.cen))) * (1.0 + 1e-12);
+        T.dup = T.c[0] == T.c[1] || T.c[1] == T.c[2] || T.c[0] == T.c[2];
+    }
+    // No row claims more than an eighth of the scene's extent: it bounds the pairs that are looked at; free flights longer than that go to the balls or the query
+    const double cap = 0.125 * std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
+    const double ray_eps = 1500.0 * 5.9604644775390625e-8;                              // kRayEpsilon (dmath.h)
+    for (uint32_t f = 0; f < nf; ++f) {
+        const Face &T = F[f];
+        if (T.dup) continue;
+        const D3 e1 = T.v[1] - T.v[0], e2 = T.v[2] - T.v[0], N = cross3(e1, e2);
+        const double n2 = len3(N);
+        if (!(n2 > 0.0) || n2 < 2e-3 * len3(e1) * len3(e2)) continue;
+        double amax = 0.0, m_min = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            const double q[3] = { a == 0 ? T.v[0].x : (a == 1 ? T.v[0].y : T.v[0].z), a == 0 ? T.v[1].x : (a == 1 ? T.v[1].y : T.v[1].z), a == 0 ? T.v[2].x : (a == 1 ? T.v[2].y : T.v[2].z) };
+            amax = std::max(amax, std::max(std::fabs(q[0]), std::max(std::fabs(q[1]), std::fabs(q[2]))));
+            const bool one_sign = (q[0] > 0 && q[1] > 0 && q[2] > 0) || (q[0] < 0 && q[1] < 0 && q[2] < 0);
+            if (one_sign) m_min = std::max(m_min, std::min(std::fabs(q[0]), std::min(std::fabs(q[1]), std::fabs(q[2]))));       // the least max|p| over the face is at least this
+        }
+        const double tau = 2e-6 * amax + 1e-9, mag_min = (1.0 + m_min) * ray_eps * (1.0 - 1e-5), mag_max = (1.0 + amax) * ray_eps * (1.0 + 1e-5);
+        const double h_o_max = mag_max + tau;
+        const uint32_t shape = d.face_shape ? d.face_shape[f] : 0u;
+        const bool flip = shape < d.n_shapes && d.shapes[shape].flip_normals;
+        D3 nu[2], ne[2][3]; double R[2][K];
+        for (int s = 0; s < 2; ++s) {
+            nu[s] = N * (((s == 0) != flip ? 1.0 : -1.0) / n2);
+            for (int e = 0; e < 3; ++e) {                                                // edge e: from vertex e to vertex e + 1, opposite to vertex e + 2
+                D3 m = cross3(T.v[(e + 1) % 3] - T.v[e], nu[s]); m = m * (1.0 / len3(m));
+                if (dot3(T.v[(e + 2) % 3] - T.v[e], m) > 0.0) m = m * -1.0;
+                ne[s][e] = m;
+            }
+            for (int k = 0; k < K; ++k) R[s][k] = tau < 0.25 * mag_min * tan_k[k] ? cap : 0.0;
+        }
+        // Two passes: the faces around f first (every neighbour is among them), which bring most rows down to their final length; then the others,
+        // culled by bounding spheres against the widest cone at the height the rows still reach.
+        bool dead = false;
+        for (int pass = 0; pass < 2 && !dead; ++pass) {
+        double base[2];
+        for (int s = 0; s < 2; ++s) { double r = 0.0; for (int k = 0; k < K; ++k) r = std::max(r, R[s][k]); base[s] = T.rad + (r + h_o_max + tau) * inv_cos_k[K - 1] + 4.0 * tau; }
+        for (uint32_t g = 0; g < nf; ++g) {
+            if (g == f) continue;
+            const Face &G = F[g];
+            const D3 dc = G.cen - T.cen; const double dist2 = dot3(dc, dc), near = 3.0 * T.rad + G.rad, far = std::max(base[0], base[1]) + G.rad;
+            if ((dist2 <= near * near) != (pass == 0) || dist2 > far * far) continue;
+            int match[3], ns = 0;
+            for (int j = 0; j < 3; ++j) { match[j] = -1; for (int i = 0; i < 3; ++i) if (G.c[j] == T.c[i]) match[j] = i; ns += match[j] >= 0; }
+            if (ns == 3 || (ns > 0 && G.dup)) { for (int s = 0; s < 2; ++s) for (int k = 0; k < K; ++k) R[s][k] = 0.0; dead = true; break; }
+            for (int s = 0; s < 2; ++s) {
+                const D3 hn = nu[s]; const double h_off = dot3(hn, T.v[0]);
+                if (ns == 2) {
+                    int jw = 0, seen = 0; for (int j = 0; j < 3; ++j) { if (match[j] < 0) jw = j; else seen |= 1 << match[j]; }
+                    const int opp = seen == 3 ? 2 : (seen == 6 ? 0 : 1), e = (opp + 1) % 3;          // the edge opposite to f's unmatched vertex
+                    const D3 w = G.v[jw]; const double hw = dot3(hn, w) - h_off, lat = dot3(w - T.v[e], ne[s][e]), slack = 1e-9 * (1.0 + len3(w - T.v[e]));
+                    for (int k = 0; k < K; ++k) if (hw >= -slack && lat - hw * tan_k[k] <= slack) R[s][k] = 0.0;
+                } else if (ns == 1) {
+                    int iv = 0, jv = 0; for (int j = 0; j < 3; ++j) if (match[j] >= 0) { iv = match[j]; jv = j; }
+                    const D3 v = T.v[iv], w1 = G.v[(jv + 1) % 3], w2 = G.v[(jv + 2) % 3];
+                    const int ea = iv, eb = (iv + 2) % 3;                                            // the two edges of f at vertex iv
+                    const double slack = 1e-9 * (1.0 + std::max(len3(w1 - v), len3(w2 - v)));
+                    const double h1 = dot3(hn, w1 - v), h2 = dot3(hn, w2 - v);
+                    for (int k = 0; k < K; ++k) {
+                        // c(x) <= slack for -h, phi_ea, phi_eb along w1 + t (w2 - w1), t in [0, 1]
+                        const double c1[3] = { -h1, dot3(w1 - v, ne[s][ea]) - h1 * tan_k[k], dot3(w1 - v, ne[s][eb]) - h1 * tan_k[k] };
+                        const double c2[3] = { -h2, dot3(w2 - v, ne[s][ea]) - h2 * tan_k[k], dot3(w2 - v, ne[s][eb]) - h2 * tan_k[k] };
+                        double t0 = 0.0, t1 = 1.0;
+                        for (int c = 0; c < 3; ++c) {
+                            const double u0 = c1[c] - slack, du = c2[c] - c1[c];                       // u0 + t du <= 0
+                            if (du == 0.0) { if (u0 > 0.0) t1 = -1.0; }
+                            else if (du > 0.0) t1 = std::min(t1, -u0 / du);
+                            else t0 = std::max(t0, -u0 / du);
+                        }
+                        if (t0 <= t1) R[s][k] = 0.0;
+                    }
+                } else {
+                    if (dist2 > (base[s] + G.rad) * (base[s] + G.rad)) continue;
+                    const double hc = dot3(hn, G.cen) - h_off;
+                    if (hc + G.rad < -tau) continue;
+                    double lat[3]; for (int e = 0; e < 3; ++e) lat[e] = dot3(G.cen - T.v[e], ne[s][e]);
+                    for (int k = K - 1; k >= 0; --k) {                                               // the widest cone first: a triangle outside it is outside the narrower ones
+                        if (!(R[s][k] > 0.0) || hc - G.rad - h_o_max - tau >= R[s][k]) continue;
+                        const double tp = tau * (1.0 + tan_k[k]);
+                        bool outside = false;
+                        for (int e = 0; e < 3; ++e) outside = outside || lat[e] - hc * tan_k[k] - G.rad * inv_cos_k[k] > tp;
+                        if (outside) break;
+                        ConePlane pl[4]; pl[0] = { hn * -1.0, tau - h_off };
+                        for (int e = 0; e < 3; ++e) { const D3 n = ne[s][e] - hn * tan_k[k]; pl[1 + e] = { n, tp + dot3(T.v[e], ne[s][e]) - h_off * tan_k[k] }; }
+                        double hmin;
+                        if (!clip_min_height(G.v, pl, hn, hmin)) break;
+                        R[s][k] = std::max(0.0, std::min(R[s][k], hmin - h_off - h_o_max - tau));
+                    }
+                }
+            }
+        }
+        }
+        for (int s = 0; s < 2; ++s) for (int k = 0; k < K; ++k) out[((size_t) 2 * f + s) * K + k] = half_round_down(R[s][k]);
+    }
+}
+
 void prepare_geometry(const lrt_scene_desc &d, const PrepOptions &opt, PreparedScene &P) {
     DScene &sc = P.sc;
     memset(&sc, 0, sizeof(sc));                          // the record is uploaded byte for byte: its padding is cleared too
@@ -252,6 +440,11 @@ void prepare_geometry(const lrt_scene_desc &d, const PrepOptions &opt, PreparedS
             g.enabled = 1; sc.grid = g;                                    // (g.d: the upload side builds the field, k_build_dist_grid)
         }
     }
+    // ---- per-face cone table: proves the segments that start on a surface, which the distance field cannot (build_cone_table).  Only the
+    // closed-records volpath kernels read it, and those run on the LDS image, without spheres, beside the distance field, on scenes that
+    // closed_records() accepts: the build is quadratic in the faces and is not paid for a scene whose renders can never use it.  (A parameter update
+    // that makes a scene qualify later renders it with 64-byte records and no table, as with LRT_NO_CONE_PROOF.)
+    if (P.use_lds && !P.ext && sc.grid.enabled && !opt.no_cone_proof && closed_records(d, d.sensor.medium)) { build_cone_table(d, P.cone_tab); sc.cone_enabled = 1; }
 }
 
 void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedScene &P) {

@@ -16,9 +16,10 @@ struct PrepOptions {
     bool no_dist_grid = false;     // LRT_NO_DIST_GRID
     int dist_grid_res = 0;         // LRT_DIST_GRID_RES clamped to 8 .. 256; 0: by the face count
     bool no_nee_reject = false;    // LRT_NO_NEE_REJECT
+    bool no_cone_proof = false;    // LRT_NO_CONE_PROOF: no per-face cone table (build_cone_table)
     size_t lds_limit = 0;          // LDS bytes a workgroup may ask for (device.hip: the opt-in maximum minus the kernels' static words)
     int n_cus = 256;               // compute units of the device: the upload side sets it and takes it back for the launch geometry; the preparation does not use it
-    static PrepOptions from_env(); // reads the five switches; lds_limit and n_cus stay at their defaults
+    static PrepOptions from_env(); // reads the six switches; lds_limit and n_cus stay at their defaults
 };
 
 // BSDF leaf flags as DBsdf::flags stores them (dshade.h names the same values F_DELTA, F_SMOOTH, F_NULL; device.hip asserts that they agree)
@@ -39,6 +40,7 @@ struct PreparedScene {
     // cam, film and the distance field's geometry (grid.enabled set, grid.d null: the upload side builds the field).  Every pointer is null.
     DScene sc{};
     float grid_abs_margin = 0.f;                       // k_build_dist_grid's margin
+    std::vector<uint16_t> cone_tab;                    // build_cone_table's rows, 2 * LRT_CONE_BINS binary16 per face; empty: no table (sc.cone_enabled = 0)
     bool env_interior_positive = false;                // envmap: rows 1..h-2 of the sampling density strictly positive
     bool ext = false, has_area_emitter = false, has_het = false, has_non_bio = false, prb_null = false, use_lds = false;   // DeviceScene's flags of the same names
     int bvh_leaf = 4;
@@ -49,6 +51,14 @@ struct PreparedScene {
 void prepare_geometry(const lrt_scene_desc &d, const PrepOptions &opt, PreparedScene &P);
 void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedScene &P);
 PreparedScene prepare_scene(const lrt_scene_desc &d, const PrepOptions &opt);
+
+// Per-face cone table: out[(2 * f + s) * LRT_CONE_BINS + k] = R as binary16, rounded down, with this property: a segment whose origin lies on face f,
+// displaced to side s as spawn_ray displaces a float32 hit point (s = 0: along the geometric normal the device computes, flip_normals applied; s = 1:
+// against it), whose direction makes a cosine of at least LRT_CONE_COSk with that side's normal and whose length is at most R meets no triangle of
+// the scene.  0: nothing is claimed.  (scene_prep.cpp has the construction.)
+void build_cone_table(const lrt_scene_desc &d, std::vector<uint16_t> &out);
+// a table entry as the device reads it
+float cone_table_value(uint16_t h);
 
 // bytes of the LDS image of a BVH: nodes, float4 vertices, 8-byte triangle slots, 16-bit traversal stacks of 1024 threads
 size_t lds_image_bytes(const HostBVH &b, uint32_t n_vertices);
