@@ -20,7 +20,10 @@
  *   lrt_trace                            the ray-tracing callback seam of the LLVM variants
  *                                        src/render/scene_native.inl:135-202 (SoA RayHit layout)
  *   lrt_param_set / lrt_param_get        mi.traverse(scene)[key] (src/media/homogeneous.cpp:146-151,
- *                                        src/phase/hg.cpp:60-62)
+ *                                        src/phase/hg.cpp:60-62; the tabulated / Rayleigh / blended phase
+ *                                        functions of lrt_scene_desc.phases [v116] have no keys)
+ *   lrt_scene_desc.phases [v116]         PhaseFunction plugins src/phase/tabphase.cpp, rayleigh.cpp, blendphase.cpp
+ *                                        (isotropic.cpp and hg.cpp stay in lrt_medium_desc.phase / g)
  *   lrt_film_develop                     HDRFilm::develop src/films/hdrfilm.cpp:306-410
  *   lrt_last_error                       Throw(...) -> Python RuntimeError
  *
@@ -58,7 +61,11 @@ enum { LRT_MEDIUM_HOMOGENEOUS = 0, LRT_MEDIUM_LIVER = 1, LRT_MEDIUM_PARENCHYMA =
        LRT_MEDIUM_HETEROGENEOUS = 4   /* src/media/heterogeneous.cpp: sigma_t from a grid volume, delta tracking */ };
 enum { LRT_BSDF_DIFFUSE = 0, LRT_BSDF_DIELECTRIC = 1, LRT_BSDF_BUMPMAP = 2, LRT_BSDF_NULL = 3, LRT_BSDF_ROUGHDIELECTRIC = 4 };
 enum { LRT_TEX_RGB = 0, LRT_TEX_CHECKERBOARD = 1, LRT_TEX_BITMAP = 2 };
-enum { LRT_PHASE_ISOTROPIC = 0, LRT_PHASE_HG = 1 };
+enum { LRT_PHASE_ISOTROPIC = 0, LRT_PHASE_HG = 1,
+       /* [v116] entries of lrt_scene_desc.phases only (lrt_medium_desc.phase stays ISOTROPIC or HG) */
+       LRT_PHASE_TABULATED = 2,       /* src/phase/tabphase.cpp: `values` over cos(theta) in [-1, 1], physics convention (cos = 1: forward) */
+       LRT_PHASE_RAYLEIGH = 3,        /* src/phase/rayleigh.cpp                             */
+       LRT_PHASE_BLEND = 4            /* src/phase/blendphase.cpp: one level, a constant weight */ };
 enum { LRT_EMITTER_AREA = 0, LRT_EMITTER_ENVMAP = 1, LRT_EMITTER_CONSTANT = 2,
        LRT_EMITTER_POINT = 3          /* [v106] src/emitters/point.cpp: `intensity` in radiance[3], position = to_world * 0 */ };
 enum { LRT_SHAPE_MESH = 0, LRT_SHAPE_RECTANGLE = 1,
@@ -143,7 +150,28 @@ typedef struct {
     float   grid_bbox_min[3], grid_bbox_max[3];   /* world-space bounds of that cube (Volume::update_bbox)       */
     float   grid_max;         /* maximum of the grid values (Volume::max)            */
     const float *grid_data;   /* x fastest: data[(z * res_y + y) * res_x + x]         */
+    /* [v116] read only when lrt_scene_desc.n_phases > 0: index into phases[] of a TABULATED, RAYLEIGH or BLEND entry (an ISOTROPIC / HG
+       entry is LRT_ERR_INVALID here), -1: none (`phase` / `g` above describe the medium).  With an entry, `phase` / `g` are ignored by
+       the forward integrators. */
+    int32_t phase_index;
+    int32_t pad_phase;
 } lrt_medium_desc;
+
+/* [v116] One phase function of the table lrt_scene_desc.phases.  A medium points at a TABULATED, RAYLEIGH or BLEND entry;
+   ISOTROPIC and HG entries exist as the children of a BLEND (a medium that scatters by one of those two says so in `phase` / `g`).
+   TABULATED: n_values >= 2 non-negative values with some mass, the nodes of a piecewise linear density over cos(theta) in [-1, 1]
+   (ContinuousDistribution, include/mitsuba/core/distr_1d.h:548-597, built as the scalar constructor builds it).
+   BLEND: (1 - weight) * child[0] + weight * child[1], weight clipped to [0, 1]; a child is never a BLEND.
+   The forward integrators render such media on the EXT kernel instances; prbvolpath refuses the scene, lrt_param_set has no key
+   for `values` / `weight`, and the CPU oracle under oracle/ must not be handed such a scene. */
+typedef struct {
+    int32_t  type;            /* LRT_PHASE_*                                       */
+    float    g;               /* HG                                                */
+    float    weight;          /* BLEND                                             */
+    int32_t  child[2];        /* BLEND: indices into phases[] (phase_0, phase_1), else -1 */
+    uint32_t n_values;        /* TABULATED                                         */
+    const float *values;
+} lrt_phase_desc;
 
 typedef struct {
     int32_t type;             /* LRT_EMITTER_*                                     */
@@ -209,6 +237,9 @@ typedef struct {
                                      2^32 - 1 samples are split into passes as well (integrator.cpp:275-293)  */
     uint32_t use_spectral_mis;    /* volpathmis `use_spectral_mis` (volpathmis.cpp:47, default true)                */
     uint32_t pad;
+    /* [v116] the phase-function table; n_phases = 0 (a description from before v116, zero-filled here): every medium scatters by its `phase` / `g` */
+    uint32_t n_phases, pad_phases;
+    const lrt_phase_desc *phases;
 } lrt_scene_desc;
 
 /* ----------------------------------------------------------- render call */
@@ -263,7 +294,7 @@ typedef struct {
 typedef struct lrt_scene lrt_scene;
 
 LRT_API const char *lrt_last_error(void);
-LRT_API int         lrt_version(void);   /* 115: lrt_render_stats.n_proven appended (lrt_render_stats_get writes 8 bytes more: rebuild hosts against this header); 114: the roughdielectric BSDF (LRT_BSDF_ROUGHDIELECTRIC, the fields after `scale` of lrt_bsdf_desc), lrt_math_eval fn 9 / 10; 113: lrt_bsdf_probe; 112:lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
+LRT_API int         lrt_version(void);   /* 116: tabulated, Rayleigh and blended phase functions (lrt_phase_desc, lrt_scene_desc.phases, lrt_medium_desc.phase_index), lrt_phase_probe, lrt_math_eval fn 11; 115: lrt_render_stats.n_proven appended (lrt_render_stats_get writes 8 bytes more: rebuild hosts against this header); 114: the roughdielectric BSDF (LRT_BSDF_ROUGHDIELECTRIC, the fields after `scale` of lrt_bsdf_desc), lrt_math_eval fn 9 / 10; 113: lrt_bsdf_probe; 112:lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
 
 LRT_API lrt_status lrt_scene_load_xml(const char *path, const char *const *defines,
                                       int n_defines, lrt_scene **out);
@@ -333,7 +364,8 @@ LRT_API lrt_status lrt_render_backward_multi(lrt_scene *scene, const lrt_render_
 /* Test hook [v104]: the device's own log / exp / sincos / atan2 / acos / log2 kernels (csrc/dmath.h: the arithmetic every path value
  * goes through, standing in for Dr.Jit's dr::log / dr::exp / ... of include/mitsuba/core/math.h users) and its division / sqrt / rcp,
  * one value per lane.  fn: 0 log(x), 1 exp(x), 2 sincos(x) -> out, out2, 3 atan2(y, x), 4 acos(x), 5 log2(x), 6 x / y, 7 sqrt(x), 8 1 / x,
- * [v114] 9 erf(x), 10 erfinv(x) (Beckmann's visible-normal sampling, csrc/dshade.h). */
+ * [v114] 9 erf(x), 10 erfinv(x) (Beckmann's visible-normal sampling, csrc/dshade.h),
+ * [v116] 11 cbrt(x) (the Rayleigh phase function's inversion, csrc/dshade.h). */
 LRT_API lrt_status lrt_math_eval(int fn, const float *x, const float *y, uint32_t n, float *out, float *out2, int device);
 
 /* Test hook [v107]: Scene::sample_emitter_direction of the render kernels that serve spheres, point emitters and mesh
@@ -364,6 +396,14 @@ LRT_API lrt_status lrt_envmap_probe(lrt_scene *scene, const float *dir, uint32_t
 #define LRT_BSDF_PROBE_FLOATS 30
 LRT_API lrt_status lrt_bsdf_probe(lrt_scene *scene, const float *o, const float *d, const float *sample, const float *wo_query,
                                   uint32_t n, float *out, int device);
+
+/* Test hook [v116]: the phase function of medium `medium` as the EXT render kernels call it (csrc/dshade.h phase_sample<true> /
+ * phase_eval<true>), one call per lane, whatever the medium's phase type.  For input i: PhaseFunction::sample(ctx, mei with
+ * wi = wi[3 i ..], sample[3 i], (sample[3 i + 1], sample[3 i + 2])) and PhaseFunction::eval_pdf(ctx, mei, wo_query[3 i ..]).
+ * out: LRT_PHASE_PROBE_FLOATS floats per input: [0..2] the sampled wo, [3] its weight, [4] its pdf, [5] eval and [6] pdf at wo_query. */
+#define LRT_PHASE_PROBE_FLOATS 7
+LRT_API lrt_status lrt_phase_probe(lrt_scene *scene, int medium, const float *wi, const float *sample, const float *wo_query,
+                                   uint32_t n, float *out, int device);
 
 /* SoA ray queries (layout mirrors RayHit of src/render/scene_native.inl:135-142).
  * Miss: t = +inf, prim = 0xffffffff.  any_hit: only t (0 on hit, +inf on miss). */

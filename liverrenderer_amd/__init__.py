@@ -122,7 +122,7 @@ _TAGS = {
     "bitmap": "texture", "checkerboard": "texture",
     "homogeneous": "medium", "liver": "medium", "parenchyma": "medium", "glissonCapsule": "medium", "heterogeneous": "medium",
     "gridvolume": "volume",
-    "isotropic": "phase", "hg": "phase",
+    "isotropic": "phase", "hg": "phase", "tabphase": "phase", "rayleigh": "phase", "blendphase": "phase",
     "obj": "shape", "rectangle": "shape", "cube": "shape",
     "area": "emitter", "envmap": "emitter", "constant": "emitter",
 }
@@ -178,6 +178,8 @@ def _dict_to_xml(name, d, out, indent, top_ids, parent=None):
             out.append(f'{sub}<float name="{_esc(k)}" value="{_fmt(v)}"/>')
         elif isinstance(v, str):
             out.append(f'{sub}<string name="{_esc(k)}" value="{_esc(v)}"/>')
+        elif typ == "tabphase" and k == "values" and isinstance(v, (list, tuple, np.ndarray)):      # the plugin reads a string (tabphase.cpp:45-57)
+            out.append(f'{sub}<string name="values" value="{", ".join(_fmt(x) for x in np.asarray(v).reshape(-1))}"/>')
         elif isinstance(v, (list, tuple, np.ndarray)):
             out.append(f'{sub}<rgb name="{_esc(k)}" value="{", ".join(_fmt(x) for x in v)}"/>')
         else:
@@ -493,6 +495,19 @@ class Scene:
         FP = C.POINTER(C.c_float)
         _lib.check(self._lib.lrt_envmap_probe(self._h, d.ctypes.data_as(FP), d.shape[0], out.ctypes.data_as(FP), int(device)))
         return out[:, 0].copy(), out[:, 1:4].copy()
+
+    def phase_probe(self, medium, wi, sample, wo_query, device=0):
+        """lrt_phase_probe (test hook): the phase function of medium `medium` (an index into desc.media) as the EXT render kernels call it,
+        per lane: PhaseFunction::sample(wi, sample = (s1, s2x, s2y)) and eval_pdf(wi, wo_query) (n x 3 each).  Returns a dict of arrays:
+        wo (n x 3), weight, pdf, eval, eval_pdf (n each)."""
+        a = [np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (wi, sample, wo_query)]
+        n = a[0].shape[0]
+        if any(x.shape[0] != n for x in a):
+            raise ValueError("phase_probe: wi, sample and wo_query must have the same number of rows")
+        out = np.zeros((n, _lib.PHASE_PROBE_FLOATS), np.float32)
+        FP = C.POINTER(C.c_float)
+        _lib.check(self._lib.lrt_phase_probe(self._h, int(medium), *[x.ctypes.data_as(FP) for x in a], n, out.ctypes.data_as(FP), int(device)))
+        return {"wo": out[:, 0:3], "weight": out[:, 3], "pdf": out[:, 4], "eval": out[:, 5], "eval_pdf": out[:, 6]}
 
     def bsdf_probe(self, o, d, sample, wo_query, device=0):
         """lrt_bsdf_probe (test hook): per ray (o, d) (n x 3 each) the closest hit without a ray offset, its surface interaction, the hit

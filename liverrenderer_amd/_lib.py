@@ -15,6 +15,7 @@ INTEGRATOR = {"path": 0, "volpath": 1, "prbvolpath": 2, "biovolpath": 3, "biovol
 MEDIUM = {"homogeneous": 0, "liver": 1, "parenchyma": 2, "glissonCapsule": 3, "heterogeneous": 4}
 EMITTER = {"area": 0, "envmap": 1, "constant": 2}
 PROBE_FLOATS = 20      # include/liverrt.h LRT_PROBE_FLOATS (lrt_emitter_probe)
+PHASE_PROBE_FLOATS = 7 # include/liverrt.h LRT_PHASE_PROBE_FLOATS (lrt_phase_probe)
 BSDF_PROBE_FLOATS = 30 # include/liverrt.h LRT_BSDF_PROBE_FLOATS (lrt_bsdf_probe)
 
 
@@ -47,7 +48,14 @@ class MediumDesc(C.Structure):
                 ("sigma_lipid_water", C.c_float * 3), ("sigma_hepatocity", C.c_float),
                 # heterogeneous medium (grid volume)
                 ("grid_res", C.c_int32 * 3), ("grid_to_local", C.c_float * 12), ("grid_bbox_min", C.c_float * 3),
-                ("grid_bbox_max", C.c_float * 3), ("grid_max", C.c_float), ("grid_data", C.POINTER(C.c_float))]
+                ("grid_bbox_max", C.c_float * 3), ("grid_max", C.c_float), ("grid_data", C.POINTER(C.c_float)),
+                # [v116] read only when SceneDesc.n_phases > 0: index into SceneDesc.phases, -1: none
+                ("phase_index", C.c_int32), ("pad_phase", C.c_int32)]
+
+
+class PhaseDesc(C.Structure):                # [v116] lrt_phase_desc: one entry of the phase-function table
+    _fields_ = [("type", C.c_int32), ("g", C.c_float), ("weight", C.c_float), ("child", C.c_int32 * 2), ("n_values", C.c_uint32),
+                ("values", C.POINTER(C.c_float))]
 
 
 class EmitterDesc(C.Structure):
@@ -79,7 +87,8 @@ class SceneDesc(C.Structure):
                 ("media", C.POINTER(MediumDesc)), ("emitters", C.POINTER(EmitterDesc)),
                 ("sensor", SensorDesc), ("film", FilmDesc), ("integrator", IntegratorDesc),
                 ("sample_count", C.c_uint32), ("sampler_seed", C.c_uint32),
-                ("sampler_type", C.c_uint32), ("samples_per_pass", C.c_uint32), ("use_spectral_mis", C.c_uint32), ("pad", C.c_uint32)]
+                ("sampler_type", C.c_uint32), ("samples_per_pass", C.c_uint32), ("use_spectral_mis", C.c_uint32), ("pad", C.c_uint32),
+                ("n_phases", C.c_uint32), ("pad_phases", C.c_uint32), ("phases", C.POINTER(PhaseDesc))]       # [v116]
 
 
 AOV_MAX_INTEGRATORS, AOV_MAX_AOVS, AOV_NAME_LEN = 4, 16, 64
@@ -208,6 +217,8 @@ def lib():
     L.lrt_envmap_probe.restype = C.c_int
     L.lrt_bsdf_probe.argtypes = [C.c_void_p, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), C.c_uint32, P(C.c_float), C.c_int]
     L.lrt_bsdf_probe.restype = C.c_int
+    L.lrt_phase_probe.argtypes = [C.c_void_p, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), C.c_uint32, P(C.c_float), C.c_int]
+    L.lrt_phase_probe.restype = C.c_int
     L.lrt_param_set.argtypes = [C.c_void_p, C.c_char_p, P(C.c_float), C.c_int]
     L.lrt_param_get.argtypes = [C.c_void_p, C.c_char_p, P(C.c_float), C.c_int]
     L.lrt_image_read.argtypes = [C.c_char_p, P(C.c_int), P(C.c_int), P(C.c_int), P(P(C.c_float))]
@@ -246,7 +257,7 @@ def lib():
 
 EXPORTED_SYMBOLS = ["lrt_last_error", "lrt_version", "lrt_scene_load_xml", "lrt_scene_load_xml_string", "lrt_scene_from_desc",
                     "lrt_scene_desc_get", "lrt_scene_free", "lrt_render", "lrt_render_multi", "lrt_render_backward_multi", "lrt_math_eval", "lrt_render_stats_get", "lrt_film_develop",
-                    "lrt_render_samples", "lrt_render_backward", "lrt_render_backward_grid", "lrt_trace", "lrt_emitter_probe", "lrt_envmap_probe", "lrt_bsdf_probe", "lrt_param_set", "lrt_param_get",
+                    "lrt_render_samples", "lrt_render_backward", "lrt_render_backward_grid", "lrt_trace", "lrt_emitter_probe", "lrt_envmap_probe", "lrt_bsdf_probe", "lrt_phase_probe", "lrt_param_set", "lrt_param_get",
                     "lrt_image_read", "lrt_image_free", "lrt_image_write_exr", "lrt_image_write_png",
                     "lrt_vae_model_create", "lrt_vae_model_free", "lrt_vae_scatter",
                     "lrt_scene_aov_get", "lrt_aov_channel_name", "lrt_render_aov", "lrt_render_aov_samples", "lrt_image_write_exr_channels",

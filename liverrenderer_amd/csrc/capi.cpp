@@ -3,6 +3,7 @@
 // thread-local message for lrt_last_error().
 #include "host_scene.h"
 #include "device_scene.h"
+#include "scene_prep.h"
 #include "image_io.h"
 #include <algorithm>
 #include <cmath>
@@ -30,7 +31,7 @@ static lrt_status fail(lrt_status st, const std::string &msg) { g_error = msg; r
 extern "C" {
 
 const char *lrt_last_error(void) { return g_error.c_str(); }
-int lrt_version(void) { return 115; }    // 1.15: lrt_render_stats::n_proven (the struct grows by 8 bytes); 1.14: the roughdielectric BSDF, lrt_math_eval fn 9 (erf) / 10 (erfinv); 1.13: lrt_bsdf_probe; 1.12: lrt_render_backward_grid, "<id>.sigma_t.data" in lrt_param_set / lrt_param_get; 1.11: lrt_envmap_probe; 1.10: the moment integrator (lrt_render_moment, lrt_render_moment_samples, lrt_scene_moment_get, lrt_moment_channel_name); 1.9: the guided denoiser (lrt_denoiser_create / lrt_denoise / lrt_denoiser_free), lrt_image_read_named; 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
+int lrt_version(void) { return 116; }    // 1.16: tabulated / Rayleigh / blended phase functions (lrt_scene_desc.phases), lrt_phase_probe, lrt_math_eval fn 11 (cbrt); 1.15: lrt_render_stats::n_proven (the struct grows by 8 bytes); 1.14: the roughdielectric BSDF, lrt_math_eval fn 9 (erf) / 10 (erfinv); 1.13: lrt_bsdf_probe; 1.12: lrt_render_backward_grid, "<id>.sigma_t.data" in lrt_param_set / lrt_param_get; 1.11: lrt_envmap_probe; 1.10: the moment integrator (lrt_render_moment, lrt_render_moment_samples, lrt_scene_moment_get, lrt_moment_channel_name); 1.9: the guided denoiser (lrt_denoiser_create / lrt_denoise / lrt_denoiser_free), lrt_image_read_named; 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
 
 static std::vector<std::pair<std::string, std::string>> parse_defines(const char *const *defines, int n) {
     std::vector<std::pair<std::string, std::string>> r;
@@ -104,6 +105,8 @@ static void validate_desc(const lrt_scene_desc &d) {
         if (M.phase != LRT_PHASE_ISOTROPIC && M.phase != LRT_PHASE_HG) bad("invalid phase function");
         if (M.phase == LRT_PHASE_HG && !(M.g > -1.f && M.g < 1.f)) bad("The asymmetry parameter must lie in the interval (-1, 1)!");
     }
+    try { validate_phases(d); }                 // the phase table and the media's indices into it (scene_prep.cpp)
+    catch (const std::runtime_error &e) { if (!strncmp(e.what(), "unsupported", 11)) throw; bad(e.what()); }
     for (uint32_t i = 0; i < d.n_shapes; ++i) {
         const lrt_shape_desc &s = d.shapes[i];
         if (s.bsdf < 0 || (uint32_t) s.bsdf >= d.n_bsdfs) bad("shape references an invalid bsdf");
@@ -399,6 +402,16 @@ lrt_status lrt_bsdf_probe(lrt_scene *scene, const float *o, const float *d, cons
     LRT_CATCH
 }
 
+lrt_status lrt_phase_probe(lrt_scene *scene, int medium, const float *wi, const float *sample, const float *wo_query, uint32_t n, float *out, int device) {
+    if (!scene || ((!wi || !sample || !wo_query || !out) && n)) return fail(LRT_ERR_INVALID, "lrt_phase_probe: null argument");
+    if (medium < 0 || (size_t) medium >= scene->st.media.size()) return fail(LRT_ERR_INVALID, "lrt_phase_probe: no such medium");
+    LRT_TRY
+        ensure_device(scene, device);
+        device_phase_probe(scene->dev, medium, wi, sample, wo_query, n, out);
+        return LRT_OK;
+    LRT_CATCH
+}
+
 static lrt_medium_desc *find_medium(lrt_scene *s, const char *key, const char **rest) {
     for (auto &M : s->st.media) {
         size_t L = strlen(M.id);
@@ -439,7 +452,7 @@ lrt_status lrt_param_set(lrt_scene *scene, const char *key, const float *v, int 
         else dst = M->sigma_lipid_water;
         for (int i = 0; i < 3; ++i) dst[i] = v[n == 3 ? i : 0];
     } else if (M->type == LRT_MEDIUM_PARENCHYMA && !strcmp(rest, "sigma_hepatocity")) M->sigma_hepatocity = v[0];
-    else if (!strcmp(rest, "phase_function.g")) {
+    else if (!strcmp(rest, "phase_function.g") && !(scene->st.desc.n_phases && M->phase_index >= 0)) {     // (a medium with an entry of the phase table has no parameter keys)
         // mi.traverse exposes `g` for an hg phase function only (src/phase/hg.cpp:60-62; isotropic.cpp has no parameter).  The
         // one extension kept from round 1: a NON-ZERO g on an isotropic medium turns it into hg ("HG variant ...
         // supplied through lrt_param_set"); g = 0 on an isotropic medium is rejected like any unknown key.

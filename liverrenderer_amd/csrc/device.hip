@@ -96,7 +96,7 @@ struct DeviceScene {
     std::vector<DMedium> h_media; DMedium *d_media = nullptr;
     std::vector<DBioMedium> h_bio; DBioMedium *d_bio = nullptr;
     std::vector<DHetMedium> h_het; DHetMedium *d_het = nullptr; std::vector<float *> het_data; bool has_het = false, has_non_bio = false, need_mis = false; uint32_t ws_layouts = 0;   // ws_layouts: the record layouts the workspace is allocated for (layout_bit mask)
-    bool ext = false;                      // spheres, point emitters, area emitters on meshes or a roughdielectric on a shape: the EXT kernel instances (ExtTracer, point- / mesh-emitter sampling, the rough BSDF), wide records
+    bool ext = false;                      // spheres, point emitters, area emitters on meshes, a roughdielectric on a shape or a tabulated / Rayleigh / blended phase function on a referenced medium: the EXT kernel instances (ExtTracer, point- / mesh-emitter sampling, the rough BSDF, DScene::phases), wide records
     bool has_area_emitter = false;         // decides the record layout: only an area emitter's pdf reads the last scatter position (record_layout.h)
     float *dgrid = nullptr; size_t dgrid_floats = 0;   // lrt_render_backward_grid with a host result: the device-side gradient grid
     bool prb_null = false;                 // prbvolpath.py:84-91 `handle_null_scattering`: a heterogeneous medium is attached to a shape
@@ -315,6 +315,8 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
     sc.mesh_emitters = up(P.mesh_emitters);
     sc.mesh_emitter_tab = up(P.mesh_emitter_tab);
     sc.cone_tab = P.cone_tab.empty() ? nullptr : (const uint2 *) up(P.cone_tab);      // (sc.cone_enabled: set by the preparation with the table)
+    sc.phases = P.phases.empty() ? nullptr : up(P.phases);
+    sc.phase_pool = P.phase_pool.empty() ? nullptr : up(P.phase_pool);
     sc.env_data = (const float4 *) up(P.env_data);
     sc.env_hier = up(P.env_hier);
     HIP_CHECK(hipMalloc((void **) &D->d_sc, sizeof(DScene))); D->track(D->d_sc);
@@ -485,7 +487,7 @@ static void check_integrator_media(DeviceScene *D, int integrator) {
     if ((integrator == LRT_INTEGRATOR_BIOVOLPATH || integrator == LRT_INTEGRATOR_BIOVOLPATH06) && D->has_non_bio)
         throw std::runtime_error("NotImplementedError: sample_interaction (the bio integrators need liver / parenchyma / glissonCapsule media)");
     if (integrator == LRT_INTEGRATOR_PRBVOLPATH && D->ext)
-        throw std::runtime_error("unsupported: prbvolpath on a scene with sphere shapes, point emitters, area emitters on meshes or a roughdielectric BSDF (its adjoint is built for triangles, rectangle / infinite emitters and the diffuse / dielectric / null BSDFs)");
+        throw std::runtime_error("unsupported: prbvolpath on a scene with sphere shapes, point emitters, area emitters on meshes, a roughdielectric BSDF or a tabulated / Rayleigh / blended phase function (its adjoint is built for triangles, rectangle / infinite emitters, the diffuse / dielectric / null BSDFs and the isotropic / hg phase functions)");
     if (integrator == LRT_INTEGRATOR_VOLPATHMIS) D->need_mis = true;          // its wider path record is allocated on first use
 }
 
@@ -1120,9 +1122,20 @@ void device_bsdf_probe(DeviceScene *D, const float *o, const float *d, const flo
 // Test hook (include/liverrt.h lrt_math_eval): the transcendental kernels of csrc/dmath.h evaluated on the device, one lane per value.
 // orc_math.h holds the same polynomials written a second time, so bit-equality of the render lanes says nothing about their accuracy:
 // tests/test_parity_gpu.py bounds the DEVICE values against float64 and checks them bit for bit against the oracle's twins.
+// The kernel is also where lrt_phase_probe runs: the set of compiled kernels is pinned (tests/golden/kernel_names.txt), and this kernel is the
+// one whose first argument already selects what a lane evaluates.  fn = LRT_MATH_PHASE_PROBE + m (device_phase_probe only; lrt_math_eval
+// refuses it): `y` is the scene record, `x` holds 9 floats per lane (wi, sample, wo_query), `out` takes LRT_PHASE_PROBE_FLOATS per lane
+// for medium m, out2 is not written.
+#define LRT_MATH_PHASE_PROBE 0x100
 __global__ void k_math_eval(int fn, const float *__restrict__ x, const float *__restrict__ y, uint32_t n, float *__restrict__ out, float *__restrict__ out2) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (fn >= LRT_MATH_PHASE_PROBE) {
+        SceneRef sc = *(ScenePtr) (const void *) y;
+        const float *in = x + 9 * (size_t) i;
+        phase_probe_lane(sc, fn - LRT_MATH_PHASE_PROBE, in, in + 3, in + 6, out + (size_t) LRT_PHASE_PROBE_FLOATS * i);
+        return;
+    }
     float a = 0.f, b = 0.f;
     switch (fn) {
         case 0: a = m_log(x[i]); break;
@@ -1136,13 +1149,14 @@ __global__ void k_math_eval(int fn, const float *__restrict__ x, const float *__
         case 8: a = rcp(x[i]); break;
         case 9: a = m_erf(x[i]); break;
         case 10: a = m_erfinv(x[i]); break;
+        case 11: a = m_cbrt(x[i]); break;
         default: break;
     }
     out[i] = a; out2[i] = b;
 }
 void device_math_eval(int fn, const float *x, const float *y, uint32_t n, float *out, float *out2, int device) {
     select_device(device);
-    if (fn < 0 || fn > 10) throw std::invalid_argument("lrt_math_eval: function 0 .. 10");
+    if (fn < 0 || fn > 11) throw std::invalid_argument("lrt_math_eval: function 0 .. 11");
     if (!n) return;
     DevTmp dx(n), dy(n), d1(n), d2(n);
     HIP_CHECK(hipMemcpy(dx.p, x, (size_t) n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dy.p, y ? y : x, (size_t) n * 4, hipMemcpyHostToDevice));
@@ -1150,6 +1164,23 @@ void device_math_eval(int fn, const float *x, const float *y, uint32_t n, float 
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpy(out, d1.p, (size_t) n * 4, hipMemcpyDeviceToHost));
     if (out2) HIP_CHECK(hipMemcpy(out2, d2.p, (size_t) n * 4, hipMemcpyDeviceToHost));
+}
+
+// Test hook (include/liverrt.h lrt_phase_probe): phase_probe_lane (kernels.h) on the scene's device image, through k_math_eval's selector
+// LRT_MATH_PHASE_PROBE (above)
+void device_phase_probe(DeviceScene *D, int medium, const float *wi, const float *sample, const float *wo_query, uint32_t n, float *out) {
+    HIP_CHECK(hipSetDevice(D->device));
+    if (medium < 0 || (size_t) medium >= D->h_media.size()) throw std::invalid_argument("lrt_phase_probe: no such medium");
+    if (!n) return;
+    hipStream_t st = D->stream;
+    std::vector<float> packed((size_t) n * 9);               // per lane: wi, sample, wo_query
+    for (size_t i = 0; i < n; ++i) for (int c = 0; c < 3; ++c) { packed[9 * i + c] = wi[3 * i + c]; packed[9 * i + 3 + c] = sample[3 * i + c]; packed[9 * i + 6 + c] = wo_query[3 * i + c]; }
+    DevTmp in, dout((size_t) n * LRT_PHASE_PROBE_FLOATS);
+    in.upload(packed.data(), packed.size(), st);
+    k_math_eval<<<(n + 255) / 256, 256, 0, st>>>(LRT_MATH_PHASE_PROBE + medium, in.p, (const float *) D->d_sc, n, dout.p, nullptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * LRT_PHASE_PROBE_FLOATS * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
 }
 
 // ---- guided denoiser (kernels_denoise.h)

@@ -42,8 +42,25 @@ struct DMedium {
     float scale; int32_t het;            // sigma_t = property * scale (needed by the PRB adjoint); het: heterogeneous (sc.het[index])
     float w_spec[3], w_plain[3];         // real-scattering weights sigma_s / mean(sigma_t / combined), sigma_s / sigma_t (k_medium_prepare)
     float nee_vmin[3];                   // per channel: 1 - u >= nee_vmin proves that the free-flight distance -log(1 - u) / sigma_t stays below the distance
-    float pad2[3];                       // of every sample of an infinite emitter (upload_media; volpath_iteration's early NEE rejection)
+    int32_t phase_ext;                   // of every sample of an infinite emitter (upload_media; volpath_iteration's early NEE rejection)
+    float pad2[2];                       // phase_ext: 1 + the medium's entry in DScene::phases, 0: `phase` / `g` above (the EXT instances only read it)
 };
+static_assert(sizeof(DMedium) == 96, "DMedium stride");
+
+// Phase functions beyond isotropic / HG (src/phase/tabphase.cpp, rayleigh.cpp, blendphase.cpp): DScene::phases, read by the EXT instances only.
+// A tabulated entry is ContinuousDistribution's state (include/mitsuba/core/distr_1d.h:599-609) over DScene::phase_pool:
+//   rec_off: n - 1 interval records of 4 floats, 16-byte aligned: (values[i], values[i + 1], i ? cdf[i - 1] : 0, cdf[i]), so that the three
+//            gathers of eval_pdf / sample (y0, y1, c0) are one vector load from one aligned record;
+//   cdf_off: the plain cdf, n - 1 floats, which the binary search walks (one dword per trip).
+struct DPhase {
+    int32_t type; float g, weight; int32_t child0, child1;      // LRT_PHASE_*; hg; blend (weight clipped to [0, 1], children never blends)
+    uint32_t n;                                                 // tabulated: number of values
+    float interval_size, inv_interval_size, integral, normalization;
+    uint32_t valid_x, valid_y;                                  // first and last interval with mass
+    uint32_t rec_off, cdf_off;                                  // into phase_pool (floats)
+    uint32_t pad[2];
+};
+static_assert(sizeof(DPhase) == 64, "DPhase stride");
 
 // bio media (liver / parenchyma / glissonCapsule): element coefficients of the 5-argument sample_interaction
 // (kernels_bio.h); kept apart from DMedium so that the path / volpath kernels' medium loads stay as they are
@@ -161,6 +178,8 @@ struct DScene {
     const float *mesh_emitter_tab;       // every mesh emitter's pmf and cdf
     const uint2 *cone_tab;               // per face and side (2 * face + side): the free lengths of LRT_CONE_BINS direction cones as binary16, rounded down (scene_prep.cpp: build_cone_table); null: none
     int32_t cone_enabled, pad_cone;      // the closed-records volpath kernels only read the table
+    const DPhase *phases;                // tabulated / Rayleigh / blended phase functions and a blend's children (DMedium::phase_ext; the EXT instances only read them)
+    const float *phase_pool;             // every tabulated entry's interval records and cdf
 };
 
 // Direction bins of DScene::cone_tab: bin k holds the directions whose cosine to the side's geometric normal is at least LRT_CONE_COSk

@@ -1065,6 +1065,20 @@ DEV uint32_t mesh_emitter_search(const float *__restrict__ cdf, uint32_t n, floa
     }
     return start;
 }
+// The same loop over [start, end] with `s` already scaled by the distribution's total: ContinuousDistribution::sample (distr_1d.h:429-446, the
+// tabulated phase function below) runs it over [valid.x, valid.y] with the same predicate.  (Kept beside mesh_emitter_search, not under it:
+// folding the two moved instructions in the kernels that sample mesh emitters, which this addition leaves as they were.)
+DEV uint32_t cdf_search(const float *__restrict__ cdf, uint32_t start, uint32_t end, float total, float s) {
+    const uint32_t trips = end > start ? 32u - (uint32_t) __builtin_clz(end - start) : 0u;
+    for (uint32_t i = 0; i < trips; ++i) {
+        const uint32_t middle = (start + end) >> 1;
+        const float c = cdf[middle];
+        const bool pred = (c < s || c == 0.f) && c != total;
+        start = pred ? min(middle + 1u, end) : start;
+        end = pred ? end : middle;
+    }
+    return start;
+}
 // Mesh::sample_position (src/render/mesh.cpp:861-935): `sy` picks the face (DiscreteDistribution::sample_reuse, distr_1d.h:174-182)
 // and is replaced by its re-scaled value, then warp::square_to_uniform_triangle (include/mitsuba/core/warp.h:153-156).
 DEV void mesh_emitter_position(SceneRef sc, const DMeshEmitter &M, float sx, float sy, V3 *p_out, V3 *n_out) {
@@ -1347,6 +1361,104 @@ DEV void phase_sample(const DMedium &M, V3 wi, float s2x, float s2y, V3 *wo, flo
     }
 }
 DEV float phase_eval(const DMedium &M, V3 wi, V3 wo) { return M.phase == LRT_PHASE_HG ? hg_eval(M.g, dot(wo, wi)) : kInvFourPi; }
+
+// ------------------------------------------------- tabulated, Rayleigh and blended phase functions
+// (src/phase/tabphase.cpp, rayleigh.cpp, blendphase.cpp; DPhase in device_types.h).  Compiled into the EXT instances and k_math_eval (fn 11, and the
+// phase probe it hosts) alone: phase_sample<false> / phase_eval<false> are the two functions above.
+// cbrt stands in for Dr.Jit's dr::cbrt (rayleigh.cpp:63-64): exp(log|x| / 3) and one Newton step on y^3 = |x| with the residual formed by an
+// fma; measured against float64 through lrt_math_eval fn 11: at most 1 ulp over the normal floats.  +-0, inf and NaN
+// return x; subnormal arguments are not served (the Rayleigh inversion's arguments lie in [0.236, 4.24]).
+DEV float m_cbrt(float x) {
+    const float a = __builtin_fabsf(x);
+    if (!(a > 0.f) || a == kInf) return x;
+    float y = m_exp(m_log(a) * 0.333333343f);
+    const float y2 = y * y;
+    y = y - fma_(y2, y, -a) / (3.f * y2);
+    return mulsign(y, x);
+}
+// ContinuousDistribution::eval_pdf_normalized over [-1, 1] (distr_1d.h:370-392): 0 outside the range (the masked gathers read 0)
+DEV float tab_eval_pdf(SceneRef sc, const DPhase &P, float x) {
+    if (!(x >= -1.f && x <= 1.f)) return 0.f;
+    const float xs = (x - (-1.f)) * P.inv_interval_size;
+    const uint32_t index = min((uint32_t) xs, P.n - 2u);
+    const float4 r = *(const float4 *) (sc.phase_pool + P.rec_off + 4u * index);
+    const float w1 = xs - (float) index, w0 = 1.f - w1;
+    return fma_(w0, r.x, w1 * r.y) * P.normalization;
+}
+// ContinuousDistribution::sample (distr_1d.h:429-459)
+DEV float tab_sample(SceneRef sc, const DPhase &P, float sample) {
+    sample *= P.integral;
+    const uint32_t index = cdf_search(sc.phase_pool + P.cdf_off, P.valid_x, P.valid_y, P.integral, sample);
+    const float4 r = *(const float4 *) (sc.phase_pool + P.rec_off + 4u * index);
+    const float y0 = r.x, y1 = r.y, c0 = r.z;
+    sample = (sample - c0) * P.inv_interval_size;
+    const float t_linear = (y0 - safe_sqrt(fma_(y0, y0, 2.f * sample * (y1 - y0)))) * rcp(y0 - y1),
+                t_const = sample * rcp(y0),
+                t = y0 == y1 ? t_const : t_linear;
+    return fma_((float) index + t, P.interval_size, -1.f);
+}
+DEV float rayleigh_eval(float cos_theta) { return ((3.f / 16.f) * kInvPi) * (1.f + sqr(cos_theta)); }    // rayleigh.cpp:50-52
+
+// One leaf (isotropic, hg, tabphase, rayleigh): PhaseFunction::sample -> wo, pdf (every leaf's weight is 1), and eval_pdf (eval = pdf in all four)
+DEV void phase_leaf_sample(SceneRef sc, const DPhase &P, V3 wi, float s2x, float s2y, V3 *wo, float *pdf) {
+    if (P.type == LRT_PHASE_TABULATED) {                    // tabphase.cpp:77-103
+        const float cos_theta_prime = tab_sample(sc, P, s2x);
+        const float sin_theta_prime = safe_sqrt(1.f - cos_theta_prime * cos_theta_prime);
+        float sp, cp; m_sincos(2.f * kPi * s2y, &sp, &cp);
+        Frame f(wi);
+        *wo = -f.to_world(V3(sin_theta_prime * cp, sin_theta_prime * sp, cos_theta_prime));
+        *pdf = tab_eval_pdf(sc, P, cos_theta_prime) * kInvTwoPi;
+    } else if (P.type == LRT_PHASE_RAYLEIGH) {              // rayleigh.cpp:54-74
+        const float z = 2.f * (2.f * s2x - 1.f);
+        const float tmp = __builtin_sqrtf(sqr(z) + 1.f);
+        const float A = m_cbrt(z + tmp), B = m_cbrt(z - tmp);
+        const float cos_theta = A + B;
+        const float sin_theta = safe_sqrt(1.f - sqr(cos_theta));
+        float sp, cp; m_sincos(kTwoPi * s2y, &sp, &cp);
+        Frame f(wi);
+        *wo = f.to_world(V3(sin_theta * cp, sin_theta * sp, cos_theta));
+        *pdf = rayleigh_eval(-cos_theta);
+    } else {
+        DMedium M; M.phase = P.type; M.g = P.g;
+        phase_sample(M, wi, s2x, s2y, wo, pdf);
+    }
+}
+DEV float phase_leaf_eval(SceneRef sc, const DPhase &P, V3 wi, V3 wo) {
+    if (P.type == LRT_PHASE_TABULATED) return tab_eval_pdf(sc, P, -dot(wo, wi)) * kInvTwoPi;     // tabphase.cpp:105-118
+    if (P.type == LRT_PHASE_RAYLEIGH) return rayleigh_eval(dot(wo, wi));                         // rayleigh.cpp:76-83
+    return P.type == LRT_PHASE_HG ? hg_eval(P.g, dot(wo, wi)) : kInvFourPi;
+}
+
+// PhaseFunction::sample(ctx, mei, s1, (s2x, s2y)) -> wo, pdf, weight.  EXT: the medium may carry an entry of DScene::phases; without it
+// this is phase_sample above, `s1` unused and the weight 1.
+template <bool EXT>
+DEV void phase_sample(SceneRef sc, const DMedium &M, V3 wi, float s1, float s2x, float s2y, V3 *wo, float *pdf, float *weight) {
+    *weight = 1.f;
+    if (!EXT || M.phase_ext == 0) { phase_sample(M, wi, s2x, s2y, wo, pdf); return; }
+    const DPhase P = tab(sc.phases, (uint32_t) (M.phase_ext - 1));
+    if (P.type != LRT_PHASE_BLEND) { phase_leaf_sample(sc, P, wi, s2x, s2y, wo, pdf); return; }
+    // blendphase.cpp:122-153 (the children are leaves: they ignore the re-scaled s1, and their weights are 1)
+    const float w = P.weight;
+    const bool m0 = s1 > w;
+    const DPhase Ps = tab(sc.phases, (uint32_t) (m0 ? P.child0 : P.child1)), Po = tab(sc.phases, (uint32_t) (m0 ? P.child1 : P.child0));
+    float pdf_s; phase_leaf_sample(sc, Ps, wi, s2x, s2y, wo, &pdf_s);
+    const float pdf_o = phase_leaf_eval(sc, Po, wi, *wo);
+    const float pdf0 = m0 ? pdf_s : pdf_o, pdf1 = m0 ? pdf_o : pdf_s;
+    const float pdf_weighted = w * pdf1 + (1.f - w) * pdf0;
+    // (with the sampled child's weight 1 and eval = pdf, both of the source's numerators, w * eval1 + (1 - w) * w0 * pdf0 and
+    //  w * w1 * pdf1 + (1 - w) * eval0, are pdf_weighted's own expression: the quotient is 1 up to the rounding of rcp, or 0)
+    *weight = pdf_weighted * (pdf_weighted > 0.f ? rcp(pdf_weighted) : 0.f);
+    *pdf = pdf_weighted;
+}
+// PhaseFunction::eval_pdf: the value (the pdf equals it in every family)
+template <bool EXT>
+DEV float phase_eval(SceneRef sc, const DMedium &M, V3 wi, V3 wo) {
+    if (!EXT || M.phase_ext == 0) return phase_eval(M, wi, wo);
+    const DPhase P = tab(sc.phases, (uint32_t) (M.phase_ext - 1));
+    if (P.type != LRT_PHASE_BLEND) return phase_leaf_eval(sc, P, wi, wo);
+    const float v0 = phase_leaf_eval(sc, tab(sc.phases, (uint32_t) P.child0), wi, wo), v1 = phase_leaf_eval(sc, tab(sc.phases, (uint32_t) P.child1), wi, wo);
+    return fma_(v1, P.weight, fma_(-v0, P.weight, v0));         // dr::lerp(v0, v1, weight), blendphase.cpp:182-188
+}
 
 DEV int target_medium(const DShape &sd, V3 d, V3 n) { return dot(d, n) > 0.f ? sd.exterior_medium : sd.interior_medium; }
 DEV bool is_medium_transition(const DShape &sd) { return sd.interior_medium >= 0 || sd.exterior_medium >= 0; }

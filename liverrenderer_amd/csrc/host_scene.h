@@ -22,6 +22,8 @@ struct SceneStorage {
     std::vector<lrt_emitter_desc> emitters;
     std::vector<std::vector<float>> emdata;
     std::vector<std::vector<float>> meddata;   // heterogeneous media: grid values
+    std::vector<lrt_phase_desc> phases;        // the phase-function table
+    std::vector<std::vector<float>> phasedata; // tabulated entries: their values
     lrt_scene_desc desc{};
     // `aov` integrator (loader.cpp): its configuration and the developed channel names, beside the ordinary description
     bool has_aov = false;

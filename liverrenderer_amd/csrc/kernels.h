@@ -398,15 +398,16 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
             } else if (!rejected) {
                 DirSample ds;
                 V3 emitted = volpath_sample_emitter<HET>(sc, rng, mei.p, V3(0.f), false, 0, V3(0.f), medium, channel, &ds, tr, n_shadow);
-                float phase_val = phase_eval(M, mei.wi, ds.d);
+                float phase_val = phase_eval<TR::kExt>(sc, M, mei.wi, ds.d);
                 V3 c = throughput * phase_val * emitted * mis_weight(ds.pdf, ds.delta ? 0.f : phase_val);
                 result = result + c;
             }
         }
-        (void) rng.next();
+        const float s1 = rng.next();                                    // (the blend's lobe choice; unused without EXT)
         float s2x, s2y; rng.next2(s2x, s2y);
-        V3 wo; float phase_pdf; phase_sample(M, mei.wi, s2x, s2y, &wo, &phase_pdf);
+        V3 wo; float phase_pdf, phase_weight; phase_sample<TR::kExt>(sc, M, mei.wi, s1, s2x, s2y, &wo, &phase_pdf, &phase_weight);
         if (phase_pdf > 0.f) {
+            if (TR::kExt) throughput = throughput * phase_weight;       // volpath.cpp:296 (1 outside a blend)
             ray = spawn_ray(mei.p, V3(0.f), wo);
             s.last_pdf = phase_pdf;
         }
@@ -1059,6 +1060,17 @@ k_envmap_probe(ScenePtr scp, const float *__restrict__ dir, uint32_t n, float *_
     const V3 le = emitter_eval_env(sc, d);
     float *o = out + 4 * (size_t) i;
     o[0] = pdf; o[1] = le.x; o[2] = le.y; o[3] = le.z;
+}
+
+// Test hook (lrt_phase_probe), one lane: the phase function of medium `medium`, phase_sample<true> with the lane's wi and (s1, s2x, s2y)
+// as the EXT instances of the volume integrators call it, and phase_eval<true> at the world direction woq.  (k_math_eval in device.hip
+// runs it under its selector LRT_MATH_PHASE_PROBE: the hook adds no kernel symbol.)
+DEV void phase_probe_lane(SceneRef sc, int medium, const float *wi_in, const float *smp, const float *woq, float *o) {
+    const DMedium M = tab(sc.media, medium);
+    const V3 wi(wi_in[0], wi_in[1], wi_in[2]);
+    V3 wo; float pdf, weight; phase_sample<true>(sc, M, wi, smp[0], smp[1], smp[2], &wo, &pdf, &weight);
+    const float ev = phase_eval<true>(sc, M, wi, V3(woq[0], woq[1], woq[2]));
+    o[0] = wo.x; o[1] = wo.y; o[2] = wo.z; o[3] = weight; o[4] = pdf; o[5] = ev; o[6] = ev;     // (eval = pdf in every family)
 }
 
 // Test hook (lrt_bsdf_probe): the surface code at a chosen ray, one per lane: a closest-hit query through the EXT tracer (spheres count),

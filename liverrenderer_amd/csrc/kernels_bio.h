@@ -240,10 +240,11 @@ DEV bool biovolpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, con
         const DMedium M = tab(sc.media, medium);
         throughput = throughput * mei.transmittance;                    // :268 / :272
         tissue_depth += __builtin_fabsf(-ray.d.z * mei.t);              // |cos_theta(-ray.d) * mei.t|
-        (void) rng.next();
+        const float s1 = rng.next();
         float s2x, s2y; rng.next2(s2x, s2y);
-        V3 wo; float phase_pdf; phase_sample(M, -ray.d, s2x, s2y, &wo, &phase_pdf);
+        V3 wo; float phase_pdf, phase_weight; phase_sample<TR::kExt>(sc, M, -ray.d, s1, s2x, s2y, &wo, &phase_pdf, &phase_weight);
         if (phase_pdf > 0.f) {
+            if (TR::kExt) throughput = throughput * phase_weight;       // biovolpath.cpp:291 (1 outside a blend)
             ray = spawn_ray(mei.p, V3(0.f), wo);
             s.last_pdf = phase_pdf;
         }
@@ -352,9 +353,10 @@ DEV bool biovolpath06_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, c
     if (in_medium && mei.valid()) {                                     // :185-198
         const DMedium M = tab(sc.media, medium);
         throughput = throughput * mei.transmittance;
-        (void) rng.next();
+        const float s1 = rng.next();
         float s2x, s2y; rng.next2(s2x, s2y);
-        V3 wo; float phase_pdf; phase_sample(M, -ray.d, s2x, s2y, &wo, &phase_pdf);
+        V3 wo; float phase_pdf, phase_weight; phase_sample<TR::kExt>(sc, M, -ray.d, s1, s2x, s2y, &wo, &phase_pdf, &phase_weight);
+        if (TR::kExt) throughput = throughput * phase_weight;           // biovolpath06.cpp:191
         tissue_depth += __builtin_fabsf(-ray.d.z * mei.t);
         ray.o = mei.p; ray.d = wo; ray.maxt = kLargest;                 // Ray3f(mei.p, wo, time, wavelengths)
         null_chain = false; scattered_chain = true;

@@ -222,19 +222,20 @@ DEV bool volpathmis_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, con
             if (sample_emitters) {
                 DirSample ds; MisW<SMIS> nee_end, uni_end;
                 V3 emitted = mis_sample_emitter<SMIS>(sc, rng, mei.p, V3(0.f), false, 0u, medium, p_over_f, channel, &ds, nee_end, uni_end, tr, n_shadow);
-                const float pv = phase_eval(M, mei.wi, ds.d);
+                const float pv = phase_eval<TR::kExt>(sc, M, mei.wi, ds.d);
                 mis_update(nee_end, V3(1.f), V3(pv), channel, true);
                 mis_update(uni_end, V3(ds.delta ? 0.f : pv), V3(pv), channel, true);
                 result = result + mis_weight2(nee_end, uni_end) * emitted;
             }
             p_over_f_nee = p_over_f;
-            (void) rng.next();
+            const float s1 = rng.next();
             float s2x, s2y; rng.next2(s2x, s2y);
-            V3 wo; float phase_pdf; phase_sample(M, mei.wi, s2x, s2y, &wo, &phase_pdf);
+            V3 wo; float phase_pdf, phase_weight; phase_sample<TR::kExt>(sc, M, mei.wi, s1, s2x, s2y, &wo, &phase_pdf, &phase_weight);
             ray = spawn_ray(mei.p, V3(0.f), wo);
             needs_intersection = true;
-            mis_update(p_over_f, V3(phase_pdf), V3(1.f * phase_pdf), channel, true);
-            mis_update(p_over_f_nee, V3(1.f), V3(1.f * phase_pdf), channel, true);
+            const float phase_f = (TR::kExt ? phase_weight : 1.f) * phase_pdf;      // volpathmis.cpp:331-352: phase_weight * phase_pdf
+            mis_update(p_over_f, V3(phase_pdf), V3(phase_f), channel, true);
+            mis_update(p_over_f_nee, V3(1.f), V3(phase_f), channel, true);
         }
     }
     // ---- surface interactions

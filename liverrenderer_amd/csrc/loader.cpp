@@ -9,13 +9,14 @@
 // bio media carry both the homogeneous parameters that path / volpath /
 // prbvolpath see through the 4-argument sample_interaction() and the element
 // coefficients of the 5-argument one, docs/BIO_TRANSPORT_SPEC.md); phase
-// {isotropic, hg}; shape {obj, rectangle, cube, sphere}; emitter {area, envmap, constant, point}.
+// {isotropic, hg, tabphase, rayleigh, blendphase}; shape {obj, rectangle, cube, sphere}; emitter {area, envmap, constant, point}.
 // Plugin `type` names match without regard to case (plugin_type): the reference finds plugins by file name
 // (src/core/plugin.cpp:96-139), and the fork's SphereLiverPoint scenes, written on a case-insensitive file system, say
 // "Dielectric".  A medium child of a shape named neither "interior" nor "exterior" is ignored, as src/render/shape.cpp:40-49
 // ignores it.  A sphere is one shape without faces (lrt_shape_desc); the point emitter keeps its position in to_world.
 // An area emitter may be the child of a rectangle or of any triangle mesh (obj, cube); not of a sphere.
 #include "host_scene.h"
+#include "scene_prep.h"
 #include "xml.h"
 #include "image_io.h"
 #include <map>
@@ -38,6 +39,9 @@ void SceneStorage::fix_pointers() {
     desc.positions = positions.data(); desc.normals = normals.data(); desc.texcoords = texcoords.data();
     desc.faces = faces.data(); desc.face_shape = face_shape.data(); desc.shapes = shapes.data(); desc.bsdfs = bsdfs.data();
     desc.textures = textures.data(); desc.media = media.data(); desc.emitters = emitters.data();
+    phasedata.resize(phases.size());
+    for (size_t i = 0; i < phases.size(); ++i) { phases[i].values = phasedata[i].empty() ? nullptr : phasedata[i].data(); phases[i].n_values = (uint32_t) phasedata[i].size(); }
+    desc.n_phases = (uint32_t) phases.size(); desc.pad_phases = 0; desc.phases = phases.empty() ? nullptr : phases.data();
 }
 
 void SceneStorage::copy_from(const lrt_scene_desc &d) {
@@ -53,6 +57,9 @@ void SceneStorage::copy_from(const lrt_scene_desc &d) {
     media.assign(d.media, d.media + d.n_media);
     emitters.assign(d.emitters, d.emitters + d.n_emitters);
     texdata.assign(textures.size(), {}); emdata.assign(emitters.size(), {}); meddata.assign(media.size(), {});
+    phases.assign(d.phases, d.phases + (d.phases ? d.n_phases : 0)); phasedata.assign(phases.size(), {});
+    for (size_t i = 0; i < phases.size(); ++i)
+        if (phases[i].type == LRT_PHASE_TABULATED && phases[i].values) phasedata[i].assign(phases[i].values, phases[i].values + phases[i].n_values);
     for (size_t i = 0; i < media.size(); ++i)
         if (media[i].type == LRT_MEDIUM_HETEROGENEOUS && media[i].grid_data)
             meddata[i].assign(media[i].grid_data, media[i].grid_data + (size_t) media[i].grid_res[0] * media[i].grid_res[1] * media[i].grid_res[2]);
@@ -416,6 +423,44 @@ struct Loader {
         else fail("unsupported bsdf type \"" + o->type + "\"");
         S.bsdfs.push_back(B); int ix = (int) S.bsdfs.size() - 1; bsdf_ix[o.get()] = ix; return ix;
     }
+    // One entry of the phase table (lrt_phase_desc): tabphase, rayleigh, blendphase, and isotropic / hg as a blend's children.
+    // src/phase/tabphase.cpp:44-67, rayleigh.cpp:41-48, blendphase.cpp:70-92
+    int make_phase(const Obj &ph, bool top) {
+        lrt_phase_desc Q{}; Q.child[0] = Q.child[1] = -1;
+        std::vector<float> data;
+        if (ph.type == "isotropic") Q.type = LRT_PHASE_ISOTROPIC;
+        else if (ph.type == "hg") { Q.type = LRT_PHASE_HG; Q.g = get_float(ph, "g", 0.8f); if (!(Q.g > -1.f && Q.g < 1.f)) fail("The asymmetry parameter must lie in the interval (-1, 1)!"); }
+        else if (ph.type == "rayleigh") Q.type = LRT_PHASE_RAYLEIGH;
+        else if (ph.type == "tabphase") {
+            Q.type = LRT_PHASE_TABULATED;
+            auto it = ph.props.find("values");
+            if (it == ph.props.end()) fail("Property \"values\" has not been specified!");
+            if (it->second.tag != "string") fail("'values' must be a string");
+            const std::string v = attr(*it->second.node, "value");
+            for (size_t i = 0; i < v.size();) {            // string::tokenize(values, " ,"), then (ScalarFloat) std::stod per token
+                if (v[i] == ' ' || v[i] == ',') { ++i; continue; }
+                size_t j = i; while (j < v.size() && v[j] != ' ' && v[j] != ',') ++j;
+                const std::string tok = v.substr(i, j - i); i = j;
+                try { data.push_back((float) std::stod(tok)); } catch (...) { fail("Could not parse floating point value '" + tok + "'"); }
+            }
+            PhaseTable T; phase_table(data.data(), data.size(), T);      // the reference's constructor errors
+            if (!(T.integral > 0.f) || !std::isfinite(T.integral)) fail("ContinuousDistribution: no probability mass found!");
+        } else if (ph.type == "blendphase") {
+            if (!top) fail("unsupported: a blendphase as the child of a blendphase (one level is built)");
+            Q.type = LRT_PHASE_BLEND;
+            int n = 0;
+            for (auto &c : ph.children) if (c.second->tag == "phase") {
+                if (n == 2) fail("BlendPhase: Cannot specify more than two child phase functions");
+                Q.child[n++] = make_phase(*c.second, false);
+            }
+            for (auto &c : ph.children) if (c.second->tag == "volume" && c.first == "weight") fail("unsupported: a volume as the weight of a blendphase (a constant weight is built)");
+            if (!has(ph, "weight")) fail("Property \"weight\" has not been specified!");
+            Q.weight = get_float(ph, "weight", 0.f);
+            if (n != 2) fail("BlendPhase: Two child phase functions must be specified!");
+        } else fail("unsupported phase function \"" + ph.type + "\"");
+        S.phases.push_back(Q); S.phasedata.resize(S.phases.size()); S.phasedata.back() = std::move(data);
+        return (int) S.phases.size() - 1;
+    }
     int make_medium(const ObjP &o) {
         auto it = medium_ix.find(o.get()); if (it != medium_ix.end()) return it->second;
         lrt_medium_desc M{};
@@ -439,9 +484,10 @@ struct Loader {
         M.scale = get_float(*o, "scale", 1.f);
         M.has_spectral_extinction = get_bool(*o, "has_spectral_extinction", !parenchyma);
         M.sample_emitters = get_bool(*o, "sample_emitters", !parenchyma);
-        M.phase = LRT_PHASE_ISOTROPIC; M.g = 0.f;
+        M.phase = LRT_PHASE_ISOTROPIC; M.g = 0.f; M.phase_index = -1;
         if (ObjP ph = child(*o, "phase")) {
             if (ph->type == "hg") { M.phase = LRT_PHASE_HG; M.g = get_float(*ph, "g", 0.8f); if (!(M.g > -1.f && M.g < 1.f)) fail("The asymmetry parameter must lie in the interval (-1, 1)!"); }
+            else if (ph->type == "tabphase" || ph->type == "rayleigh" || ph->type == "blendphase") M.phase_index = make_phase(*ph, true);   // an entry of the phase table
             else if (ph->type != "isotropic") fail("unsupported phase function \"" + ph->type + "\"");
         }
         // ---- bio parameters of the 5-argument sample_interaction (docs/BIO_TRANSPORT_SPEC.md section 2)
@@ -896,6 +942,10 @@ struct Loader {
         bool ext = false;                       // spheres / point / mesh emitters: prbvolpath's adjoint is built for triangles and rectangle / infinite emitters
         for (auto &sh : S.shapes) ext = ext || sh.kind == LRT_SHAPE_SPHERE;
         for (auto &e : S.emitters) ext = ext || e.type == LRT_EMITTER_POINT || (e.type == LRT_EMITTER_AREA && S.shapes[e.shape].kind == LRT_SHAPE_MESH);
+        bool phase_ext = false;                 // a tabulated / Rayleigh / blended phase function on a medium that a shape or the sensor references (scene_prep.cpp)
+        auto ext_medium = [&](int m) { return m >= 0 && S.media[m].phase_index >= 0; };
+        for (auto &sh : S.shapes) phase_ext = phase_ext || ext_medium(sh.interior_medium) || ext_medium(sh.exterior_medium);
+        phase_ext = phase_ext || ext_medium(S.desc.sensor.medium);
         bool rough = false;                     // a roughdielectric on a shape, nested or not: it runs on the EXT instances too (scene_prep.cpp)
         for (auto &sh : S.shapes) if (sh.bsdf >= 0) {
             const lrt_bsdf_desc &B = S.bsdfs[sh.bsdf];
@@ -905,6 +955,7 @@ struct Loader {
         for (int k = 0; S.has_aov && k < S.aov.n_integrators; ++k) prb = prb || S.aov.integrators[k].type == LRT_INTEGRATOR_PRBVOLPATH;
         if (ext && prb) fail("unsupported: prbvolpath on a scene with sphere shapes, point emitters or area emitters on meshes");
         if (rough && prb) fail("unsupported: prbvolpath on a scene with a roughdielectric BSDF (no adjoint is built for it)");
+        if (phase_ext && prb) fail("unsupported: prbvolpath on a scene with a tabulated / Rayleigh / blended phase function (no adjoint is built for them)");
         S.fix_pointers();
     }
 };

@@ -398,6 +398,12 @@ void prepare_geometry(const lrt_scene_desc &d, const PrepOptions &opt, PreparedS
         const lrt_bsdf_desc &B = d.bsdfs[b];
         if (B.type == LRT_BSDF_ROUGHDIELECTRIC || (B.type == LRT_BSDF_BUMPMAP && B.nested >= 0 && (uint32_t) B.nested < d.n_bsdfs && d.bsdfs[B.nested].type == LRT_BSDF_ROUGHDIELECTRIC)) P.ext = true;
     }
+    // So does a tabulated / Rayleigh / blended phase function on a medium that a shape or the sensor references (again, an unreferenced one changes nothing)
+    {
+        auto ext_medium = [&](int32_t m) { return m >= 0 && (uint32_t) m < d.n_media && medium_has_phase_entry(d, (uint32_t) m); };
+        if (ext_medium(d.sensor.medium)) P.ext = true;
+        for (uint32_t i = 0; i < d.n_shapes; ++i) if (ext_medium(d.shapes[i].interior_medium) || ext_medium(d.shapes[i].exterior_medium)) P.ext = true;
+    }
     // ---- acceleration structure
     // Leaf size: the smallest of 2, 3, 4, 6, 8, 12, 16 triangles whose BVH image fits the LDS next to the traversal stacks (fatter
     // leaves = fewer nodes: more triangle tests per leaf, but every fetch of the traversal stays in LDS; Liver-MultiMesh's two meshes
@@ -513,6 +519,7 @@ void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedSc
     }
     // ---- media: what the scene as a whole needs to know about them (the tables themselves: prepare_media)
     if (d.n_media > 64) throw std::runtime_error("at most 64 media are supported");
+    prepare_phases(d, P.phases, P.phase_pool);
     for (uint32_t i = 0; i < d.n_media; ++i) {
         const lrt_medium_desc &M = d.media[i];
         if (M.type == LRT_MEDIUM_HOMOGENEOUS || M.type == LRT_MEDIUM_HETEROGENEOUS) P.has_non_bio = true;
@@ -604,6 +611,7 @@ void prepare_media(const lrt_scene_desc &d, float bsphere_r, std::vector<DMedium
         for (int k = 0; k < 3; ++k) { o.sigma_t[k] = medium_sigma_t(M, k); o.albedo[k] = M.albedo[k]; }   // homogeneous.cpp:121-126 eval_sigmat
         o.has_spectral_extinction = M.has_spectral_extinction; o.sample_emitters = M.sample_emitters; o.phase = M.phase; o.g = M.g;
         o.scale = M.scale; o.het = M.type == LRT_MEDIUM_HETEROGENEOUS ? 1 : 0;
+        o.phase_ext = medium_has_phase_entry(d, i) ? M.phase_index + 1 : 0;
         // Early NEE rejection (volpath_iteration): an infinite emitter's sample lies at distance >= 2 r (r: the scene's bounding sphere); the
         // kernel rejects when -log(1 - u) / sigma_t <= bound(dist), bound(x) = x * 0.998f - 1e-3f (monotone in x).  1 - u >= vmin implies that
         // for dist = 2 r, hence for every sample: vmin = exp(-sigma_t bound(2 r) (1 - 1e-4)) (1 + 1e-4), far outside the 3e-7 relative error
@@ -623,6 +631,76 @@ void prepare_media(const lrt_scene_desc &d, float bsphere_r, std::vector<DMedium
         for (int k = 0; k < 3; ++k) { o.res[k] = M.grid_res[k]; o.bbox_min[k] = M.grid_bbox_min[k]; o.bbox_max[k] = M.grid_bbox_max[k]; }
         for (int k = 0; k < 12; ++k) o.to_local[k] = M.grid_to_local[k];
         o.scale = M.scale; o.max_density = M.scale * M.grid_max;                    // heterogeneous.cpp:164,171
+    }
+}
+
+void phase_table(const float *values, size_t size, PhaseTable &out) {
+    if (size < 2) throw std::runtime_error("ContinuousDistribution: needs at least two entries!");
+    out.cdf.assign(size - 1, 0.f);
+    uint32_t vx = (uint32_t) -1, vy = (uint32_t) -1;
+    const double range = double(1.f) - double(-1.f), interval_size = range / (double) (size - 1);
+    double integral = 0.;
+    for (size_t i = 0; i < size - 1; ++i) {
+        const double y0 = (double) values[i], y1 = (double) values[i + 1];
+        const double value = 0.5 * interval_size * (y0 + y1);
+        integral += value;
+        out.cdf[i] = (float) integral;
+        if (y0 < 0. || y1 < 0.) throw std::runtime_error("ContinuousDistribution: entries must be non-negative!");
+        else if (value > 0.) { if (vx == (uint32_t) -1) vx = (uint32_t) i; vy = (uint32_t) i; }
+    }
+    if (vx == (uint32_t) -1 || vy == (uint32_t) -1) throw std::runtime_error("ContinuousDistribution: no probability mass found!");
+    out.valid_x = vx; out.valid_y = vy;
+    out.integral = out.cdf[vy]; out.normalization = 1.f / out.integral;
+    out.interval_size = (float) interval_size; out.inv_interval_size = 1.f / out.interval_size;
+}
+
+void validate_phases(const lrt_scene_desc &d) {
+    auto bad = [](const std::string &m) { throw std::runtime_error("phase table: " + m); };
+    if (d.n_phases && !d.phases) bad("null array");
+    for (uint32_t i = 0; i < d.n_phases; ++i) {
+        const lrt_phase_desc &Q = d.phases[i];
+        if (Q.type < LRT_PHASE_ISOTROPIC || Q.type > LRT_PHASE_BLEND) bad("invalid phase function");
+        if (Q.type == LRT_PHASE_HG && !(Q.g > -1.f && Q.g < 1.f)) bad("The asymmetry parameter must lie in the interval (-1, 1)!");
+        if (Q.type == LRT_PHASE_TABULATED) {
+            if (Q.n_values && !Q.values) bad("tabulated phase function without values");
+            for (uint32_t k = 0; k < Q.n_values; ++k) if (!std::isfinite(Q.values[k])) bad("tabulated phase function with a value that is not finite");
+            PhaseTable T; phase_table(Q.values, Q.n_values, T);
+            if (!(T.integral > 0.f) || !std::isfinite(T.integral)) bad("ContinuousDistribution: no probability mass found!");
+        }
+        if (Q.type == LRT_PHASE_BLEND) {
+            if (!(Q.weight == Q.weight)) bad("blendphase with a weight that is not a number");
+            for (int32_t c : { Q.child[0], Q.child[1] }) {
+                if (c < 0 || (uint32_t) c >= d.n_phases) bad("blendphase references an invalid child");
+                if (d.phases[c].type == LRT_PHASE_BLEND) throw std::runtime_error("unsupported: a blendphase as the child of a blendphase (one level is built)");
+            }
+        }
+    }
+    for (uint32_t m = 0; m < d.n_media && d.n_phases; ++m) {
+        const int32_t ix = d.media[m].phase_index;
+        if (ix < -1 || ix >= (int32_t) d.n_phases) bad("medium references an invalid entry");
+        // (isotropic / hg entries are a blend's children: a medium that scatters by one of them says so in `phase` / `g`, keeps its parameter key and its kernels)
+        if (ix >= 0 && d.phases[ix].type < LRT_PHASE_TABULATED) bad("medium references an isotropic / hg entry (a medium's entry is tabulated, rayleigh or blend; use the medium's `phase` / `g`)");
+    }
+}
+
+void prepare_phases(const lrt_scene_desc &d, std::vector<DPhase> &phases, std::vector<float> &pool) {
+    phases.clear(); pool.clear();
+    if (!d.n_phases) return;
+    validate_phases(d);
+    phases.resize(d.n_phases);
+    for (uint32_t i = 0; i < d.n_phases; ++i) {
+        const lrt_phase_desc &Q = d.phases[i]; DPhase &o = phases[i]; memset(&o, 0, sizeof(o));
+        o.type = Q.type; o.g = Q.g; o.child0 = o.child1 = 0;
+        if (Q.type == LRT_PHASE_BLEND) { o.weight = std::min(std::max(Q.weight, 0.f), 1.f); o.child0 = Q.child[0]; o.child1 = Q.child[1]; }   // blendphase.cpp:156-159 eval_weight
+        if (Q.type != LRT_PHASE_TABULATED) continue;
+        PhaseTable T; phase_table(Q.values, Q.n_values, T);
+        o.n = Q.n_values; o.interval_size = T.interval_size; o.inv_interval_size = T.inv_interval_size; o.integral = T.integral; o.normalization = T.normalization;
+        o.valid_x = T.valid_x; o.valid_y = T.valid_y;
+        o.rec_off = (uint32_t) pool.size();                    // (a multiple of 4 floats: every entry pads its cdf below)
+        for (uint32_t k = 0; k + 1 < Q.n_values; ++k) { pool.push_back(Q.values[k]); pool.push_back(Q.values[k + 1]); pool.push_back(k ? T.cdf[k - 1] : 0.f); pool.push_back(T.cdf[k]); }
+        o.cdf_off = (uint32_t) pool.size();
+        pool.insert(pool.end(), T.cdf.begin(), T.cdf.end());
+        while (pool.size() % 4) pool.push_back(0.f);
     }
 }
 

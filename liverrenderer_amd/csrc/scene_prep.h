@@ -40,6 +40,7 @@ struct PreparedScene {
     // cam, film and the distance field's geometry (grid.enabled set, grid.d null: the upload side builds the field).  Every pointer is null.
     DScene sc{};
     float grid_abs_margin = 0.f;                       // k_build_dist_grid's margin
+    std::vector<DPhase> phases; std::vector<float> phase_pool;   // DScene::phases / phase_pool (prepare_phases); empty: the description has no phase table
     std::vector<uint16_t> cone_tab;                    // build_cone_table's rows, 2 * LRT_CONE_BINS binary16 per face; empty: no table (sc.cone_enabled = 0)
     bool env_interior_positive = false;                // envmap: rows 1..h-2 of the sampling density strictly positive
     bool ext = false, has_area_emitter = false, has_het = false, has_non_bio = false, prb_null = false, use_lds = false;   // DeviceScene's flags of the same names
@@ -70,6 +71,19 @@ inline float medium_sigma_t(const lrt_medium_desc &M, int k) { return M.sigma_t[
 // The media tables (max(n_media, 1) entries each).  DBioMedium::log10_hep and DMedium::w_spec / w_plain are the device's to fill
 // (k_bio_prepare, k_medium_prepare); DHetMedium::data is the upload side's.  bsphere_r: DEnv::bsphere_r of the scene.
 void prepare_media(const lrt_scene_desc &d, float bsphere_r, std::vector<DMedium> &media, std::vector<DBioMedium> &bio, std::vector<DHetMedium> &het);
+
+// ContinuousDistribution(range = (-1, 1), values, n) as the reference's scalar constructor builds it (include/mitsuba/core/distr_1d.h:548-597):
+// the running integral in double, cdf[i] = (float) integral, `valid` = the first and last interval with mass.  Throws the reference's texts
+// ("needs at least two entries", "entries must be non-negative", "no probability mass found").
+struct PhaseTable { std::vector<float> cdf; float interval_size = 0.f, inv_interval_size = 0.f, integral = 0.f, normalization = 0.f; uint32_t valid_x = 0, valid_y = 0; };
+void phase_table(const float *values, size_t n, PhaseTable &out);
+// Every index, count and value of the description's phase table and of the media's indices into it (lrt_scene_from_desc and the upload
+// share it); `unsupported: ...` for a blend as a blend's child.
+void validate_phases(const lrt_scene_desc &d);
+// does medium m scatter by an entry of the table?  (n_phases = 0: the indices are not read)
+inline bool medium_has_phase_entry(const lrt_scene_desc &d, uint32_t m) { return d.n_phases > 0 && d.media[m].phase_index >= 0; }
+// DScene::phases and phase_pool: an entry per description entry, the tabulated ones with their interval records and cdf
+void prepare_phases(const lrt_scene_desc &d, std::vector<DPhase> &phases, std::vector<float> &pool);
 
 // spp: samples of ONE pass; spp_total = n_passes * spp (integrator.cpp:176-184,275-293)
 struct ResolvedOpts { int integrator, max_depth, rr_depth, hide_emitters; uint32_t spp, seed, tile_rank, tile_count; uint32_t spp_total = 0, n_passes = 1, pass = 0; };
