@@ -67,7 +67,9 @@ enum { LRT_PHASE_ISOTROPIC = 0, LRT_PHASE_HG = 1,
        LRT_PHASE_RAYLEIGH = 3,        /* src/phase/rayleigh.cpp                             */
        LRT_PHASE_BLEND = 4            /* src/phase/blendphase.cpp: one level, a constant weight */ };
 enum { LRT_EMITTER_AREA = 0, LRT_EMITTER_ENVMAP = 1, LRT_EMITTER_CONSTANT = 2,
-       LRT_EMITTER_POINT = 3          /* [v106] src/emitters/point.cpp: `intensity` in radiance[3], position = to_world * 0 */ };
+       LRT_EMITTER_POINT = 3,         /* [v106] src/emitters/point.cpp: `intensity` in radiance[3], position = to_world * 0 */
+       LRT_EMITTER_SPOT = 4,          /* [v117] src/emitters/spot.cpp: `intensity` in radiance[3], at to_world * 0, looking along to_world * (0, 0, 1) */
+       LRT_EMITTER_DIRECTIONAL = 5    /* [v117] src/emitters/directional.cpp: `irradiance` in radiance[3], light travels along to_world * (0, 0, 1) */ };
 enum { LRT_SHAPE_MESH = 0, LRT_SHAPE_RECTANGLE = 1,
        LRT_SHAPE_SPHERE = 2           /* [v106] src/shapes/sphere.cpp: n_faces = 0, analytic intersection (see lrt_shape_desc) */ };
 /* The CPU oracle under oracle/ renders LRT_SHAPE_SPHERE and LRT_EMITTER_POINT too; it refuses LRT_EMITTER_AREA on an
@@ -175,17 +177,32 @@ typedef struct {
 
 typedef struct {
     int32_t type;             /* LRT_EMITTER_*                                     */
-    float   radiance[3];      /* area / constant; point [v106]: intensity          */
+    float   radiance[3];      /* area / constant; point [v106] and spot [v117]: intensity; directional [v117]: irradiance */
     int32_t shape;            /* area: owning shape, a rectangle or [v107] any LRT_SHAPE_MESH */
     float   scale;            /* envmap                                            */
-    float   to_world[16];     /* envmap, row-major; point [v106]: position in column 3 */
+    float   to_world[16];     /* envmap, row-major; point [v106]: position in column 3; spot / directional [v117]: the emitter's pose */
     int32_t width, height;    /* envmap: ORIGINAL bitmap resolution (w, h)         */
     const float *data;        /* envmap: h * w * 3 linear RGB floats               */
+    /* [v117] read only when type is LRT_EMITTER_SPOT (a zero-filled description from before v117 means what it meant) */
+    float   cutoff_angle;     /* degrees; 0 < beam_width <= cutoff_angle <= 180, and cutoff_angle < 90 with a texture (uv_factor = tan(cutoff)) */
+    float   beam_width;       /* degrees; the plugin's default is 3/4 of the cutoff (the XML loader fills it in) */
+    int32_t texture;          /* projection texture: index into textures[] of a checkerboard, -1: none */
+    int32_t pad_spot;
 } lrt_emitter_desc;
 /* [v107] An area emitter on an LRT_SHAPE_MESH shape samples a face by area (src/render/mesh.cpp:449-482,861-935; the table
    is built from positions[] and faces[] of its face range).  A mesh without faces, or one whose total area is zero, is
    rejected (LRT_ERR_INVALID).  prbvolpath rejects scenes with such an emitter (LRT_ERR_UNSUPPORTED), and the CPU oracle
    under oracle/ must not be handed one (it samples area emitters as rectangles).                                  */
+/* [v117] LRT_EMITTER_SPOT and LRT_EMITTER_DIRECTIONAL are delta emitters (spot.cpp:176-215, directional.cpp:148-176): no ray hits
+   them, they are sampled through Scene::sample_emitter_direction alone and share the uniform emitter selection with every other
+   emitter.  Both keep their value in `radiance` and their pose in `to_world`, which must be finite and invertible.  A directional
+   light is infinite but no environment emitter: it does not count towards "only one environment emitter".  A spot's texture must be
+   a checkerboard (an RGB texture is LRT_ERR_INVALID, as the plugin refuses a texture that does not vary; a bitmap is
+   LRT_ERR_UNSUPPORTED).  Out-of-range angles are LRT_ERR_INVALID (the plugin only asserts cutoff >= beam in debug builds).  The
+   forward integrators render such scenes on the EXT kernel instances; prbvolpath refuses them (LRT_ERR_UNSUPPORTED), lrt_param_set
+   has no key for an emitter, and the CPU oracle under oracle/ must not be handed such a scene (it has no branch for either type and
+   would treat them as a constant sky).  Not built: sample_ray / sample_position (no integrator here traces from lights), a bitmap
+   projection texture, the `projector` emitter, any adjoint. */
 
 /* samplers: src/samplers/independent.cpp (PCG32 stream per lane), src/samplers/ldsampler.cpp ((0,2)-sequence,
    TEA-shuffled permutation + per-pixel scramble) */
@@ -294,7 +311,7 @@ typedef struct {
 typedef struct lrt_scene lrt_scene;
 
 LRT_API const char *lrt_last_error(void);
-LRT_API int         lrt_version(void);   /* 116: tabulated, Rayleigh and blended phase functions (lrt_phase_desc, lrt_scene_desc.phases, lrt_medium_desc.phase_index), lrt_phase_probe, lrt_math_eval fn 11; 115: lrt_render_stats.n_proven appended (lrt_render_stats_get writes 8 bytes more: rebuild hosts against this header); 114: the roughdielectric BSDF (LRT_BSDF_ROUGHDIELECTRIC, the fields after `scale` of lrt_bsdf_desc), lrt_math_eval fn 9 / 10; 113: lrt_bsdf_probe; 112:lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
+LRT_API int         lrt_version(void);   /* 117: spot and directional emitters (LRT_EMITTER_SPOT / _DIRECTIONAL, lrt_emitter_desc grows by cutoff_angle, beam_width, texture: rebuild hosts against this header); 116: tabulated, Rayleigh and blended phase functions (lrt_phase_desc, lrt_scene_desc.phases, lrt_medium_desc.phase_index), lrt_phase_probe, lrt_math_eval fn 11; 115: lrt_render_stats.n_proven appended (lrt_render_stats_get writes 8 bytes more: rebuild hosts against this header); 114: the roughdielectric BSDF (LRT_BSDF_ROUGHDIELECTRIC, the fields after `scale` of lrt_bsdf_desc), lrt_math_eval fn 9 / 10; 113: lrt_bsdf_probe; 112:lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
 
 LRT_API lrt_status lrt_scene_load_xml(const char *path, const char *const *defines,
                                       int n_defines, lrt_scene **out);

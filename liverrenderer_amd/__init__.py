@@ -124,7 +124,7 @@ _TAGS = {
     "gridvolume": "volume",
     "isotropic": "phase", "hg": "phase", "tabphase": "phase", "rayleigh": "phase", "blendphase": "phase",
     "obj": "shape", "rectangle": "shape", "cube": "shape",
-    "area": "emitter", "envmap": "emitter", "constant": "emitter",
+    "area": "emitter", "envmap": "emitter", "constant": "emitter", "spot": "emitter", "directional": "emitter",
 }
 
 
@@ -180,6 +180,8 @@ def _dict_to_xml(name, d, out, indent, top_ids, parent=None):
             out.append(f'{sub}<string name="{_esc(k)}" value="{_esc(v)}"/>')
         elif typ == "tabphase" and k == "values" and isinstance(v, (list, tuple, np.ndarray)):      # the plugin reads a string (tabphase.cpp:45-57)
             out.append(f'{sub}<string name="values" value="{", ".join(_fmt(x) for x in np.asarray(v).reshape(-1))}"/>')
+        elif typ == "directional" and k == "direction" and isinstance(v, (list, tuple, np.ndarray)):    # a vector, not a colour (directional.cpp:75)
+            out.append(f'{sub}<vector name="direction" value="{", ".join(_fmt(x) for x in np.asarray(v).reshape(-1))}"/>')
         elif isinstance(v, (list, tuple, np.ndarray)):
             out.append(f'{sub}<rgb name="{_esc(k)}" value="{", ".join(_fmt(x) for x in v)}"/>')
         else:

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("LRT_LIBRARY") or os.path.join(_HERE, "libliverrt.so")
 OK, INVALID, UNSUPPORTED = 0, 1, 4      # lrt_status values the wrappers and tests name
 INTEGRATOR = {"path": 0, "volpath": 1, "prbvolpath": 2, "biovolpath": 3, "biovolpath06": 4, "volpathmis": 5}
 MEDIUM = {"homogeneous": 0, "liver": 1, "parenchyma": 2, "glissonCapsule": 3, "heterogeneous": 4}
-EMITTER = {"area": 0, "envmap": 1, "constant": 2}
+EMITTER = {"area": 0, "envmap": 1, "constant": 2, "point": 3, "spot": 4, "directional": 5}
 PROBE_FLOATS = 20      # include/liverrt.h LRT_PROBE_FLOATS (lrt_emitter_probe)
 PHASE_PROBE_FLOATS = 7 # include/liverrt.h LRT_PHASE_PROBE_FLOATS (lrt_phase_probe)
 BSDF_PROBE_FLOATS = 30 # include/liverrt.h LRT_BSDF_PROBE_FLOATS (lrt_bsdf_probe)
@@ -60,7 +60,9 @@ class PhaseDesc(C.Structure):                # [v116] lrt_phase_desc: one entry 
 
 class EmitterDesc(C.Structure):
     _fields_ = [("type", C.c_int32), ("radiance", C.c_float * 3), ("shape", C.c_int32), ("scale", C.c_float),
-                ("to_world", C.c_float * 16), ("width", C.c_int32), ("height", C.c_int32), ("data", C.POINTER(C.c_float))]
+                ("to_world", C.c_float * 16), ("width", C.c_int32), ("height", C.c_int32), ("data", C.POINTER(C.c_float)),
+                # [v117] read only for a spot (type 4): degrees, degrees, index into SceneDesc.textures of a checkerboard (-1: none)
+                ("cutoff_angle", C.c_float), ("beam_width", C.c_float), ("texture", C.c_int32), ("pad_spot", C.c_int32)]
 
 
 class SensorDesc(C.Structure):

@@ -314,6 +314,7 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
     sc.emitters = up(P.emitters);
     sc.mesh_emitters = up(P.mesh_emitters);
     sc.mesh_emitter_tab = up(P.mesh_emitter_tab);
+    sc.delta_emitters = P.delta_emitters.empty() ? nullptr : up(P.delta_emitters);
     sc.cone_tab = P.cone_tab.empty() ? nullptr : (const uint2 *) up(P.cone_tab);      // (sc.cone_enabled: set by the preparation with the table)
     sc.phases = P.phases.empty() ? nullptr : up(P.phases);
     sc.phase_pool = P.phase_pool.empty() ? nullptr : up(P.phase_pool);
@@ -487,7 +488,7 @@ static void check_integrator_media(DeviceScene *D, int integrator) {
     if ((integrator == LRT_INTEGRATOR_BIOVOLPATH || integrator == LRT_INTEGRATOR_BIOVOLPATH06) && D->has_non_bio)
         throw std::runtime_error("NotImplementedError: sample_interaction (the bio integrators need liver / parenchyma / glissonCapsule media)");
     if (integrator == LRT_INTEGRATOR_PRBVOLPATH && D->ext)
-        throw std::runtime_error("unsupported: prbvolpath on a scene with sphere shapes, point emitters, area emitters on meshes, a roughdielectric BSDF or a tabulated / Rayleigh / blended phase function (its adjoint is built for triangles, rectangle / infinite emitters, the diffuse / dielectric / null BSDFs and the isotropic / hg phase functions)");
+        throw std::runtime_error("unsupported: prbvolpath on a scene with sphere shapes, point / spot / directional emitters, area emitters on meshes, a roughdielectric BSDF or a tabulated / Rayleigh / blended phase function (its adjoint is built for triangles, rectangle / infinite emitters, the diffuse / dielectric / null BSDFs and the isotropic / hg phase functions)");
     if (integrator == LRT_INTEGRATOR_VOLPATHMIS) D->need_mis = true;          // its wider path record is allocated on first use
 }
 

@@ -108,6 +108,21 @@ struct DMeshEmitter {
     int32_t mesh, pad[3];
 };
 
+// spot and directional emitters (src/emitters/spot.cpp, directional.cpp): one entry per emitter (DScene::delta_emitters, indexed like
+// DScene::emitters; all zero for every other emitter).  DEmitter keeps its 88 bytes: type and radiance (intensity / irradiance) stay there.
+// spot: pos = to_world's translation, to_local = the linear part of to_world^-1, the constructor's derived floats (spot.cpp:104-112).
+// directional: dir = to_world * (0, 0, 1), and the scene's bounding sphere as set_scene takes it (directional.cpp:98-108).
+struct DDeltaEmitter {
+    float pos[3]; float cos_cutoff;
+    float to_local[9];
+    float cos_beam, cutoff, inv_transition, uv_factor;
+    int32_t texture;                     // spot: projection texture (a checkerboard), -1: none
+    float dir[3];
+    float bsphere_c[3], bsphere_r;
+    float pad[3];
+};
+static_assert(sizeof(DDeltaEmitter) == 112, "DDeltaEmitter stride");
+
 #define LRT_MAX_HIER_LEVELS 16
 
 struct DCamera {
@@ -180,6 +195,7 @@ struct DScene {
     int32_t cone_enabled, pad_cone;      // the closed-records volpath kernels only read the table
     const DPhase *phases;                // tabulated / Rayleigh / blended phase functions and a blend's children (DMedium::phase_ext; the EXT instances only read them)
     const float *phase_pool;             // every tabulated entry's interval records and cdf
+    const DDeltaEmitter *delta_emitters; // n_emitters entries: spot and directional emitters (the EXT instances only read them); null: the scene has neither
 };
 
 // Direction bins of DScene::cone_tab: bin k holds the directions whose cosine to the side's geometric normal is at least LRT_CONE_COSk

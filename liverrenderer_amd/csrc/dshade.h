@@ -1149,7 +1149,37 @@ DEV V3 sample_emitter_direction(SceneRef sc, V3 ref_p, float sx, float sy, DirSa
         ds->dist = __builtin_sqrtf(dist2);
         ds->d = ds->d * inv_dist;
         spec = V3(E.radiance[0], E.radiance[1], E.radiance[2]) * sqr(inv_dist);
-    } else if (E.type == LRT_EMITTER_ENVMAP) {          // src/emitters/envmap.cpp:415-459
+    } else if (EXT && E.type == LRT_EMITTER_SPOT) {    // src/emitters/spot.cpp:176-210: a delta position, pdf 1, n = 0
+        const DDeltaEmitter S = tab(sc.delta_emitters, index);      // (one emitter: wave-uniform, scalar loads; several: per lane)
+        ds->p = V3(S.pos[0], S.pos[1], S.pos[2]);
+        ds->pdf = 1.f; ds->delta = true;
+        ds->d = ds->p - ref_p;
+        ds->dist = norm(ds->d);
+        const float inv_dist = rcp(ds->dist);                        // dr::rcp: dmath.h rcp, a correctly rounded 1 / x
+        ds->d = ds->d * inv_dist;
+        const V3 local_d = xform_vec9(S.to_local, -ds->d);
+        // falloff_curve (spot.cpp:142-150) on the normalised local direction; only the lanes of the transition ring pay the acos (dr::acos: m_acos)
+        const float cos_theta = normalize(local_d).z;
+        float falloff = 0.f;
+        if (cos_theta > S.cos_cutoff) falloff = cos_theta >= S.cos_beam ? 1.f : (S.cutoff - m_acos(cos_theta)) * S.inv_transition;
+        V3 radiance(0.f);
+        if (falloff > 0.f) {                                         // (`active &= falloff > 0`: the dark lanes skip the texture)
+            radiance = V3(E.radiance[0], E.radiance[1], E.radiance[2]);
+            if (S.texture >= 0) {                                    // direction_to_uv (spot.cpp:129-134) on local_d as it is, not normalised
+                SI tsi; const float den = local_d.z * S.uv_factor;
+                tsi.uv.x = .5f + .5f * local_d.x / den; tsi.uv.y = .5f + .5f * local_d.y / den;
+                radiance = radiance * tex_eval(sc, S.texture, tsi);
+            }
+        }
+        spec = radiance * (falloff * sqr(inv_dist));
+    } else if (EXT && E.type == LRT_EMITTER_DIRECTIONAL) {   // src/emitters/directional.cpp:148-176: a delta direction, pdf 1, n = d
+        const DDeltaEmitter S = tab(sc.delta_emitters, index);
+        const V3 d(S.dir[0], S.dir[1], S.dir[2]), c(S.bsphere_c[0], S.bsphere_c[1], S.bsphere_c[2]);
+        const float radius = fmax_(S.bsphere_r, norm(ref_p - c)), dist = 2.f * radius;
+        ds->p = ref_p - d * dist; ds->n = d; ds->d = -d; ds->dist = dist;
+        ds->pdf = 1.f; ds->delta = true;
+        spec = V3(E.radiance[0], E.radiance[1], E.radiance[2]);
+    } else if (E.type == LRT_EMITTER_ENVMAP) {         // src/emitters/envmap.cpp:415-459
         EnvRef EV = sc.env;
         float u, v, pdf; hier_sample(sc, sx, sy, &u, &v, &pdf);
         u += .5f / (float) (EV.w - 1u);

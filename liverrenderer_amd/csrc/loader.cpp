@@ -9,12 +9,14 @@
 // bio media carry both the homogeneous parameters that path / volpath /
 // prbvolpath see through the 4-argument sample_interaction() and the element
 // coefficients of the 5-argument one, docs/BIO_TRANSPORT_SPEC.md); phase
-// {isotropic, hg, tabphase, rayleigh, blendphase}; shape {obj, rectangle, cube, sphere}; emitter {area, envmap, constant, point}.
+// {isotropic, hg, tabphase, rayleigh, blendphase}; shape {obj, rectangle, cube, sphere}; emitter {area, envmap, constant, point, spot, directional}.
 // Plugin `type` names match without regard to case (plugin_type): the reference finds plugins by file name
 // (src/core/plugin.cpp:96-139), and the fork's SphereLiverPoint scenes, written on a case-insensitive file system, say
 // "Dielectric".  A medium child of a shape named neither "interior" nor "exterior" is ignored, as src/render/shape.cpp:40-49
 // ignores it.  A sphere is one shape without faces (lrt_shape_desc); the point emitter keeps its position in to_world.
 // An area emitter may be the child of a rectangle or of any triangle mesh (obj, cube); not of a sphere.
+// A spot keeps its pose in to_world and its angles in degrees (beam_width filled in with the plugin's default); its projection texture may be a
+// checkerboard.  A directional light's `direction` becomes the to_world the plugin builds from it.
 #include "host_scene.h"
 #include "scene_prep.h"
 #include "xml.h"
@@ -703,6 +705,51 @@ struct Loader {
             S.emitters.push_back(E); S.emdata.push_back(std::move(data));
             return;
         }
+        else if (o->type == "spot") {           // src/emitters/spot.cpp:90-117; a medium child is ignored, as for the point emitter
+            E.type = LRT_EMITTER_SPOT; E.texture = -1;
+            if (child(*o, "texture", "intensity")) fail("The parameter 'intensity' cannot be spatially varying (e.g. bitmap type)!");
+            get_rgb(*o, "intensity", 1.f, E.radiance);
+            if (has(*o, "texture")) fail("The parameter 'texture' must be spatially varying (e.g. bitmap type)!");      // a colour: Properties makes a uniform texture of it
+            if (ObjP t = child(*o, "texture", "texture")) {
+                if (t->type == "bitmap") fail("unsupported: a bitmap texture as the spot emitter's 'texture' (bitmaps are held as one luminance float per texel, for bump maps only; a checkerboard is supported)");
+                E.texture = make_texture(t);
+                if (S.textures[E.texture].type != LRT_TEX_CHECKERBOARD) fail("The parameter 'texture' must be spatially varying (e.g. bitmap type)!");
+            }
+            E.cutoff_angle = get_float(*o, "cutoff_angle", 20.0f);
+            E.beam_width = get_float(*o, "beam_width", E.cutoff_angle * 3.0f / 4.0f);
+            to_float(get_xform(*o, "to_world"), E.to_world);
+            S.emitters.push_back(E); S.emdata.push_back(std::move(data));
+            S.fix_pointers();                   // (the check below reads the description)
+            validate_delta_emitter(S.desc, (uint32_t) S.emitters.size() - 1);
+            return;
+        }
+        else if (o->type == "directional") {    // src/emitters/directional.cpp:65-90; not an environment emitter
+            E.type = LRT_EMITTER_DIRECTIONAL; E.texture = -1;
+            Mat4 T = get_xform(*o, "to_world");
+            to_float(T, E.to_world);
+            if (has(*o, "direction")) {
+                if (has(*o, "to_world")) fail("Only one of the parameters 'direction' and 'to_world' can be specified at the same time!'");
+                double v[3]; vec3_attr(*o->props["direction"].node, 0.0, v);
+                // normalize, coordinate_system (include/mitsuba/core/vector.h:118-138) and look_at(0, direction, up) (transform.h:177-205), in float32
+                auto nrm = [](float *a) { const float s = 1.f / sqrtf(fmaf(a[2], a[2], fmaf(a[1], a[1], a[0] * a[0]))); a[0] *= s; a[1] *= s; a[2] *= s; };
+                auto crs = [](const float *a, const float *b, float *r) { r[0] = fmaf(a[1], b[2], -(a[2] * b[1])); r[1] = fmaf(a[2], b[0], -(a[0] * b[2])); r[2] = fmaf(a[0], b[1], -(a[1] * b[0])); };
+                float n[3] = { (float) v[0], (float) v[1], (float) v[2] }; nrm(n);
+                const float sign = copysignf(1.f, n[2]), a = -(1.f / (sign + n[2])), b = n[0] * n[1] * a;
+                const float up[3] = { copysignf(1.f, n[2]) * (n[0] * n[0] * a) + 1.f, copysignf(1.f, n[2]) * b, -copysignf(1.f, n[2]) * n[0] };
+                float dir[3] = { n[0], n[1], n[2] }; nrm(dir);
+                float left[3]; crs(up, dir, left); nrm(left);
+                float nup[3]; crs(dir, left, nup);
+                for (int k = 0; k < 16; ++k) E.to_world[k] = 0.f;
+                for (int i = 0; i < 3; ++i) { E.to_world[4 * i] = left[i]; E.to_world[4 * i + 1] = nup[i]; E.to_world[4 * i + 2] = dir[i]; }
+                E.to_world[15] = 1.f;
+            }
+            if (child(*o, "texture", "irradiance")) fail("Expected a non-spatially varying irradiance spectra!");
+            get_rgb(*o, "irradiance", 1.f, E.radiance);
+            S.emitters.push_back(E); S.emdata.push_back(std::move(data));
+            S.fix_pointers();
+            validate_delta_emitter(S.desc, (uint32_t) S.emitters.size() - 1);
+            return;
+        }
         else if (o->type == "envmap") {         // src/emitters/envmap.cpp:109-236
             E.type = LRT_EMITTER_ENVMAP; E.scale = get_float(*o, "scale", 1.f);
             if (get_bool(*o, "mis_compensation", false)) fail("envmap: mis_compensation is not supported");
@@ -942,6 +989,8 @@ struct Loader {
         bool ext = false;                       // spheres / point / mesh emitters: prbvolpath's adjoint is built for triangles and rectangle / infinite emitters
         for (auto &sh : S.shapes) ext = ext || sh.kind == LRT_SHAPE_SPHERE;
         for (auto &e : S.emitters) ext = ext || e.type == LRT_EMITTER_POINT || (e.type == LRT_EMITTER_AREA && S.shapes[e.shape].kind == LRT_SHAPE_MESH);
+        bool delta_em = false;                  // spot / directional emitters: the EXT instances as well, and no adjoint either
+        for (auto &e : S.emitters) delta_em = delta_em || e.type == LRT_EMITTER_SPOT || e.type == LRT_EMITTER_DIRECTIONAL;
         bool phase_ext = false;                 // a tabulated / Rayleigh / blended phase function on a medium that a shape or the sensor references (scene_prep.cpp)
         auto ext_medium = [&](int m) { return m >= 0 && S.media[m].phase_index >= 0; };
         for (auto &sh : S.shapes) phase_ext = phase_ext || ext_medium(sh.interior_medium) || ext_medium(sh.exterior_medium);
@@ -954,6 +1003,7 @@ struct Loader {
         bool prb = S.desc.integrator.type == LRT_INTEGRATOR_PRBVOLPATH;
         for (int k = 0; S.has_aov && k < S.aov.n_integrators; ++k) prb = prb || S.aov.integrators[k].type == LRT_INTEGRATOR_PRBVOLPATH;
         if (ext && prb) fail("unsupported: prbvolpath on a scene with sphere shapes, point emitters or area emitters on meshes");
+        if (delta_em && prb) fail("unsupported: prbvolpath on a scene with a spot or directional emitter (no adjoint is built for them)");
         if (rough && prb) fail("unsupported: prbvolpath on a scene with a roughdielectric BSDF (no adjoint is built for it)");
         if (phase_ext && prb) fail("unsupported: prbvolpath on a scene with a tabulated / Rayleigh / blended phase function (no adjoint is built for them)");
         S.fix_pointers();

@@ -78,6 +78,27 @@ static void inverse3(const float *m16, float *out9) {    // double-precision inv
     out9[6] = (float) ((m[1][0] * m[2][1] - m[1][1] * m[2][0]) * id); out9[7] = (float) ((m[0][1] * m[2][0] - m[0][0] * m[2][1]) * id); out9[8] = (float) ((m[0][0] * m[1][1] - m[0][1] * m[1][0]) * id);
 }
 
+// A spot or directional emitter of a description (scene_prep.h).  The plugin only asserts cutoff >= beam in debug builds (spot.cpp:111);
+// here every value that would put an infinity or a NaN into the device table is refused by name.
+void validate_delta_emitter(const lrt_scene_desc &d, uint32_t i) {
+    const lrt_emitter_desc &E = d.emitters[i];
+    const char *who = E.type == LRT_EMITTER_SPOT ? "spot emitter" : "directional emitter";
+    double m[3][3]; bool finite = true;
+    for (int k = 0; k < 16; ++k) finite = finite && std::isfinite(E.to_world[k]);
+    for (int a = 0; a < 3; ++a) { for (int b = 0; b < 3; ++b) m[a][b] = E.to_world[4 * a + b]; finite = finite && std::isfinite(E.radiance[a]); }
+    const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) + m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+    if (!finite || !(std::fabs(det) > 0.0) || !std::isfinite(1.0 / det)) throw std::runtime_error(std::string(who) + ": to_world must be finite and invertible, the value finite");
+    if (E.type != LRT_EMITTER_SPOT) return;
+    if (!(E.beam_width > 0.f) || !(E.beam_width <= E.cutoff_angle) || !(E.cutoff_angle <= 180.f))
+        throw std::runtime_error("spot emitter: 0 < beam_width <= cutoff_angle <= 180 degrees is required (beam_width " + std::to_string(E.beam_width) + ", cutoff_angle " + std::to_string(E.cutoff_angle) + ")");
+    if (E.texture < -1 || E.texture >= (int32_t) d.n_textures) throw std::runtime_error("spot emitter references an invalid texture");
+    if (E.texture < 0) return;
+    if (d.textures[E.texture].type == LRT_TEX_BITMAP)
+        throw std::runtime_error("unsupported: a bitmap texture as the spot emitter's 'texture' (bitmaps are held as one luminance float per texel, for bump maps only; a checkerboard is supported)");
+    if (d.textures[E.texture].type != LRT_TEX_CHECKERBOARD) throw std::runtime_error("The parameter 'texture' must be spatially varying (e.g. bitmap type)!");    // spot.cpp:98-100
+    if (!(E.cutoff_angle < 90.f)) throw std::runtime_error("spot emitter: cutoff_angle must be below 90 degrees when a texture is given (uv_factor = tan(cutoff_angle) must be positive and finite)");
+}
+
 static uint32_t log2i_ceil(uint32_t v) { uint32_t r = 0; while ((1u << r) < v) ++r; return r; }
 
 // include/mitsuba/core/distr_2d.h:403-510 (normalised, single slice); levels are
@@ -388,7 +409,7 @@ void prepare_geometry(const lrt_scene_desc &d, const PrepOptions &opt, PreparedS
     sc.n_spheres = (uint32_t) spheres.size();
     for (uint32_t i = 0; i < d.n_emitters; ++i) {
         const lrt_emitter_desc &e = d.emitters[i];
-        if (e.type == LRT_EMITTER_POINT || (e.type == LRT_EMITTER_AREA && e.shape >= 0 && (uint32_t) e.shape < d.n_shapes && d.shapes[e.shape].kind == LRT_SHAPE_MESH)) P.ext = true;
+        if (e.type == LRT_EMITTER_POINT || e.type == LRT_EMITTER_SPOT || e.type == LRT_EMITTER_DIRECTIONAL || (e.type == LRT_EMITTER_AREA && e.shape >= 0 && (uint32_t) e.shape < d.n_shapes && d.shapes[e.shape].kind == LRT_SHAPE_MESH)) P.ext = true;
     }
     if (!spheres.empty()) P.ext = true;
     // A roughdielectric on a shape, nested or not, runs on the EXT instances (an unreferenced one changes nothing: the scene keeps its kernels)
@@ -557,6 +578,23 @@ void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedSc
             for (int a = 0; a < 3; ++a) o.n[a] = sd.flip_normals ? -d.normals[3 * v0 + a] : d.normals[3 * v0 + a];
         } else if (S.type == LRT_EMITTER_POINT) {             // src/emitters/point.cpp: position and intensity (radiance[])
             memcpy(o.to_world, S.to_world, sizeof(float) * 12);
+        } else if (S.type == LRT_EMITTER_SPOT || S.type == LRT_EMITTER_DIRECTIONAL) {
+            if (P.delta_emitters.empty()) P.delta_emitters.assign(d.n_emitters, DDeltaEmitter{});
+            validate_delta_emitter(d, i);
+            DDeltaEmitter &D = P.delta_emitters[i]; D.texture = -1;
+            memcpy(o.to_world, S.to_world, sizeof(float) * 12);
+            if (S.type == LRT_EMITTER_SPOT) {                   // src/emitters/spot.cpp:104-112, in float32 as the plugin's ScalarFloat members
+                const float deg = 3.14159265358979323846f / 180.f;       // dr::deg_to_rad: value * (Pi / 180)
+                const float cutoff = S.cutoff_angle * deg, beam = S.beam_width * deg;
+                D.cutoff = cutoff; D.inv_transition = 1.0f / (cutoff - beam);
+                D.cos_cutoff = cosf(cutoff); D.cos_beam = cosf(beam); D.uv_factor = tanf(cutoff);
+                for (int a = 0; a < 3; ++a) D.pos[a] = S.to_world[4 * a + 3];
+                inverse3(S.to_world, D.to_local);
+                D.texture = S.texture;
+            } else {                                            // src/emitters/directional.cpp:98-108,153: to_world * (0, 0, 1) and set_scene's sphere
+                for (int a = 0; a < 3; ++a) { D.dir[a] = S.to_world[4 * a + 2]; D.bsphere_c[a] = E.bsphere_c[a]; }
+                D.bsphere_r = E.bsphere_r;
+            }
         } else {
             E.type = S.type; E.emitter = (int) i; E.scale = S.scale; for (int k = 0; k < 3; ++k) E.radiance[k] = S.radiance[k];
             if (S.type == LRT_EMITTER_ENVMAP) {             // src/emitters/envmap.cpp:139-236

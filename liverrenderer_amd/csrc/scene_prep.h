@@ -35,6 +35,7 @@ struct PreparedScene {
     std::vector<DBsdf> bsdfs;
     std::vector<DEmitter> emitters;
     std::vector<DMeshEmitter> mesh_emitters; std::vector<float> mesh_emitter_tab;
+    std::vector<DDeltaEmitter> delta_emitters;         // DScene::delta_emitters, one entry per emitter; empty: the scene has no spot or directional emitter
     std::vector<float> env_data, env_hier;             // (w+1) x h RGBx texels, sampling hierarchy
     // The scalar part of the scene record: counts, root leaf, one_shape, has_null_bsdf, nee_fast_reject, env (with the bounding sphere),
     // cam, film and the distance field's geometry (grid.enabled set, grid.d null: the upload side builds the field).  Every pointer is null.
@@ -84,6 +85,11 @@ void validate_phases(const lrt_scene_desc &d);
 inline bool medium_has_phase_entry(const lrt_scene_desc &d, uint32_t m) { return d.n_phases > 0 && d.media[m].phase_index >= 0; }
 // DScene::phases and phase_pool: an entry per description entry, the tabulated ones with their interval records and cdf
 void prepare_phases(const lrt_scene_desc &d, std::vector<DPhase> &phases, std::vector<float> &pool);
+
+// Emitter i of the description, an LRT_EMITTER_SPOT or LRT_EMITTER_DIRECTIONAL: a finite, invertible to_world; a spot's angles
+// (0 < beam_width <= cutoff_angle <= 180, cutoff_angle < 90 with a texture) and its texture's index and type.  Throws the text
+// (lrt_scene_from_desc and the preparation share it); `unsupported: ...` for a bitmap texture, the plugin's own text for a uniform one.
+void validate_delta_emitter(const lrt_scene_desc &d, uint32_t i);
 
 // spp: samples of ONE pass; spp_total = n_passes * spp (integrator.cpp:176-184,275-293)
 struct ResolvedOpts { int integrator, max_depth, rr_depth, hide_emitters; uint32_t spp, seed, tile_rank, tile_count; uint32_t spp_total = 0, n_passes = 1, pass = 0; };
