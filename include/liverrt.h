@@ -311,7 +311,7 @@ typedef struct {
 typedef struct lrt_scene lrt_scene;
 
 LRT_API const char *lrt_last_error(void);
-LRT_API int         lrt_version(void);   /* 117: spot and directional emitters (LRT_EMITTER_SPOT / _DIRECTIONAL, lrt_emitter_desc grows by cutoff_angle, beam_width, texture: rebuild hosts against this header); 116: tabulated, Rayleigh and blended phase functions (lrt_phase_desc, lrt_scene_desc.phases, lrt_medium_desc.phase_index), lrt_phase_probe, lrt_math_eval fn 11; 115: lrt_render_stats.n_proven appended (lrt_render_stats_get writes 8 bytes more: rebuild hosts against this header); 114: the roughdielectric BSDF (LRT_BSDF_ROUGHDIELECTRIC, the fields after `scale` of lrt_bsdf_desc), lrt_math_eval fn 9 / 10; 113: lrt_bsdf_probe; 112:lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
+LRT_API int         lrt_version(void);   /* 118: lrt_medium_probe; the loader refuses a singular volume to_world and an empty use_grid_bbox header box; 117: spot and directional emitters (LRT_EMITTER_SPOT / _DIRECTIONAL, lrt_emitter_desc grows by cutoff_angle, beam_width, texture: rebuild hosts against this header); 116: tabulated, Rayleigh and blended phase functions (lrt_phase_desc, lrt_scene_desc.phases, lrt_medium_desc.phase_index), lrt_phase_probe, lrt_math_eval fn 11; 115: lrt_render_stats.n_proven appended (lrt_render_stats_get writes 8 bytes more: rebuild hosts against this header); 114: the roughdielectric BSDF (LRT_BSDF_ROUGHDIELECTRIC, the fields after `scale` of lrt_bsdf_desc), lrt_math_eval fn 9 / 10; 113: lrt_bsdf_probe; 112:lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
 
 LRT_API lrt_status lrt_scene_load_xml(const char *path, const char *const *defines,
                                       int n_defines, lrt_scene **out);
@@ -421,6 +421,19 @@ LRT_API lrt_status lrt_bsdf_probe(lrt_scene *scene, const float *o, const float 
 #define LRT_PHASE_PROBE_FLOATS 7
 LRT_API lrt_status lrt_phase_probe(lrt_scene *scene, int medium, const float *wi, const float *sample, const float *wo_query,
                                    uint32_t n, float *out, int device);
+
+/* Test hook [v118]: free-flight sampling in medium `medium` as the volume integrators call it (csrc/dshade.h het_sample_interaction for a
+ * heterogeneous medium, medium_sample_interaction otherwise), one call per lane: Medium::sample_interaction(ray(o[3 i ..], d[3 i ..],
+ * maxt[i]), sample[i], channel[i]) (src/render/medium.cpp:40-82); channel > 2 counts as 2.
+ * out: LRT_MEDIUM_PROBE_FLOATS floats per input:
+ *   [0] 1 if the interaction is valid else 0, [1] t (+inf when not valid), [2..4] p = o + sampled_t d (also when not valid), [5] mint,
+ *   [6..8] sigma_t, [9..11] sigma_s, [12..14] sigma_n, [15..17] combined extinction (the majorant);
+ *   a grid medium also: [18..20] to_local(p) in the grid's unit cube and [21] the raw grid lookup there (no `scale`); else 0.
+ * A lane whose maxt is NaN asks for the grid lookup alone: o[3 i ..] is then the local point, anywhere in space (clamp-to-edge outside the unit
+ * cube); [18..21] are written, [0..17] are 0. */
+#define LRT_MEDIUM_PROBE_FLOATS 22
+LRT_API lrt_status lrt_medium_probe(lrt_scene *scene, int medium, const float *o, const float *d, const float *maxt, const float *sample,
+                                    const uint32_t *channel, uint32_t n, float *out, int device);
 
 /* SoA ray queries (layout mirrors RayHit of src/render/scene_native.inl:135-142).
  * Miss: t = +inf, prim = 0xffffffff.  any_hit: only t (0 on hit, +inf on miss). */

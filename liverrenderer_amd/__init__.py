@@ -511,6 +511,23 @@ class Scene:
         _lib.check(self._lib.lrt_phase_probe(self._h, int(medium), *[x.ctypes.data_as(FP) for x in a], n, out.ctypes.data_as(FP), int(device)))
         return {"wo": out[:, 0:3], "weight": out[:, 3], "pdf": out[:, 4], "eval": out[:, 5], "eval_pdf": out[:, 6]}
 
+    def medium_probe(self, medium, o, d, maxt, sample, channel, device=0):
+        """lrt_medium_probe (test hook): free-flight sampling in medium `medium` (an index into desc.media) as the volume integrators call
+        it, per lane: Medium::sample_interaction(ray(o, d, maxt), sample, channel) (o, d: n x 3; maxt, sample, channel: n).  A lane with
+        maxt = NaN evaluates the grid at the local point o alone.  Returns a dict of arrays: valid (bool), t, p, mint, sigma_t, sigma_s,
+        sigma_n, combined (n x 3 each), local (n x 3), grid, and raw (n x LRT_MEDIUM_PROBE_FLOATS, every float as returned)."""
+        o, d = (np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (o, d))
+        maxt, sample = (np.ascontiguousarray(x, np.float32).reshape(-1) for x in (maxt, sample))
+        channel = np.ascontiguousarray(channel, np.uint32).reshape(-1)
+        n = o.shape[0]
+        if any(x.shape[0] != n for x in (d, maxt, sample, channel)):
+            raise ValueError("medium_probe: o, d, maxt, sample and channel must have the same number of rows")
+        out = np.zeros((n, _lib.MEDIUM_PROBE_FLOATS), np.float32)
+        FP = C.POINTER(C.c_float)
+        _lib.check(self._lib.lrt_medium_probe(self._h, int(medium), *[x.ctypes.data_as(FP) for x in (o, d, maxt, sample)],
+                                              channel.ctypes.data_as(C.POINTER(C.c_uint32)), n, out.ctypes.data_as(FP), int(device)))
+        return _lib.medium_probe_fields(out)
+
     def bsdf_probe(self, o, d, sample, wo_query, device=0):
         """lrt_bsdf_probe (test hook): per ray (o, d) (n x 3 each) the closest hit without a ray offset, its surface interaction, the hit
         shape's BSDF sampled with sample (n x 3: s1, s2.x, s2.y) as the integrators do, and its eval / pdf at the world direction

@@ -15,6 +15,7 @@ INTEGRATOR = {"path": 0, "volpath": 1, "prbvolpath": 2, "biovolpath": 3, "biovol
 MEDIUM = {"homogeneous": 0, "liver": 1, "parenchyma": 2, "glissonCapsule": 3, "heterogeneous": 4}
 EMITTER = {"area": 0, "envmap": 1, "constant": 2, "point": 3, "spot": 4, "directional": 5}
 PROBE_FLOATS = 20      # include/liverrt.h LRT_PROBE_FLOATS (lrt_emitter_probe)
+MEDIUM_PROBE_FLOATS = 22 # include/liverrt.h LRT_MEDIUM_PROBE_FLOATS (lrt_medium_probe)
 PHASE_PROBE_FLOATS = 7 # include/liverrt.h LRT_PHASE_PROBE_FLOATS (lrt_phase_probe)
 BSDF_PROBE_FLOATS = 30 # include/liverrt.h LRT_BSDF_PROBE_FLOATS (lrt_bsdf_probe)
 
@@ -221,6 +222,8 @@ def lib():
     L.lrt_bsdf_probe.restype = C.c_int
     L.lrt_phase_probe.argtypes = [C.c_void_p, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), C.c_uint32, P(C.c_float), C.c_int]
     L.lrt_phase_probe.restype = C.c_int
+    L.lrt_medium_probe.argtypes = [C.c_void_p, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_uint32), C.c_uint32, P(C.c_float), C.c_int]
+    L.lrt_medium_probe.restype = C.c_int
     L.lrt_param_set.argtypes = [C.c_void_p, C.c_char_p, P(C.c_float), C.c_int]
     L.lrt_param_get.argtypes = [C.c_void_p, C.c_char_p, P(C.c_float), C.c_int]
     L.lrt_image_read.argtypes = [C.c_char_p, P(C.c_int), P(C.c_int), P(C.c_int), P(P(C.c_float))]
@@ -259,7 +262,7 @@ def lib():
 
 EXPORTED_SYMBOLS = ["lrt_last_error", "lrt_version", "lrt_scene_load_xml", "lrt_scene_load_xml_string", "lrt_scene_from_desc",
                     "lrt_scene_desc_get", "lrt_scene_free", "lrt_render", "lrt_render_multi", "lrt_render_backward_multi", "lrt_math_eval", "lrt_render_stats_get", "lrt_film_develop",
-                    "lrt_render_samples", "lrt_render_backward", "lrt_render_backward_grid", "lrt_trace", "lrt_emitter_probe", "lrt_envmap_probe", "lrt_bsdf_probe", "lrt_phase_probe", "lrt_param_set", "lrt_param_get",
+                    "lrt_render_samples", "lrt_render_backward", "lrt_render_backward_grid", "lrt_trace", "lrt_emitter_probe", "lrt_envmap_probe", "lrt_bsdf_probe", "lrt_phase_probe", "lrt_medium_probe", "lrt_param_set", "lrt_param_get",
                     "lrt_image_read", "lrt_image_free", "lrt_image_write_exr", "lrt_image_write_png",
                     "lrt_vae_model_create", "lrt_vae_model_free", "lrt_vae_scatter",
                     "lrt_scene_aov_get", "lrt_aov_channel_name", "lrt_render_aov", "lrt_render_aov_samples", "lrt_image_write_exr_channels",
@@ -272,6 +275,12 @@ def bsdf_probe_fields(out):
     return {"shape": out[:, 0].astype("int32"), "t": out[:, 1], "p": out[:, 2:5], "n": out[:, 5:8], "sh_n": out[:, 8:11], "uv": out[:, 11:13],
             "wi": out[:, 13:16], "wo": out[:, 16:19], "wo_z": out[:, 19], "pdf": out[:, 20], "eta": out[:, 21], "type": out[:, 22].astype("int32"),
             "weight": out[:, 23:26], "eval": out[:, 26:29], "eval_pdf": out[:, 29], "raw": out}
+
+
+def medium_probe_fields(out):
+    """The record of lrt_medium_probe / orc_medium_probe (n x LRT_MEDIUM_PROBE_FLOATS) as a dict of arrays"""
+    return {"valid": out[:, 0] != 0, "t": out[:, 1], "p": out[:, 2:5], "mint": out[:, 5], "sigma_t": out[:, 6:9], "sigma_s": out[:, 9:12],
+            "sigma_n": out[:, 12:15], "combined": out[:, 15:18], "local": out[:, 18:21], "grid": out[:, 21], "raw": out}
 
 
 def check(status):

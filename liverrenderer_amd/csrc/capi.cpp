@@ -31,7 +31,7 @@ static lrt_status fail(lrt_status st, const std::string &msg) { g_error = msg; r
 extern "C" {
 
 const char *lrt_last_error(void) { return g_error.c_str(); }
-int lrt_version(void) { return 117; }    // 1.17: spot and directional emitters (lrt_emitter_desc::cutoff_angle / beam_width / texture); 1.16: tabulated / Rayleigh / blended phase functions (lrt_scene_desc.phases), lrt_phase_probe, lrt_math_eval fn 11 (cbrt); 1.15: lrt_render_stats::n_proven (the struct grows by 8 bytes); 1.14: the roughdielectric BSDF, lrt_math_eval fn 9 (erf) / 10 (erfinv); 1.13: lrt_bsdf_probe; 1.12: lrt_render_backward_grid, "<id>.sigma_t.data" in lrt_param_set / lrt_param_get; 1.11: lrt_envmap_probe; 1.10: the moment integrator (lrt_render_moment, lrt_render_moment_samples, lrt_scene_moment_get, lrt_moment_channel_name); 1.9: the guided denoiser (lrt_denoiser_create / lrt_denoise / lrt_denoiser_free), lrt_image_read_named; 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
+int lrt_version(void) { return 118; }    // 1.18: lrt_medium_probe; a singular volume to_world and an empty use_grid_bbox header box are refused; 1.17: spot and directional emitters (lrt_emitter_desc::cutoff_angle / beam_width / texture); 1.16: tabulated / Rayleigh / blended phase functions (lrt_scene_desc.phases), lrt_phase_probe, lrt_math_eval fn 11 (cbrt); 1.15: lrt_render_stats::n_proven (the struct grows by 8 bytes); 1.14: the roughdielectric BSDF, lrt_math_eval fn 9 (erf) / 10 (erfinv); 1.13: lrt_bsdf_probe; 1.12: lrt_render_backward_grid, "<id>.sigma_t.data" in lrt_param_set / lrt_param_get; 1.11: lrt_envmap_probe; 1.10: the moment integrator (lrt_render_moment, lrt_render_moment_samples, lrt_scene_moment_get, lrt_moment_channel_name); 1.9: the guided denoiser (lrt_denoiser_create / lrt_denoise / lrt_denoiser_free), lrt_image_read_named; 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
 
 static std::vector<std::pair<std::string, std::string>> parse_defines(const char *const *defines, int n) {
     std::vector<std::pair<std::string, std::string>> r;
@@ -102,6 +102,10 @@ static void validate_desc(const lrt_scene_desc &d) {
         const lrt_medium_desc &M = d.media[i];
         if (M.type < LRT_MEDIUM_HOMOGENEOUS || M.type > LRT_MEDIUM_HETEROGENEOUS) bad("invalid medium type");
         if (M.type == LRT_MEDIUM_HETEROGENEOUS && (!M.grid_data || M.grid_res[0] < 1 || M.grid_res[1] < 1 || M.grid_res[2] < 1)) bad("heterogeneous medium without grid data");
+        if (M.type == LRT_MEDIUM_HETEROGENEOUS) {                  // the volume's frame arrives ready-made (the XML loader derives it from to_world)
+            for (int k = 0; k < 12; ++k) if (!std::isfinite(M.grid_to_local[k])) bad("heterogeneous medium: grid_to_local is not finite (a singular volume to_world?)");
+            for (int k = 0; k < 3; ++k) if (!(M.grid_bbox_max[k] > M.grid_bbox_min[k]) || !std::isfinite(M.grid_bbox_min[k]) || !std::isfinite(M.grid_bbox_max[k])) bad("heterogeneous medium: empty or unbounded grid bounding box");
+        }
         if (M.phase != LRT_PHASE_ISOTROPIC && M.phase != LRT_PHASE_HG) bad("invalid phase function");
         if (M.phase == LRT_PHASE_HG && !(M.g > -1.f && M.g < 1.f)) bad("The asymmetry parameter must lie in the interval (-1, 1)!");
     }
@@ -413,6 +417,17 @@ lrt_status lrt_phase_probe(lrt_scene *scene, int medium, const float *wi, const 
     LRT_TRY
         ensure_device(scene, device);
         device_phase_probe(scene->dev, medium, wi, sample, wo_query, n, out);
+        return LRT_OK;
+    LRT_CATCH
+}
+
+lrt_status lrt_medium_probe(lrt_scene *scene, int medium, const float *o, const float *d, const float *maxt, const float *sample, const uint32_t *channel,
+                            uint32_t n, float *out, int device) {
+    if (!scene || ((!o || !d || !maxt || !sample || !channel || !out) && n)) return fail(LRT_ERR_INVALID, "lrt_medium_probe: null argument");
+    if (medium < 0 || (size_t) medium >= scene->st.media.size()) return fail(LRT_ERR_INVALID, "lrt_medium_probe: no such medium");
+    LRT_TRY
+        ensure_device(scene, device);
+        device_medium_probe(scene->dev, medium, o, d, maxt, sample, channel, n, out);
         return LRT_OK;
     LRT_CATCH
 }

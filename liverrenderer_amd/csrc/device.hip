@@ -1126,14 +1126,17 @@ void device_bsdf_probe(DeviceScene *D, const float *o, const float *d, const flo
 // The kernel is also where lrt_phase_probe runs: the set of compiled kernels is pinned (tests/golden/kernel_names.txt), and this kernel is the
 // one whose first argument already selects what a lane evaluates.  fn = LRT_MATH_PHASE_PROBE + m (device_phase_probe only; lrt_math_eval
 // refuses it): `y` is the scene record, `x` holds 9 floats per lane (wi, sample, wo_query), `out` takes LRT_PHASE_PROBE_FLOATS per lane
-// for medium m, out2 is not written.
+// for medium m, out2 is not written.  lrt_medium_probe runs here in the same way: fn = LRT_MATH_MEDIUM_PROBE + m (device_medium_probe only),
+// `x` holds 9 floats per lane (o, d, maxt, sample, channel), `out` takes LRT_MEDIUM_PROBE_FLOATS per lane.
 #define LRT_MATH_PHASE_PROBE 0x100
+#define LRT_MATH_MEDIUM_PROBE 0x40000000
 __global__ void k_math_eval(int fn, const float *__restrict__ x, const float *__restrict__ y, uint32_t n, float *__restrict__ out, float *__restrict__ out2) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (fn >= LRT_MATH_PHASE_PROBE) {
         SceneRef sc = *(ScenePtr) (const void *) y;
         const float *in = x + 9 * (size_t) i;
+        if (fn >= LRT_MATH_MEDIUM_PROBE) { medium_probe_lane(sc, fn - LRT_MATH_MEDIUM_PROBE, in, out + (size_t) LRT_MEDIUM_PROBE_FLOATS * i); return; }
         phase_probe_lane(sc, fn - LRT_MATH_PHASE_PROBE, in, in + 3, in + 6, out + (size_t) LRT_PHASE_PROBE_FLOATS * i);
         return;
     }
@@ -1181,6 +1184,26 @@ void device_phase_probe(DeviceScene *D, int medium, const float *wi, const float
     k_math_eval<<<(n + 255) / 256, 256, 0, st>>>(LRT_MATH_PHASE_PROBE + medium, in.p, (const float *) D->d_sc, n, dout.p, nullptr);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * LRT_PHASE_PROBE_FLOATS * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Test hook (include/liverrt.h lrt_medium_probe): medium_probe_lane (kernels.h) on the scene's device image, through k_math_eval's selector
+// LRT_MATH_MEDIUM_PROBE (above)
+void device_medium_probe(DeviceScene *D, int medium, const float *o, const float *d, const float *maxt, const float *sample, const uint32_t *channel, uint32_t n, float *out) {
+    HIP_CHECK(hipSetDevice(D->device));
+    if (medium < 0 || (size_t) medium >= D->h_media.size()) throw std::invalid_argument("lrt_medium_probe: no such medium");
+    if (!n) return;
+    hipStream_t st = D->stream;
+    std::vector<float> packed((size_t) n * 9);               // per lane: o, d, maxt, sample, channel
+    for (size_t i = 0; i < n; ++i) {
+        for (int c = 0; c < 3; ++c) { packed[9 * i + c] = o[3 * i + c]; packed[9 * i + 3 + c] = d[3 * i + c]; }
+        packed[9 * i + 6] = maxt[i]; packed[9 * i + 7] = sample[i]; packed[9 * i + 8] = (float) std::min<uint32_t>(channel[i], 2u);
+    }
+    DevTmp in, dout((size_t) n * LRT_MEDIUM_PROBE_FLOATS);
+    in.upload(packed.data(), packed.size(), st);
+    k_math_eval<<<(n + 255) / 256, 256, 0, st>>>(LRT_MATH_MEDIUM_PROBE + medium, in.p, (const float *) D->d_sc, n, dout.p, nullptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * LRT_MEDIUM_PROBE_FLOATS * 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
 }
 

@@ -1073,6 +1073,31 @@ DEV void phase_probe_lane(SceneRef sc, int medium, const float *wi_in, const flo
     o[0] = wo.x; o[1] = wo.y; o[2] = wo.z; o[3] = weight; o[4] = pdf; o[5] = ev; o[6] = ev;     // (eval = pdf in every family)
 }
 
+// Test hook (lrt_medium_probe), one lane: free-flight sampling in medium `medium` as volpath_iteration<HET> and any_medium_sample call it:
+// het_sample_interaction for a grid medium, medium_sample_interaction otherwise, on the ray (o, d, maxt) = in[0..6] with sample = in[7]
+// and channel = in[8].  A NaN maxt asks for the grid lookup alone: in[0..2] is then a point in the grid's local frame, wherever it lies.
+// (k_math_eval in device.hip runs it under its selector LRT_MATH_MEDIUM_PROBE: the hook adds no kernel symbol.)
+DEV void medium_probe_lane(SceneRef sc, int medium, const float *in, float *o) {
+    const DMedium M = tab(sc.media, medium);
+    Ray ray; ray.o = V3(in[0], in[1], in[2]); ray.d = V3(in[3], in[4], in[5]); ray.maxt = in[6];
+    for (int j = 0; j < LRT_MEDIUM_PROBE_FLOATS; ++j) o[j] = 0.f;
+    if (ray.maxt != ray.maxt) {
+        if (M.het) { o[18] = ray.o.x; o[19] = ray.o.y; o[20] = ray.o.z; o[21] = grid_eval(tab(sc.het, medium), ray.o); }
+        return;
+    }
+    const float ch = in[8];
+    const uint32_t channel = ch >= 2.f ? 2u : (ch >= 1.f ? 1u : 0u);
+    const MI mei = M.het ? het_sample_interaction(M, tab(sc.het, medium), ray, in[7]) : medium_sample_interaction(M, ray, in[7], channel);
+    o[0] = mei.valid() ? 1.f : 0.f; o[1] = mei.t; o[2] = mei.p.x; o[3] = mei.p.y; o[4] = mei.p.z; o[5] = mei.mint;
+    o[6] = mei.sigma_t.x; o[7] = mei.sigma_t.y; o[8] = mei.sigma_t.z; o[9] = mei.sigma_s.x; o[10] = mei.sigma_s.y; o[11] = mei.sigma_s.z;
+    o[12] = mei.sigma_n.x; o[13] = mei.sigma_n.y; o[14] = mei.sigma_n.z; o[15] = mei.combined.x; o[16] = mei.combined.y; o[17] = mei.combined.z;
+    if (M.het) {
+        const DHetMedium H = tab(sc.het, medium);
+        const V3 pl = xform_point12(H.to_local, mei.p);
+        o[18] = pl.x; o[19] = pl.y; o[20] = pl.z; o[21] = grid_eval(H, pl);
+    }
+}
+
 // Test hook (lrt_bsdf_probe): the surface code at a chosen ray, one per lane: a closest-hit query through the EXT tracer (spheres count),
 // no ray offset; the surface interaction; bsdf_sample with the lane's (s1, s2x, s2y) as path_iteration calls it; bsdf_eval and bsdf_pdf
 // at the world direction woq, brought into the shading frame as the integrators bring an emitter sample's direction.

@@ -545,8 +545,11 @@ struct Loader {
         float mx = -INFINITY; for (float x : grid) mx = std::max(mx, x);
         M.grid_max = mx;
         // m_to_local = to_world^-1 (Volume base class); use_grid_bbox: the file's bounding box maps onto the unit cube first
+        // (the reference inverts whatever it is given and renders NaNs; a volume that cannot be placed is refused here)
         Mat4 TW = get_xform(v, "to_world"), TL = inverse_affine(TW);
+        for (int k = 0; k < 12; ++k) if (!std::isfinite(TL.m[k])) fail("gridvolume: to_world is singular (not invertible)");
         if (get_bool(v, "use_grid_bbox", false)) {                                // VolumeGrid::bbox_transform: scale(1 / extents) * translate(-min)
+            for (int a = 0; a < 3; ++a) if (!(dims[3 + a] > dims[a]) || !std::isfinite(dims[a]) || !std::isfinite(dims[3 + a])) fail("gridvolume: use_grid_bbox needs a bounding box with max > min on every axis in the volume file's header");
             Mat4 B = ident();
             for (int a = 0; a < 3; ++a) { double e = (double) dims[3 + a] - (double) dims[a]; B.m[5 * a] = 1.0 / e; B.m[4 * a + 3] = -(double) dims[a] / e; }
             TL = mul(B, TL);

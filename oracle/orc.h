@@ -90,6 +90,9 @@ void  orc_square_to_uniform_sphere(float u1, float u2, float out[3]);
 void  orc_fresnel(float cos_theta_i, float eta, float out[4]);
 /* lrt_bsdf_probe on the oracle: LRT_BSDF_PROBE_FLOATS floats per input, the layout of include/liverrt.h (triangle shapes only) */
 void  orc_bsdf_probe(orc_scene *s, const float *o, const float *d, const float *sample, const float *wo_query, uint32_t n, float *out);
+/* lrt_medium_probe on the oracle: LRT_MEDIUM_PROBE_FLOATS floats per input, the layout of include/liverrt.h; 1 for a bad medium index */
+int   orc_medium_probe(orc_scene *s, int medium, const float *o, const float *d, const float *maxt, const float *sample, const uint32_t *channel,
+                       uint32_t n, float *out);
 void  orc_envmap_sample(orc_scene *s, float u1, float u2, float ref[3], float d[3], float *pdf, float rgb[3]);
 float orc_envmap_pdf(orc_scene *s, const float d[3]);
 void  orc_envmap_eval(orc_scene *s, const float d[3], float rgb[3]);

@@ -1524,6 +1524,35 @@ extern "C" void orc_bsdf_probe(orc_scene *s, const float *o, const float *d, con
         q[23] = w.x; q[24] = w.y; q[25] = w.z; q[26] = ev.x; q[27] = ev.y; q[28] = ev.z; q[29] = pdf;
     }
 }
+/* The oracle's side of lrt_medium_probe (include/liverrt.h): medium_sample_interaction on the ray (o, d, maxt) per input, the record of
+   LRT_MEDIUM_PROBE_FLOATS floats; maxt = NaN: the grid lookup at the local point o alone.  Returns 1 for a medium the scene does not have. */
+extern "C" int orc_medium_probe(orc_scene *s, int medium, const float *o, const float *d, const float *maxt, const float *sample, const uint32_t *channel,
+                                uint32_t n, float *out) {
+    const Scene &S = s->s;
+    if (medium < 0 || medium >= (int) S.d.n_media) { g_err = "orc_medium_probe: no such medium"; return 1; }
+    const lrt_medium_desc &M = S.media[medium];
+    const bool het = M.type == LRT_MEDIUM_HETEROGENEOUS;
+    for (uint32_t i = 0; i < n; ++i) {
+        float *q = out + (size_t) LRT_MEDIUM_PROBE_FLOATS * i;
+        for (int k = 0; k < LRT_MEDIUM_PROBE_FLOATS; ++k) q[k] = 0.f;
+        Ray r; r.o = V3(o[3 * i], o[3 * i + 1], o[3 * i + 2]); r.d = V3(d[3 * i], d[3 * i + 1], d[3 * i + 2]); r.maxt = maxt[i];
+        if (r.maxt != r.maxt) {
+            if (het) { q[18] = r.o.x; q[19] = r.o.y; q[20] = r.o.z; q[21] = grid_eval(M, r.o); }
+            continue;
+        }
+        const MI mei = medium_sample_interaction(S, medium, r, sample[i], channel[i] < 2u ? channel[i] : 2u);
+        q[0] = mei.valid() ? 1.f : 0.f; q[1] = mei.t; q[2] = mei.p.x; q[3] = mei.p.y; q[4] = mei.p.z; q[5] = mei.mint;
+        q[6] = mei.sigma_t.x; q[7] = mei.sigma_t.y; q[8] = mei.sigma_t.z; q[9] = mei.sigma_s.x; q[10] = mei.sigma_s.y; q[11] = mei.sigma_s.z;
+        q[12] = mei.sigma_n.x; q[13] = mei.sigma_n.y; q[14] = mei.sigma_n.z; q[15] = mei.combined.x; q[16] = mei.combined.y; q[17] = mei.combined.z;
+        if (het) {
+            const float *t = M.grid_to_local;
+            const V3 pl(fmaf(t[2], mei.p.z, fmaf(t[1], mei.p.y, fmaf(t[0], mei.p.x, t[3]))), fmaf(t[6], mei.p.z, fmaf(t[5], mei.p.y, fmaf(t[4], mei.p.x, t[7]))),
+                        fmaf(t[10], mei.p.z, fmaf(t[9], mei.p.y, fmaf(t[8], mei.p.x, t[11]))));
+            q[18] = pl.x; q[19] = pl.y; q[20] = pl.z; q[21] = grid_eval(M, pl);
+        }
+    }
+    return 0;
+}
 extern "C" void orc_envmap_sample(orc_scene *s, float u1, float u2, float ref[3], float d[3], float *pdf, float rgb[3]) {
     DirSample ds; V3 w = sample_emitter_direction(s->s, V3(ref[0], ref[1], ref[2]), u1, u2, &ds);
     d[0] = ds.d.x; d[1] = ds.d.y; d[2] = ds.d.z; *pdf = ds.pdf; rgb[0] = w.x; rgb[1] = w.y; rgb[2] = w.z;

@@ -77,6 +77,7 @@ def lib():
     L.orc_envmap_eval.argtypes = [C.c_void_p, P(C.c_float), P(C.c_float)]
     L.orc_bsdf_probe.argtypes = [C.c_void_p, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), C.c_uint32, P(C.c_float)]
     L.orc_bsdf_probe.restype = None
+    L.orc_medium_probe.argtypes = [C.c_void_p, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_uint32), C.c_uint32, P(C.c_float)]
     L.orc_rfilter_eval.argtypes = [C.c_void_p, C.c_float]
     L.orc_rfilter_eval.restype = C.c_float
     L.orc_sample_ray.argtypes = [C.c_void_p, C.c_float, C.c_float, P(C.c_float), P(C.c_float), P(C.c_float)]
@@ -199,6 +200,18 @@ class OrcScene:
         out = np.empty((n, _lib.BSDF_PROBE_FLOATS), np.float32)
         self._L.orc_bsdf_probe(self._h, *[_fp(x) for x in a], n, _fp(out))
         return _lib.bsdf_probe_fields(out)
+
+    def medium_probe(self, medium, o, d, maxt, sample, channel):
+        """orc_medium_probe: the oracle's twin of Scene.medium_probe, the same dict of arrays"""
+        o, d = (np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (o, d))
+        maxt, sample = (np.ascontiguousarray(x, np.float32).reshape(-1) for x in (maxt, sample))
+        channel = np.ascontiguousarray(channel, np.uint32).reshape(-1)
+        n = o.shape[0]
+        assert all(x.shape[0] == n for x in (d, maxt, sample, channel))
+        out = np.zeros((n, _lib.MEDIUM_PROBE_FLOATS), np.float32)
+        if self._L.orc_medium_probe(self._h, int(medium), _fp(o), _fp(d), _fp(maxt), _fp(sample), channel.ctypes.data_as(C.POINTER(C.c_uint32)), n, _fp(out)) != 0:
+            raise RuntimeError(self._L.orc_last_error().decode())
+        return _lib.medium_probe_fields(out)
 
     def envmap_sample_n(self, samples, ref=(0, 0, 0)):
         """envmap_sample at n samples (n, 2): directions (n, 3), pdfs (n,), weights (n, 3)"""
