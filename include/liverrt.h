@@ -59,7 +59,8 @@ enum { LRT_INTEGRATOR_PATH = 0, LRT_INTEGRATOR_VOLPATH = 1, LRT_INTEGRATOR_PRBVO
 /* medium plugins: src/media/homogeneous.cpp, liver.cpp, parenchyma.cpp, glissonCapsule.cpp (docs/BIO_TRANSPORT_SPEC.md) */
 enum { LRT_MEDIUM_HOMOGENEOUS = 0, LRT_MEDIUM_LIVER = 1, LRT_MEDIUM_PARENCHYMA = 2, LRT_MEDIUM_GLISSON = 3,
        LRT_MEDIUM_HETEROGENEOUS = 4   /* src/media/heterogeneous.cpp: sigma_t from a grid volume, delta tracking */ };
-enum { LRT_BSDF_DIFFUSE = 0, LRT_BSDF_DIELECTRIC = 1, LRT_BSDF_BUMPMAP = 2, LRT_BSDF_NULL = 3, LRT_BSDF_ROUGHDIELECTRIC = 4 };
+enum { LRT_BSDF_DIFFUSE = 0, LRT_BSDF_DIELECTRIC = 1, LRT_BSDF_BUMPMAP = 2, LRT_BSDF_NULL = 3, LRT_BSDF_ROUGHDIELECTRIC = 4,
+       LRT_BSDF_CONDUCTOR = 5, LRT_BSDF_PLASTIC = 6, LRT_BSDF_TWOSIDED = 7   /* [v119] src/bsdfs/conductor.cpp, plastic.cpp, twosided.cpp */ };
 enum { LRT_TEX_RGB = 0, LRT_TEX_CHECKERBOARD = 1, LRT_TEX_BITMAP = 2 };
 enum { LRT_PHASE_ISOTROPIC = 0, LRT_PHASE_HG = 1,
        /* [v116] entries of lrt_scene_desc.phases only (lrt_medium_desc.phase stays ISOTROPIC or HG) */
@@ -125,6 +126,15 @@ typedef struct {
     int32_t sample_visible;   /* visible-normal sampling (Heitz and d'Eon)         */
     int32_t specular_reflectance;    /* texture index (rgb or checkerboard), -1: none */
     int32_t specular_transmittance;  /* texture index (rgb or checkerboard), -1: none */
+    /* [v119] conductor, plastic, twosided; ignored by the other types.
+     * conductor: eta_rgb + i k_rgb, specular_reflectance (a texture index, required).
+     * plastic: eta (int_ior / ext_ior), diffuse_reflectance (a texture index, required), specular_reflectance (-1: none), nonlinear.
+     * twosided: nested (the front child), nested_back (the back child; -1 or equal to `nested`: one child serves both sides).  The children
+     * are diffuse, conductor or plastic. */
+    float   eta_rgb[3], k_rgb[3];
+    int32_t diffuse_reflectance;
+    int32_t nonlinear;
+    int32_t nested_back;
 } lrt_bsdf_desc;
 
 typedef struct {
@@ -311,7 +321,7 @@ typedef struct {
 typedef struct lrt_scene lrt_scene;
 
 LRT_API const char *lrt_last_error(void);
-LRT_API int         lrt_version(void);   /* 118: lrt_medium_probe; the loader refuses a singular volume to_world and an empty use_grid_bbox header box; 117: spot and directional emitters (LRT_EMITTER_SPOT / _DIRECTIONAL, lrt_emitter_desc grows by cutoff_angle, beam_width, texture: rebuild hosts against this header); 116: tabulated, Rayleigh and blended phase functions (lrt_phase_desc, lrt_scene_desc.phases, lrt_medium_desc.phase_index), lrt_phase_probe, lrt_math_eval fn 11; 115: lrt_render_stats.n_proven appended (lrt_render_stats_get writes 8 bytes more: rebuild hosts against this header); 114: the roughdielectric BSDF (LRT_BSDF_ROUGHDIELECTRIC, the fields after `scale` of lrt_bsdf_desc), lrt_math_eval fn 9 / 10; 113: lrt_bsdf_probe; 112:lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
+LRT_API int         lrt_version(void);   /* 119: the conductor, plastic and twosided BSDFs (LRT_BSDF_CONDUCTOR / _PLASTIC / _TWOSIDED, the fields after `specular_transmittance` of lrt_bsdf_desc); 118: lrt_medium_probe; the loader refuses a singular volume to_world and an empty use_grid_bbox header box; 117: spot and directional emitters (LRT_EMITTER_SPOT / _DIRECTIONAL, lrt_emitter_desc grows by cutoff_angle, beam_width, texture: rebuild hosts against this header); 116: tabulated, Rayleigh and blended phase functions (lrt_phase_desc, lrt_scene_desc.phases, lrt_medium_desc.phase_index), lrt_phase_probe, lrt_math_eval fn 11; 115: lrt_render_stats.n_proven appended (lrt_render_stats_get writes 8 bytes more: rebuild hosts against this header); 114: the roughdielectric BSDF (LRT_BSDF_ROUGHDIELECTRIC, the fields after `scale` of lrt_bsdf_desc), lrt_math_eval fn 9 / 10; 113: lrt_bsdf_probe; 112:lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
 
 LRT_API lrt_status lrt_scene_load_xml(const char *path, const char *const *defines,
                                       int n_defines, lrt_scene **out);

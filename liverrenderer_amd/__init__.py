@@ -119,6 +119,7 @@ _TAGS = {
     "perspective": "sensor", "independent": "sampler", "ldsampler": "sampler", "hdrfilm": "film",
     "box": "rfilter", "gaussian": "rfilter", "tent": "rfilter",
     "diffuse": "bsdf", "dielectric": "bsdf", "bumpmap": "bsdf", "null": "bsdf", "roughdielectric": "bsdf",
+    "conductor": "bsdf", "plastic": "bsdf", "twosided": "bsdf",
     "bitmap": "texture", "checkerboard": "texture",
     "homogeneous": "medium", "liver": "medium", "parenchyma": "medium", "glissonCapsule": "medium", "heterogeneous": "medium",
     "gridvolume": "volume",

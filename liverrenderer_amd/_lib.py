@@ -36,7 +36,11 @@ class BsdfDesc(C.Structure):
     _fields_ = [("type", C.c_int32), ("reflectance", C.c_int32), ("eta", C.c_float), ("nested", C.c_int32),
                 ("texture", C.c_int32), ("scale", C.c_float),
                 ("alpha_u", C.c_float), ("alpha_v", C.c_float), ("distribution", C.c_int32), ("sample_visible", C.c_int32),
-                ("specular_reflectance", C.c_int32), ("specular_transmittance", C.c_int32)]      # [v114] roughdielectric
+                ("specular_reflectance", C.c_int32), ("specular_transmittance", C.c_int32),      # [v114] roughdielectric
+                ("eta_r", C.c_float), ("eta_g", C.c_float), ("eta_b", C.c_float), ("k_r", C.c_float), ("k_g", C.c_float), ("k_b", C.c_float),   # [v119] eta_rgb[3], k_rgb[3] (scalars, so that fields compare by value)
+                ("diffuse_reflectance", C.c_int32), ("nonlinear", C.c_int32), ("nested_back", C.c_int32)]      # [v119] conductor, plastic, twosided
+    eta_rgb = property(lambda self: (self.eta_r, self.eta_g, self.eta_b))
+    k_rgb = property(lambda self: (self.k_r, self.k_g, self.k_b))
 
 
 class MediumDesc(C.Structure):

@@ -31,7 +31,7 @@ static lrt_status fail(lrt_status st, const std::string &msg) { g_error = msg; r
 extern "C" {
 
 const char *lrt_last_error(void) { return g_error.c_str(); }
-int lrt_version(void) { return 118; }    // 1.18: lrt_medium_probe; a singular volume to_world and an empty use_grid_bbox header box are refused; 1.17: spot and directional emitters (lrt_emitter_desc::cutoff_angle / beam_width / texture); 1.16: tabulated / Rayleigh / blended phase functions (lrt_scene_desc.phases), lrt_phase_probe, lrt_math_eval fn 11 (cbrt); 1.15: lrt_render_stats::n_proven (the struct grows by 8 bytes); 1.14: the roughdielectric BSDF, lrt_math_eval fn 9 (erf) / 10 (erfinv); 1.13: lrt_bsdf_probe; 1.12: lrt_render_backward_grid, "<id>.sigma_t.data" in lrt_param_set / lrt_param_get; 1.11: lrt_envmap_probe; 1.10: the moment integrator (lrt_render_moment, lrt_render_moment_samples, lrt_scene_moment_get, lrt_moment_channel_name); 1.9: the guided denoiser (lrt_denoiser_create / lrt_denoise / lrt_denoiser_free), lrt_image_read_named; 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
+int lrt_version(void) { return 119; }    // 1.19: the conductor, plastic and twosided BSDFs; 1.18: lrt_medium_probe; a singular volume to_world and an empty use_grid_bbox header box are refused; 1.17: spot and directional emitters (lrt_emitter_desc::cutoff_angle / beam_width / texture); 1.16: tabulated / Rayleigh / blended phase functions (lrt_scene_desc.phases), lrt_phase_probe, lrt_math_eval fn 11 (cbrt); 1.15: lrt_render_stats::n_proven (the struct grows by 8 bytes); 1.14: the roughdielectric BSDF, lrt_math_eval fn 9 (erf) / 10 (erfinv); 1.13: lrt_bsdf_probe; 1.12: lrt_render_backward_grid, "<id>.sigma_t.data" in lrt_param_set / lrt_param_get; 1.11: lrt_envmap_probe; 1.10: the moment integrator (lrt_render_moment, lrt_render_moment_samples, lrt_scene_moment_get, lrt_moment_channel_name); 1.9: the guided denoiser (lrt_denoiser_create / lrt_denoise / lrt_denoiser_free), lrt_image_read_named; 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
 
 static std::vector<std::pair<std::string, std::string>> parse_defines(const char *const *defines, int n) {
     std::vector<std::pair<std::string, std::string>> r;
@@ -78,15 +78,17 @@ static void validate_desc(const lrt_scene_desc &d) {
     }
     for (uint32_t i = 0; i < d.n_bsdfs; ++i) {
         const lrt_bsdf_desc &B = d.bsdfs[i];
-        if (B.type < LRT_BSDF_DIFFUSE || B.type > LRT_BSDF_ROUGHDIELECTRIC) bad("invalid bsdf type");
+        if (B.type < LRT_BSDF_DIFFUSE || B.type > LRT_BSDF_TWOSIDED) bad("invalid bsdf type");
         if (B.type == LRT_BSDF_DIFFUSE) {
             if (B.reflectance < 0 || (uint32_t) B.reflectance >= d.n_textures) bad("diffuse bsdf references an invalid texture");
             if (d.textures[B.reflectance].type == LRT_TEX_BITMAP) throw std::runtime_error("unsupported: a bitmap texture as diffuse reflectance (bitmaps are supported as bump-map heights only)");
         }
         if (B.type == LRT_BSDF_BUMPMAP) {
             if (B.nested < 0 || (uint32_t) B.nested >= d.n_bsdfs || d.bsdfs[B.nested].type == LRT_BSDF_BUMPMAP) bad("bumpmap references an invalid nested bsdf");
+            if (d.bsdfs[B.nested].type == LRT_BSDF_TWOSIDED) throw std::runtime_error("unsupported: a twosided BSDF nested in a bumpmap");
             if (B.texture < 0 || (uint32_t) B.texture >= d.n_textures) bad("bumpmap references an invalid texture");
         }
+        if (B.type == LRT_BSDF_CONDUCTOR || B.type == LRT_BSDF_PLASTIC || B.type == LRT_BSDF_TWOSIDED) validate_smooth_bsdf(d, i);
         if (B.type == LRT_BSDF_DIELECTRIC && !(B.eta > 0.f)) bad("dielectric with a non-positive relative index of refraction");
         if (B.type == LRT_BSDF_ROUGHDIELECTRIC) {
             if (!(B.eta > 0.f) || B.eta == 1.f) bad("roughdielectric: the interior and exterior indices of refraction must be positive and differ");

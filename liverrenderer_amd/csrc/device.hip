@@ -97,6 +97,7 @@ struct DeviceScene {
     std::vector<DBioMedium> h_bio; DBioMedium *d_bio = nullptr;
     std::vector<DHetMedium> h_het; DHetMedium *d_het = nullptr; std::vector<float *> het_data; bool has_het = false, has_non_bio = false, need_mis = false; uint32_t ws_layouts = 0;   // ws_layouts: the record layouts the workspace is allocated for (layout_bit mask)
     bool ext = false;                      // spheres, point emitters, area emitters on meshes, a roughdielectric on a shape or a tabulated / Rayleigh / blended phase function on a referenced medium: the EXT kernel instances (ExtTracer, point- / mesh-emitter sampling, the rough BSDF, DScene::phases), wide records
+    bool smooth_bsdf = false;              // a conductor / plastic / twosided on a shape (it sets `ext` too): prbvolpath's refusal names it
     bool has_area_emitter = false;         // decides the record layout: only an area emitter's pdf reads the last scatter position (record_layout.h)
     float *dgrid = nullptr; size_t dgrid_floats = 0;   // lrt_render_backward_grid with a host result: the device-side gradient grid
     bool prb_null = false;                 // prbvolpath.py:84-91 `handle_null_scattering`: a heterogeneous medium is attached to a shape
@@ -264,7 +265,7 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
     // prepares the rest.  P outlives the copies below (the synchronize at the end); the device pointers are patched into its scene record.
     PreparedScene P; DScene &sc = P.sc;
     prepare_geometry(d, opt, P);
-    D->n_cus = opt.n_cus; D->bvh_leaf = P.bvh_leaf; D->ext = P.ext;
+    D->n_cus = opt.n_cus; D->bvh_leaf = P.bvh_leaf; D->ext = P.ext; D->smooth_bsdf = P.smooth_bsdf;
     auto up = [&](const auto &v) { return D->track(dev_upload(v.data(), v.size(), st)); };
     sc.spheres = P.spheres.empty() ? nullptr : up(P.spheres);
     sc.nodes = (const float4 *) up(P.bvh.nodes);
@@ -315,6 +316,7 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
     sc.mesh_emitters = up(P.mesh_emitters);
     sc.mesh_emitter_tab = up(P.mesh_emitter_tab);
     sc.delta_emitters = P.delta_emitters.empty() ? nullptr : up(P.delta_emitters);
+    sc.bsdf_ext = P.bsdf_ext.empty() ? nullptr : up(P.bsdf_ext);
     sc.cone_tab = P.cone_tab.empty() ? nullptr : (const uint2 *) up(P.cone_tab);      // (sc.cone_enabled: set by the preparation with the table)
     sc.phases = P.phases.empty() ? nullptr : up(P.phases);
     sc.phase_pool = P.phase_pool.empty() ? nullptr : up(P.phase_pool);
@@ -487,6 +489,8 @@ static void launch_prb(DeviceScene *D, const DRenderParams &rp, const PoolGeomet
 static void check_integrator_media(DeviceScene *D, int integrator) {
     if ((integrator == LRT_INTEGRATOR_BIOVOLPATH || integrator == LRT_INTEGRATOR_BIOVOLPATH06) && D->has_non_bio)
         throw std::runtime_error("NotImplementedError: sample_interaction (the bio integrators need liver / parenchyma / glissonCapsule media)");
+    if (integrator == LRT_INTEGRATOR_PRBVOLPATH && D->smooth_bsdf)
+        throw std::runtime_error("unsupported: prbvolpath on a scene with a conductor / plastic / twosided BSDF (no adjoint is built for them)");
     if (integrator == LRT_INTEGRATOR_PRBVOLPATH && D->ext)
         throw std::runtime_error("unsupported: prbvolpath on a scene with sphere shapes, point / spot / directional emitters, area emitters on meshes, a roughdielectric BSDF or a tabulated / Rayleigh / blended phase function (its adjoint is built for triangles, rectangle / infinite emitters, the diffuse / dielectric / null BSDFs and the isotropic / hg phase functions)");
     if (integrator == LRT_INTEGRATOR_VOLPATHMIS) D->need_mis = true;          // its wider path record is allocated on first use

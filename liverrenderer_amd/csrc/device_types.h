@@ -27,6 +27,20 @@ struct DBsdf {
     union { int32_t pad; float alpha_v; };
 };
 static_assert(sizeof(DBsdf) == 32, "DBsdf stride");
+// conductor: specular_reflectance, flags; the complex index lives in DBsdfExt.  plastic: reflectance (= diffuse_reflectance), eta, flags; the rest
+// in DBsdfExt.  twosided: nested (= the front child), flags (= the union of the children's); the back child in DBsdfExt.
+
+// What conductor / plastic / twosided need beyond those 32 bytes (src/bsdfs/conductor.cpp, plastic.cpp, twosided.cpp): DScene::bsdf_ext, one
+// row per BSDF, indexed like DScene::bsdfs (all zero for every other type); null when the scene has none of the three.  Four 16-byte words:
+// one row is four vector (or scalar) loads.
+struct alignas(16) DBsdfExt {
+    float eta[3]; float inv_eta_2;       // conductor: real part of the index per channel | plastic: 1 / eta^2 (plastic.cpp:193)
+    float k[3]; float fdr_int;           // conductor: imaginary part               | plastic: fresnel_diffuse_reflectance(1 / eta) (:196)
+    float fdr_ext, spec_weight;          // plastic: fresnel_diffuse_reflectance(eta) (:197), specular_sampling_weight (:200-206)
+    int32_t nonlinear, specular_reflectance;   // plastic: `nonlinear`; its specular_reflectance texture, -1: none
+    int32_t back; int32_t pad[3];        // twosided: the back child (= DBsdf::nested when there is one child: the same-child branch, twosided.cpp:124)
+};
+static_assert(sizeof(DBsdfExt) == 64, "DBsdfExt stride");
 
 struct DTexture {
     int32_t type, width, height, channels;
@@ -196,6 +210,7 @@ struct DScene {
     const DPhase *phases;                // tabulated / Rayleigh / blended phase functions and a blend's children (DMedium::phase_ext; the EXT instances only read them)
     const float *phase_pool;             // every tabulated entry's interval records and cdf
     const DDeltaEmitter *delta_emitters; // n_emitters entries: spot and directional emitters (the EXT instances only read them); null: the scene has neither
+    const DBsdfExt *bsdf_ext;            // one row per BSDF: conductor / plastic / twosided (the EXT instances only read them); null: the scene has none of them
 };
 
 // Direction bins of DScene::cone_tab: bin k holds the directions whose cosine to the side's geometric normal is at least LRT_CONE_COSk

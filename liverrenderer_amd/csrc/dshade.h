@@ -871,12 +871,95 @@ DEV void rough_eval_pdf(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, V3 wo,
     *pdf_out = active ? pdf * __builtin_fabsf(dwh_dwo) : 0.f;
 }
 
-// Leaf BSDFs (diffuse / dielectric / null; EXT: roughdielectric too), evaluated in the frame `wi` is given in.
+// ------------------------------------------------- conductor, plastic, twosided (src/bsdfs/conductor.cpp, plastic.cpp, twosided.cpp)
+// Compiled into the EXT instances, k_bsdf_probe and the EXT aov kernels alone, like the roughdielectric.  X: the BSDF's row of DScene::bsdf_ext.
+DEV BSDFSample bsdf_sample_zero() { BSDFSample bs; bs.wo = V3(0.f); bs.pdf = 0.f; bs.eta = 0.f; bs.type = 0; bs.weight = V3(0.f); return bs; }   // dr::zeros<BSDFSample3f>
+// include/mitsuba/render/fresnel.h:92-117, one channel.  eta = 0, k = 1 (the plugin's defaults, a perfect mirror) gives exactly 1: temp_1 = -(1 + sin^2),
+// a_2_pb_2 = sqrt(temp_1^2) = -temp_1, a = 0, so r_s = term_1 / term_1 and r_p = r_s * term_3 / term_3.
+DEV float fresnel_conductor(float cos_theta_i, float eta_r, float eta_i) {
+    const float cos_theta_i_2 = cos_theta_i * cos_theta_i, sin_theta_i_2 = 1.f - cos_theta_i_2, sin_theta_i_4 = sin_theta_i_2 * sin_theta_i_2;
+    const float temp_1 = eta_r * eta_r - eta_i * eta_i - sin_theta_i_2;
+    const float a_2_pb_2 = safe_sqrt(temp_1 * temp_1 + 4.f * eta_i * eta_i * eta_r * eta_r);
+    const float a = safe_sqrt(.5f * (a_2_pb_2 + temp_1));
+    const float term_1 = a_2_pb_2 + cos_theta_i_2, term_2 = 2.f * cos_theta_i * a;
+    const float r_s = (term_1 - term_2) / (term_1 + term_2);
+    const float term_3 = a_2_pb_2 * cos_theta_i_2 + sin_theta_i_4, term_4 = term_2 * sin_theta_i_2;
+    const float r_p = r_s * (term_3 - term_4) / (term_3 + term_4);
+    return 0.5f * (r_s + r_p);
+}
+// conductor.cpp:247-307 sample(), unpolarized; eval() and pdf() are 0 (:309-317)
+DEV BSDFSample conductor_sample(SceneRef sc, const DBsdf &B, const DBsdfExt &X, const SI &si, V3 wi) {
+    BSDFSample bs = bsdf_sample_zero();
+    const float cos_theta_i = wi.z;
+    if (!(cos_theta_i > 0.f)) return bs;
+    bs.type = F_DELTA; bs.wo = V3(-wi.x, -wi.y, wi.z); bs.eta = 1.f; bs.pdf = 1.f;       // reflect(wi), fresnel.h:269-271
+    const V3 reflectance = tex_eval(sc, B.specular_reflectance, si);
+    bs.weight = V3(reflectance.x * fresnel_conductor(cos_theta_i, X.eta[0], X.k[0]), reflectance.y * fresnel_conductor(cos_theta_i, X.eta[1], X.k[1]),
+                   reflectance.z * fresnel_conductor(cos_theta_i, X.eta[2], X.k[2]));
+    return bs;
+}
+DEV float fresnel_r(float cos_theta_i, float eta) { float r, ctt, e0, e1; fresnel(cos_theta_i, eta, &r, &ctt, &e0, &e1); return r; }
+// the diffuse base with its internal scattering, plastic.cpp:264-265 / :290-291: diff /= 1 - (nonlinear ? diff * fdr_int : fdr_int)
+DEV V3 plastic_base(SceneRef sc, const DBsdf &B, const DBsdfExt &X, const SI &si) {
+    const V3 d = tex_eval(sc, B.reflectance, si);
+    if (X.nonlinear) return V3(d.x / (1.f - d.x * X.fdr_int), d.y / (1.f - d.y * X.fdr_int), d.z / (1.f - d.z * X.fdr_int));
+    const float den = 1.f - X.fdr_int;
+    return V3(d.x / den, d.y / den, d.z / den);
+}
+// plastic.cpp:209-271 sample(), both components enabled: the 1-D sample chooses the lobe
+DEV BSDFSample plastic_sample(SceneRef sc, const DBsdf &B, const DBsdfExt &X, const SI &si, V3 wi, float s1, float s2x, float s2y) {
+    BSDFSample bs = bsdf_sample_zero();
+    const float cos_theta_i = wi.z;
+    if (!(cos_theta_i > 0.f)) return bs;
+    const float f_i = fresnel_r(cos_theta_i, B.eta);
+    float prob_specular = f_i * X.spec_weight, prob_diffuse = (1.f - f_i) * (1.f - X.spec_weight);
+    prob_specular = prob_specular / (prob_specular + prob_diffuse);
+    prob_diffuse = 1.f - prob_specular;
+    bs.eta = 1.f;
+    if (s1 < prob_specular) {
+        bs.wo = V3(-wi.x, -wi.y, wi.z); bs.pdf = prob_specular; bs.type = F_DELTA;
+        V3 value(f_i / bs.pdf);
+        if (X.specular_reflectance >= 0) value = value * tex_eval(sc, X.specular_reflectance, si);
+        bs.weight = value;
+    } else {
+        bs.wo = square_to_cosine_hemisphere(s2x, s2y);
+        bs.pdf = prob_diffuse * (kInvPi * bs.wo.z); bs.type = F_SMOOTH;
+        const float f_o = fresnel_r(bs.wo.z, B.eta);
+        bs.weight = plastic_base(sc, B, X, si) * (X.inv_eta_2 * (1.f - f_i) * (1.f - f_o) / prob_diffuse);
+    }
+    return bs;
+}
+// plastic.cpp:325-360 eval_pdf(): what eval() (:273-297) and pdf() (:299-323) return, operation for operation
+DEV void plastic_eval_pdf(SceneRef sc, const DBsdf &B, const DBsdfExt &X, const SI &si, V3 wi, V3 wo, V3 *value_out, float *pdf_out) {
+    *value_out = V3(0.f); *pdf_out = 0.f;
+    const float cos_theta_i = wi.z, cos_theta_o = wo.z;
+    if (!(cos_theta_i > 0.f && cos_theta_o > 0.f)) return;
+    const float f_i = fresnel_r(cos_theta_i, B.eta), f_o = fresnel_r(cos_theta_o, B.eta);
+    const float hemi_pdf = kInvPi * cos_theta_o;
+    *value_out = plastic_base(sc, B, X, si) * (hemi_pdf * X.inv_eta_2 * (1.f - f_i) * (1.f - f_o));
+    const float prob_specular = f_i * X.spec_weight;
+    float prob_diffuse = (1.f - f_i) * (1.f - X.spec_weight);
+    prob_diffuse = prob_diffuse / (prob_specular + prob_diffuse);
+    *pdf_out = hemi_pdf * prob_diffuse;
+}
+// twosided.cpp:124-145: the child that serves a hit with this cos theta_i; -1: neither (two children and wi.z = 0: both masks are off).
+// One child (the same-child branch, :124-127): it serves both sides.  Either way the child sees (wi.x, wi.y, |wi.z|) and wo.z carries the sign
+// of wi.z (`abs` / `mulsign` there, the two negations of the back side here: the same bits).
+DEV int twosided_child(SceneRef sc, int b, const DBsdf &B, float wi_z) {
+    const int back = sc.bsdf_ext[b].back;
+    if (back == B.nested) return back;
+    return wi_z > 0.f ? B.nested : (wi_z < 0.f ? back : -1);
+}
+
+// Leaf BSDFs (diffuse / dielectric / null; EXT: roughdielectric, conductor and plastic too), evaluated in the frame `wi` is given in.
 // DIELECTRIC: the caller has proven that the leaf is a dielectric (the 64-byte-record kernels, closed_records (b) in device.hip): no dispatch.
-// EXT: the scene may hold a roughdielectric (the EXT instances, k_bsdf_probe); without it the rough code is not compiled in.
+// EXT: the scene may hold a roughdielectric, a conductor or a plastic (the EXT instances, k_bsdf_probe); without it their code is not compiled in.
+// b: the leaf's index, for its row of DScene::bsdf_ext (EXT alone reads it).
 template <bool DIELECTRIC = false, bool EXT = false>
-DEV BSDFSample leaf_sample(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, float s1, float s2x, float s2y) {
+DEV BSDFSample leaf_sample(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, float s1, float s2x, float s2y, int b = -1) {
     if (EXT && !DIELECTRIC && B.type == LRT_BSDF_ROUGHDIELECTRIC) return rough_sample(sc, B, si, wi, s1, s2x, s2y);
+    if (EXT && !DIELECTRIC && B.type == LRT_BSDF_CONDUCTOR) return conductor_sample(sc, B, tab(sc.bsdf_ext, b, sc.one_shape), si, wi);
+    if (EXT && !DIELECTRIC && B.type == LRT_BSDF_PLASTIC) return plastic_sample(sc, B, tab(sc.bsdf_ext, b, sc.one_shape), si, wi, s1, s2x, s2y);
     BSDFSample bs;
     bs.wo = V3(0.f); bs.pdf = 0.f; bs.eta = 0.f; bs.type = 0; bs.weight = V3(0.f);       // dr::zeros<BSDFSample3f>
     if (!DIELECTRIC && B.type == LRT_BSDF_DIFFUSE) {               // src/bsdfs/diffuse.cpp sample()
@@ -906,8 +989,9 @@ DEV BSDFSample leaf_sample(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, flo
     return bs;
 }
 template <bool EXT = false>
-DEV V3 leaf_eval(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, V3 wo) {
+DEV V3 leaf_eval(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, V3 wo, int b = -1) {
     if (EXT && B.type == LRT_BSDF_ROUGHDIELECTRIC) { V3 v; float p; rough_eval_pdf(sc, B, si, wi, wo, &v, &p); return v; }
+    if (EXT && B.type == LRT_BSDF_PLASTIC) { V3 v; float p; plastic_eval_pdf(sc, B, tab(sc.bsdf_ext, b, sc.one_shape), si, wi, wo, &v, &p); return v; }
     if (B.type == LRT_BSDF_DIFFUSE) {
         if (!(wi.z > 0.f && wo.z > 0.f)) return V3(0.f);
         return tex_eval(sc, B.reflectance, si) * kInvPi * wo.z;
@@ -915,19 +999,32 @@ DEV V3 leaf_eval(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, V3 wo) {
     return V3(0.f);
 }
 template <bool EXT = false>
-DEV float leaf_pdf(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, V3 wo) {
+DEV float leaf_pdf(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, V3 wo, int b = -1) {
     if (EXT && B.type == LRT_BSDF_ROUGHDIELECTRIC) { V3 v; float p; rough_eval_pdf(sc, B, si, wi, wo, &v, &p); return p; }
+    if (EXT && B.type == LRT_BSDF_PLASTIC) { V3 v; float p; plastic_eval_pdf(sc, B, tab(sc.bsdf_ext, b, sc.one_shape), si, wi, wo, &v, &p); return p; }
     if (B.type == LRT_BSDF_DIFFUSE) return (wi.z > 0.f && wo.z > 0.f) ? kInvPi * wo.z : 0.f;
     return 0.f;
 }
 
+// EXT: a twosided (twosided.cpp:111-258) hands the hit to one of its children, a leaf, with |wi.z|, and the sign of wi.z goes onto wo.z: of the
+// sample on the way out, of the query on the way in (twosided_child).  Every other BSDF keeps its wi and a sign of +1, which changes no bit.
+struct LeafRef { DBsdf B; int b; V3 wi; float sign; bool none; };
+template <bool EXT>
+DEV LeafRef leaf_of(SceneRef sc, int b, const DBsdf &B, V3 wi) {
+    LeafRef r; r.B = B; r.b = b; r.wi = wi; r.sign = 1.f; r.none = false;
+    if (EXT && B.type == LRT_BSDF_TWOSIDED) {
+        r.b = twosided_child(sc, b, B, wi.z); r.none = r.b < 0;
+        r.B = tab(sc.bsdfs, r.none ? B.nested : r.b, sc.one_shape); r.wi.z = __builtin_fabsf(wi.z); r.sign = wi.z;
+    }
+    return r;
+}
 template <bool DIELECTRIC = false, bool EXT = false>                 // (every leaf is a dielectric, see leaf_sample)
 DEV BSDFSample bsdf_sample(SceneRef sc, int b, const SI &si, float s1, float s2x, float s2y) {
     const DBsdf B = tab(sc.bsdfs, b, sc.one_shape);
     if (B.type == LRT_BSDF_BUMPMAP) {               // src/bsdfs/bumpmap.cpp:138-162
         Frame pf = bump_frame(sc, B, si);
         V3 pwi = pf.to_local(si.wi);
-        BSDFSample bs = leaf_sample<DIELECTRIC, EXT>(sc, tab(sc.bsdfs, B.nested, sc.one_shape), si, pwi, s1, s2x, s2y);
+        BSDFSample bs = leaf_sample<DIELECTRIC, EXT>(sc, tab(sc.bsdfs, B.nested, sc.one_shape), si, pwi, s1, s2x, s2y, B.nested);
         bool active = any_nonzero(bs.weight);
         V3 pwo = pf.to_world(bs.wo);
         active = active && (bs.wo.z * pwo.z > 0.f);
@@ -936,7 +1033,14 @@ DEV BSDFSample bsdf_sample(SceneRef sc, int b, const SI &si, float s1, float s2x
         bs.weight = active ? w : V3(0.f);
         return bs;
     }
-    return leaf_sample<DIELECTRIC, EXT>(sc, B, si, si.wi, s1, s2x, s2y);
+    if constexpr (EXT && !DIELECTRIC) {
+        const LeafRef l = leaf_of<true>(sc, b, B, si.wi);
+        if (l.none) return bsdf_sample_zero();
+        BSDFSample bs = leaf_sample<false, true>(sc, l.B, si, l.wi, s1, s2x, s2y, l.b);
+        bs.wo.z = mulsign(bs.wo.z, l.sign);
+        return bs;
+    } else
+        return leaf_sample<DIELECTRIC, EXT>(sc, B, si, si.wi, s1, s2x, s2y);
 }
 template <bool EXT = false>
 DEV V3 bsdf_eval(SceneRef sc, int b, const SI &si, V3 wo) {
@@ -945,9 +1049,14 @@ DEV V3 bsdf_eval(SceneRef sc, int b, const SI &si, V3 wo) {
         Frame pf = bump_frame(sc, B, si);
         V3 pwi = pf.to_local(si.wi), pwo = pf.to_local(wo);
         if (!(wo.z * pwo.z > 0.f)) return V3(0.f);
-        return leaf_eval<EXT>(sc, tab(sc.bsdfs, B.nested, sc.one_shape), si, pwi, pwo) * shadow_terminator(pf.n, wo);
+        return leaf_eval<EXT>(sc, tab(sc.bsdfs, B.nested, sc.one_shape), si, pwi, pwo, B.nested) * shadow_terminator(pf.n, wo);
     }
-    return leaf_eval<EXT>(sc, B, si, si.wi, wo);
+    if constexpr (EXT) {
+        const LeafRef l = leaf_of<true>(sc, b, B, si.wi);
+        if (l.none) return V3(0.f);
+        return leaf_eval<true>(sc, l.B, si, l.wi, V3(wo.x, wo.y, mulsign(wo.z, l.sign)), l.b);
+    } else
+        return leaf_eval<EXT>(sc, B, si, si.wi, wo);
 }
 template <bool EXT = false>
 DEV float bsdf_pdf(SceneRef sc, int b, const SI &si, V3 wo) {
@@ -956,9 +1065,14 @@ DEV float bsdf_pdf(SceneRef sc, int b, const SI &si, V3 wo) {
         Frame pf = bump_frame(sc, B, si);
         V3 pwi = pf.to_local(si.wi), pwo = pf.to_local(wo);
         if (!(wo.z * pwo.z > 0.f)) return 0.f;
-        return leaf_pdf<EXT>(sc, tab(sc.bsdfs, B.nested, sc.one_shape), si, pwi, pwo);
+        return leaf_pdf<EXT>(sc, tab(sc.bsdfs, B.nested, sc.one_shape), si, pwi, pwo, B.nested);
     }
-    return leaf_pdf<EXT>(sc, B, si, si.wi, wo);
+    if constexpr (EXT) {
+        const LeafRef l = leaf_of<true>(sc, b, B, si.wi);
+        if (l.none) return 0.f;
+        return leaf_pdf<true>(sc, l.B, si, l.wi, V3(wo.x, wo.y, mulsign(wo.z, l.sign)), l.b);
+    } else
+        return leaf_pdf<EXT>(sc, B, si, si.wi, wo);
 }
 DEV float bsdf_null_transmission(SceneRef sc, int b) { return tab(sc.bsdfs, b, sc.one_shape).type == LRT_BSDF_NULL ? 1.f : 0.f; }
 

@@ -39,7 +39,7 @@ DEV int aov_bsdf(SceneRef sc, const SI &si) {
 }
 
 // One AOV of one lane (aov.cpp:222-343).  A miss is the zero interaction (aov.cpp:216), so every value is 0 there.
-// EXT: the scene may hold a roughdielectric (the EXT instances)
+// EXT: the scene may hold a roughdielectric, a conductor, a plastic or a twosided (the EXT instances)
 template <bool EXT = false>
 DEV void aov_eval(SceneRef sc, AovSpecPtr A, int type, const SI &si, float v[3]) {
     v[0] = v[1] = v[2] = 0.f;
@@ -50,7 +50,14 @@ DEV void aov_eval(SceneRef sc, AovSpecPtr A, int type, const SI &si, float v[3])
             if (b < 0) break;
             DBsdf B = tab(sc.bsdfs, b, sc.one_shape);
             if (B.type == LRT_BSDF_BUMPMAP) B = sc.bsdfs[B.nested];        // bumpmap.cpp:259: the nested BSDF's, at the unperturbed si
-            if (B.type == LRT_BSDF_DIFFUSE) {                               // diffuse.cpp:181; dielectric / null: eval(wo = +z) * pi = 0 (bsdf.cpp:38-43)
+            if (EXT && B.type == LRT_BSDF_TWOSIDED) {                       // twosided.cpp:284-307: the child of the side that was hit; neither at wi.z = 0 with two children
+                const int c = twosided_child(sc, b, B, si.wi.z);
+                if (c < 0) break;
+                B = sc.bsdfs[c];
+            }
+            // diffuse.cpp:181; plastic.cpp:362-365: its diffuse_reflectance, which DBsdf keeps in the same word (EXT).  dielectric / null /
+            // conductor: the base class's eval(wo = +z) * pi = 0 (bsdf.cpp:38-43)
+            if (B.type == LRT_BSDF_DIFFUSE || (EXT && B.type == LRT_BSDF_PLASTIC)) {
                 const V3 r = tex_eval(sc, B.reflectance, si);
                 v[0] = r.x; v[1] = r.y; v[2] = r.z;
             }

@@ -4,7 +4,7 @@
 // reference's src/core/parser.cpp + Properties + PluginManager instantiation.
 // Supported plugins: integrator {path, volpath, prbvolpath, biovolpath, biovolpath06, aov, moment}; sensor perspective;
 // sampler {independent, ldsampler}; film hdrfilm; rfilter {box,
-// gaussian, tent}; bsdf {diffuse, dielectric, roughdielectric, bumpmap, null}; texture {bitmap,
+// gaussian, tent}; bsdf {diffuse, dielectric, roughdielectric, conductor, plastic, twosided, bumpmap, null}; texture {bitmap,
 // checkerboard}; medium {homogeneous, liver, parenchyma, glissonCapsule} (the
 // bio media carry both the homogeneous parameters that path / volpath /
 // prbvolpath see through the 4-argument sample_interaction() and the element
@@ -380,6 +380,7 @@ struct Loader {
     int make_bsdf(const ObjP &o) {
         auto it = bsdf_ix.find(o.get()); if (it != bsdf_ix.end()) return it->second;
         lrt_bsdf_desc B{}; B.reflectance = B.nested = B.texture = -1; B.eta = 1.f; B.scale = 1.f; B.specular_reflectance = B.specular_transmittance = -1;
+        B.diffuse_reflectance = B.nested_back = -1;
         if (o->type == "diffuse") {
             B.type = LRT_BSDF_DIFFUSE; B.reflectance = texture_or_rgb(*o, "reflectance", .5f);
             if (S.textures[B.reflectance].type == LRT_TEX_BITMAP) fail("unsupported: a bitmap texture as diffuse reflectance (bitmaps are supported as bump-map heights only)");
@@ -396,6 +397,7 @@ struct Loader {
             if (!nb) fail("Exactly one BSDF child object must be specified."); if (!nt) fail("Exactly one Texture child object must be specified.");
             B.nested = make_bsdf(nb); B.texture = make_texture(nt);
             if (S.bsdfs[B.nested].type == LRT_BSDF_BUMPMAP) fail("nested bump maps are not supported");
+            if (S.bsdfs[B.nested].type == LRT_BSDF_TWOSIDED) fail("unsupported: a twosided BSDF nested in a bumpmap (put the bumpmap's leaf under it; a twosided over a bumpmap is not built either)");
         } else if (o->type == "null") B.type = LRT_BSDF_NULL;
         else if (o->type == "roughdielectric") {     // src/bsdfs/roughdielectric.cpp:165-220
             B.type = LRT_BSDF_ROUGHDIELECTRIC;
@@ -421,7 +423,46 @@ struct Loader {
                 B.alpha_u = get_float(*o, "alpha_u", .1f); B.alpha_v = get_float(*o, "alpha_v", .1f);
             } else B.alpha_u = B.alpha_v = get_float(*o, "alpha", .1f);
         }
-        else if (o->type == "twosided") { ObjP nb = child(*o, "bsdf"); if (!nb) fail("twosided: missing nested bsdf"); fail("twosided BSDFs are not supported"); }
+        else if (o->type == "conductor") {           // src/bsdfs/conductor.cpp:224-239
+            B.type = LRT_BSDF_CONDUCTOR;
+            B.specular_reflectance = texture_or_rgb(*o, "specular_reflectance", 1.f);
+            if (S.textures[B.specular_reflectance].type == LRT_TEX_BITMAP) fail("unsupported: a bitmap texture as conductor specular_reflectance (bitmaps are supported as bump-map heights only)");
+            for (const char *k : { "eta", "k" })
+                if (child(*o, "texture", k)) fail("unsupported: a texture as conductor \"" + std::string(k) + "\" (a textured index of refraction is not built)");
+            const std::string material = get_string(*o, "material", "none");
+            if (has(*o, "eta") || material == "none") {
+                get_rgb(*o, "eta", 0.f, B.eta_rgb); get_rgb(*o, "k", 1.f, B.k_rgb);
+                if (material != "none") fail("Should specify either (eta, k) or material, not both.");
+                for (int c = 0; c < 3; ++c) if (B.eta_rgb[c] == 0.f && B.k_rgb[c] == 0.f) fail("conductor with eta = k = 0 in a channel (no index of refraction: its Fresnel term is 0 / 0 at normal incidence; the plugin's default is eta = 0, k = 1)");
+            } else fail("unsupported: conductor material \"" + material + "\" (the measured .spd tables and their conversion to RGB are not built; give eta and k)");
+        }
+        else if (o->type == "plastic") {             // src/bsdfs/plastic.cpp:157-182
+            B.type = LRT_BSDF_PLASTIC;
+            float ii = lookup_ior(*o, "int_ior", "polypropylene"), ei = lookup_ior(*o, "ext_ior", "air");
+            if (ii < 0 || ei < 0) fail("The interior and exterior indices of refraction must be positive!");
+            B.eta = ii / ei;
+            B.diffuse_reflectance = texture_or_rgb(*o, "diffuse_reflectance", .5f);
+            if (has(*o, "specular_reflectance") || child(*o, "texture", "specular_reflectance")) B.specular_reflectance = texture_or_rgb(*o, "specular_reflectance", 1.f);
+            for (int t : { B.diffuse_reflectance, B.specular_reflectance })
+                if (t >= 0 && S.textures[t].type == LRT_TEX_BITMAP) fail("unsupported: a bitmap texture as plastic diffuse_reflectance / specular_reflectance (bitmaps are supported as bump-map heights only)");
+            B.nonlinear = get_bool(*o, "nonlinear", false) ? 1 : 0;
+        }
+        else if (o->type == "twosided") {            // src/bsdfs/twosided.cpp:74-104
+            B.type = LRT_BSDF_TWOSIDED;
+            int n = 0, ch[2] = { -1, -1 };
+            for (auto &c : o->children) if (c.second->tag == "bsdf") {
+                if (n >= 2) fail("At most two nested BSDFs can be specified!");
+                if (c.second->type == "bumpmap" || c.second->type == "twosided") fail("unsupported: a " + c.second->type + " nested in a twosided BSDF (its children are diffuse, conductor or plastic)");
+                ch[n++] = make_bsdf(c.second);
+            }
+            if (n == 0) fail("A nested one-sided material is required!");
+            if (get_bool(*o, "allow_transmission", false)) fail("unsupported: twosided with allow_transmission = true");
+            for (int k = 0; k < n; ++k) {
+                const int t = S.bsdfs[ch[k]].type;
+                if (t == LRT_BSDF_DIELECTRIC || t == LRT_BSDF_ROUGHDIELECTRIC || t == LRT_BSDF_NULL) fail("Only materials without a transmission component can be nested!");
+            }
+            B.nested = ch[0]; B.nested_back = n == 2 ? ch[1] : ch[0];
+        }
         else fail("unsupported bsdf type \"" + o->type + "\"");
         S.bsdfs.push_back(B); int ix = (int) S.bsdfs.size() - 1; bsdf_ix[o.get()] = ix; return ix;
     }
@@ -1003,11 +1044,18 @@ struct Loader {
             const lrt_bsdf_desc &B = S.bsdfs[sh.bsdf];
             rough = rough || B.type == LRT_BSDF_ROUGHDIELECTRIC || (B.type == LRT_BSDF_BUMPMAP && S.bsdfs[B.nested].type == LRT_BSDF_ROUGHDIELECTRIC);
         }
+        bool smooth = false;                    // a conductor / plastic / twosided on a shape, nested or not: the EXT instances as well (scene_prep.cpp)
+        for (auto &sh : S.shapes) if (sh.bsdf >= 0) {
+            const lrt_bsdf_desc *B = &S.bsdfs[sh.bsdf];
+            if (B->type == LRT_BSDF_BUMPMAP) B = &S.bsdfs[B->nested];
+            smooth = smooth || B->type == LRT_BSDF_CONDUCTOR || B->type == LRT_BSDF_PLASTIC || B->type == LRT_BSDF_TWOSIDED;
+        }
         bool prb = S.desc.integrator.type == LRT_INTEGRATOR_PRBVOLPATH;
         for (int k = 0; S.has_aov && k < S.aov.n_integrators; ++k) prb = prb || S.aov.integrators[k].type == LRT_INTEGRATOR_PRBVOLPATH;
         if (ext && prb) fail("unsupported: prbvolpath on a scene with sphere shapes, point emitters or area emitters on meshes");
         if (delta_em && prb) fail("unsupported: prbvolpath on a scene with a spot or directional emitter (no adjoint is built for them)");
         if (rough && prb) fail("unsupported: prbvolpath on a scene with a roughdielectric BSDF (no adjoint is built for it)");
+        if (smooth && prb) fail("unsupported: prbvolpath on a scene with a conductor / plastic / twosided BSDF (no adjoint is built for them)");
         if (phase_ext && prb) fail("unsupported: prbvolpath on a scene with a tabulated / Rayleigh / blended phase function (no adjoint is built for them)");
         S.fix_pointers();
     }

@@ -1,6 +1,7 @@
 // Host half of the scene upload (scene_prep.h): the device image of an lrt_scene_desc as host arrays, the media tables, the resolved
 // render options, the tile lists and the proof predicate of the 64-byte records.  Plain host arithmetic, no HIP runtime call.
 #include "scene_prep.h"
+#include <functional>
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
@@ -381,6 +382,54 @@ void build_cone_table(const lrt_scene_desc &d, std::vector<uint16_t> &out) {
     }
 }
 
+// include/mitsuba/render/fresnel.h:327-355, in float32 with the fused multiply-adds the reference's dr::fmadd / dr::horner are
+static float fresnel_diffuse_reflectance(float eta) {
+    const float inv_eta = 1.f / eta;
+    const float approx_1 = fmaf(0.0636f, inv_eta, fmaf(eta, fmaf(eta, -1.4399f, 0.7099f), 0.6681f));
+    float approx_2 = -1.36881f;
+    for (float c : { 4.98554f, -7.80989f, 6.75335f, -3.4793f, 0.919317f }) approx_2 = fmaf(approx_2, inv_eta, c);
+    return eta < 1.f ? approx_1 : approx_2;
+}
+PlasticConstants plastic_constants(float eta, float d_mean, float s_mean) {      // plastic.cpp:192-207
+    PlasticConstants c;
+    c.inv_eta_2 = 1.f / (eta * eta);
+    c.fdr_int = fresnel_diffuse_reflectance(1.f / eta);
+    c.fdr_ext = fresnel_diffuse_reflectance(eta);
+    c.specular_sampling_weight = s_mean / (d_mean + s_mean);
+    return c;
+}
+float texture_mean(const lrt_texture_desc &T) {
+    auto mean3 = [](const float *c) { return (c[0] + c[1] + c[2]) * (1.f / 3.f); };       // src/spectra/srgb.cpp:117-122 (dr::mean of the colour: the sum times 1 / 3, as mean3 of dmath.h)
+    if (T.type == LRT_TEX_CHECKERBOARD) return .5f * (mean3(T.color0) + mean3(T.color1));   // checkerboard.cpp:112-114
+    return mean3(T.color0);
+}
+void validate_smooth_bsdf(const lrt_scene_desc &d, uint32_t i) {
+    const lrt_bsdf_desc &B = d.bsdfs[i];
+    auto bad = [](const std::string &m) { throw std::runtime_error(m); };
+    auto tex = [&](int32_t t, bool required, const char *what) {
+        if (t < (required ? 0 : -1) || t >= (int32_t) d.n_textures) bad(std::string(what) + " references an invalid texture");
+        if (t >= 0 && d.textures[t].type == LRT_TEX_BITMAP) bad(std::string("unsupported: a bitmap texture as ") + what + " (bitmaps are supported as bump-map heights only)");
+    };
+    if (B.type == LRT_BSDF_CONDUCTOR) {
+        tex(B.specular_reflectance, true, "conductor specular_reflectance");
+        for (int k = 0; k < 3; ++k) if (!std::isfinite(B.eta_rgb[k]) || !std::isfinite(B.k_rgb[k])) bad("conductor with an index of refraction that is not finite");
+        // eta = k = 0 is no index of refraction: fresnel_conductor is 0 / 0 at normal incidence (term_3 = term_4 = 0, fresnel.h:111-114).  A zero-filled
+        // tail of the description lands here, so a conductor has to state its index (the plugin's default is 0 + 1i).
+        for (int k = 0; k < 3; ++k) if (B.eta_rgb[k] == 0.f && B.k_rgb[k] == 0.f) bad("conductor with eta = k = 0 in a channel (no index of refraction: its Fresnel term is 0 / 0 at normal incidence; the plugin's default is eta = 0, k = 1)");
+    } else if (B.type == LRT_BSDF_PLASTIC) {
+        if (!(B.eta > 0.f) || !std::isfinite(B.eta)) bad("The interior and exterior indices of refraction must be positive!");
+        tex(B.diffuse_reflectance, true, "plastic diffuse_reflectance"); tex(B.specular_reflectance, false, "plastic specular_reflectance");
+    } else if (B.type == LRT_BSDF_TWOSIDED) {
+        if (B.nested < 0) bad("A nested one-sided material is required!");
+        for (int32_t c : { B.nested, B.nested_back < 0 ? B.nested : B.nested_back }) {      // (nested_back = -1: one child)
+            if (c < 0 || (uint32_t) c >= d.n_bsdfs) bad("twosided references an invalid nested bsdf");
+            const int t = d.bsdfs[c].type;
+            if (t == LRT_BSDF_DIELECTRIC || t == LRT_BSDF_ROUGHDIELECTRIC || t == LRT_BSDF_NULL) bad("Only materials without a transmission component can be nested!");
+            if (t == LRT_BSDF_BUMPMAP || t == LRT_BSDF_TWOSIDED) bad(std::string("unsupported: a ") + (t == LRT_BSDF_BUMPMAP ? "bumpmap" : "twosided") + " nested in a twosided BSDF (its children are diffuse, conductor or plastic)");
+        }
+    }
+}
+
 void prepare_geometry(const lrt_scene_desc &d, const PrepOptions &opt, PreparedScene &P) {
     DScene &sc = P.sc;
     memset(&sc, 0, sizeof(sc));                          // the record is uploaded byte for byte: its padding is cleared too
@@ -418,6 +467,14 @@ void prepare_geometry(const lrt_scene_desc &d, const PrepOptions &opt, PreparedS
         if (b < 0 || (uint32_t) b >= d.n_bsdfs) continue;
         const lrt_bsdf_desc &B = d.bsdfs[b];
         if (B.type == LRT_BSDF_ROUGHDIELECTRIC || (B.type == LRT_BSDF_BUMPMAP && B.nested >= 0 && (uint32_t) B.nested < d.n_bsdfs && d.bsdfs[B.nested].type == LRT_BSDF_ROUGHDIELECTRIC)) P.ext = true;
+    }
+    // So does a conductor, a plastic or a twosided on a shape, alone or under a bumpmap (again, an unreferenced one changes nothing)
+    for (uint32_t i = 0; i < d.n_shapes; ++i) {
+        const int32_t b = d.shapes[i].bsdf;
+        if (b < 0 || (uint32_t) b >= d.n_bsdfs) continue;
+        const lrt_bsdf_desc *B = &d.bsdfs[b];
+        if (B->type == LRT_BSDF_BUMPMAP && B->nested >= 0 && (uint32_t) B->nested < d.n_bsdfs) B = &d.bsdfs[B->nested];
+        if (B->type == LRT_BSDF_CONDUCTOR || B->type == LRT_BSDF_PLASTIC || B->type == LRT_BSDF_TWOSIDED) P.ext = P.smooth_bsdf = true;
     }
     // So does a tabulated / Rayleigh / blended phase function on a medium that a shape or the sensor references (again, an unreferenced one changes nothing)
     {
@@ -504,15 +561,25 @@ void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedSc
     }
     // ---- BSDFs
     std::vector<DBsdf> &bsdfs = P.bsdfs; bsdfs.resize(d.n_bsdfs); sc.has_null_bsdf = 0;
-    auto leaf_flags = [](int type) { return (type == LRT_BSDF_DIFFUSE || type == LRT_BSDF_ROUGHDIELECTRIC) ? PREP_F_SMOOTH : type == LRT_BSDF_DIELECTRIC ? PREP_F_DELTA : PREP_F_NULL; };   // (roughdielectric: both lobes are glossy)
+    // (roughdielectric: both lobes are glossy; plastic: a delta coat over a diffuse base, plastic.cpp:177-179; twosided: its children's, twosided.cpp:90-100)
+    std::function<int(uint32_t)> leaf_flags = [&](uint32_t b) -> int {
+        const lrt_bsdf_desc &B = d.bsdfs[b];
+        if (B.type == LRT_BSDF_TWOSIDED) { const int32_t back = B.nested_back < 0 ? B.nested : B.nested_back; return leaf_flags((uint32_t) B.nested) | leaf_flags((uint32_t) back); }   // (validated below: the children are leaves)
+        return (B.type == LRT_BSDF_DIFFUSE || B.type == LRT_BSDF_ROUGHDIELECTRIC) ? PREP_F_SMOOTH : (B.type == LRT_BSDF_DIELECTRIC || B.type == LRT_BSDF_CONDUCTOR) ? PREP_F_DELTA
+             : B.type == LRT_BSDF_PLASTIC ? (PREP_F_DELTA | PREP_F_SMOOTH) : PREP_F_NULL;
+    };
+    bool any_smooth_bsdf = false;
+    for (uint32_t i = 0; i < d.n_bsdfs; ++i) if (d.bsdfs[i].type == LRT_BSDF_CONDUCTOR || d.bsdfs[i].type == LRT_BSDF_PLASTIC || d.bsdfs[i].type == LRT_BSDF_TWOSIDED) { validate_smooth_bsdf(d, i); any_smooth_bsdf = true; }
+    if (any_smooth_bsdf) P.bsdf_ext.assign(d.n_bsdfs, DBsdfExt{});
     for (uint32_t i = 0; i < d.n_bsdfs; ++i) {
         const lrt_bsdf_desc &B = d.bsdfs[i];
         DBsdf &o = bsdfs[i]; memset(&o, 0, sizeof(o));
         o.type = B.type; o.reflectance = B.reflectance; o.nested = B.nested; o.texture = B.texture; o.eta = B.eta; o.scale = B.scale;
         if (B.type == LRT_BSDF_BUMPMAP) {
             if (B.nested < 0 || (uint32_t) B.nested >= d.n_bsdfs || d.bsdfs[B.nested].type == LRT_BSDF_BUMPMAP) throw std::runtime_error("bumpmap: invalid nested BSDF");
-            bsdfs[i].flags = leaf_flags(d.bsdfs[B.nested].type);
-        } else bsdfs[i].flags = leaf_flags(B.type);
+            if (d.bsdfs[B.nested].type == LRT_BSDF_TWOSIDED) throw std::runtime_error("unsupported: a twosided BSDF nested in a bumpmap");
+            bsdfs[i].flags = leaf_flags((uint32_t) B.nested);
+        } else bsdfs[i].flags = leaf_flags(i);
         if (B.type == LRT_BSDF_DIFFUSE && (B.reflectance < 0 || (uint32_t) B.reflectance >= d.n_textures || d.textures[B.reflectance].type == LRT_TEX_BITMAP))
             throw std::runtime_error("unsupported: a bitmap texture as diffuse reflectance (bitmaps are supported as bump-map heights only)");
         if (B.type == LRT_BSDF_NULL) sc.has_null_bsdf = 1;
@@ -526,6 +593,20 @@ void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedSc
             bsdfs[i].alpha_u = std::max(B.alpha_u, 1e-4f); bsdfs[i].alpha_v = std::max(B.alpha_v, 1e-4f);      // MicrofacetDistribution::configure (microfacet.h:425-428)
             bsdfs[i].micro = (B.distribution == 1 ? LRT_MICRO_GGX : 0) | (B.sample_visible ? LRT_MICRO_VISIBLE : 0);
         }
+        // conductor / plastic / twosided: what DBsdf has no room for lives in the row of the same index (device_types.h)
+        if (B.type == LRT_BSDF_CONDUCTOR) {
+            DBsdfExt &x = P.bsdf_ext[i];
+            o.specular_reflectance = B.specular_reflectance;
+            for (int k = 0; k < 3; ++k) { x.eta[k] = B.eta_rgb[k]; x.k[k] = B.k_rgb[k]; }
+        }
+        if (B.type == LRT_BSDF_PLASTIC) {
+            DBsdfExt &x = P.bsdf_ext[i];
+            o.reflectance = B.diffuse_reflectance;
+            const PlasticConstants c = plastic_constants(B.eta, texture_mean(d.textures[B.diffuse_reflectance]), B.specular_reflectance >= 0 ? texture_mean(d.textures[B.specular_reflectance]) : 1.f);
+            x.inv_eta_2 = c.inv_eta_2; x.fdr_int = c.fdr_int; x.fdr_ext = c.fdr_ext; x.spec_weight = c.specular_sampling_weight;
+            x.nonlinear = B.nonlinear ? 1 : 0; x.specular_reflectance = B.specular_reflectance;
+        }
+        if (B.type == LRT_BSDF_TWOSIDED) P.bsdf_ext[i].back = B.nested_back < 0 ? B.nested : B.nested_back;
     }
     // ---- bounds (src/render/scene.cpp:49; include/mitsuba/core/bbox.h:343-346; envmap.cpp:337-351)
     DEnv &E = sc.env; memset(&E, 0, sizeof(E)); E.type = -1; E.emitter = -1;

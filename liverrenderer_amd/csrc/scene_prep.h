@@ -33,6 +33,7 @@ struct PreparedScene {
     std::vector<DShape> shapes;
     std::vector<DTexture> textures; std::vector<float> tex_data;
     std::vector<DBsdf> bsdfs;
+    std::vector<DBsdfExt> bsdf_ext;                    // DScene::bsdf_ext, one row per BSDF; empty: the description has no conductor, plastic or twosided
     std::vector<DEmitter> emitters;
     std::vector<DMeshEmitter> mesh_emitters; std::vector<float> mesh_emitter_tab;
     std::vector<DDeltaEmitter> delta_emitters;         // DScene::delta_emitters, one entry per emitter; empty: the scene has no spot or directional emitter
@@ -45,6 +46,7 @@ struct PreparedScene {
     std::vector<uint16_t> cone_tab;                    // build_cone_table's rows, 2 * LRT_CONE_BINS binary16 per face; empty: no table (sc.cone_enabled = 0)
     bool env_interior_positive = false;                // envmap: rows 1..h-2 of the sampling density strictly positive
     bool ext = false, has_area_emitter = false, has_het = false, has_non_bio = false, prb_null = false, use_lds = false;   // DeviceScene's flags of the same names
+    bool smooth_bsdf = false;                          // a conductor / plastic / twosided sits on a shape (it sets `ext` too; prbvolpath names it in its refusal)
     int bvh_leaf = 4;
 };
 // The two halves of prepare_scene, for a caller that has work to start in between (device.hip launches k_build_dist_grid after the first, so that
@@ -90,6 +92,15 @@ void prepare_phases(const lrt_scene_desc &d, std::vector<DPhase> &phases, std::v
 // (0 < beam_width <= cutoff_angle <= 180, cutoff_angle < 90 with a texture) and its texture's index and type.  Throws the text
 // (lrt_scene_from_desc and the preparation share it); `unsupported: ...` for a bitmap texture, the plugin's own text for a uniform one.
 void validate_delta_emitter(const lrt_scene_desc &d, uint32_t i);
+
+// BSDF i of the description, an LRT_BSDF_CONDUCTOR, _PLASTIC or _TWOSIDED: its texture and child indices and what the loader refuses
+// (lrt_scene_from_desc and the preparation share it).  Throws the text: the plugin's own where it has one, `unsupported: ...` for what is not built.
+void validate_smooth_bsdf(const lrt_scene_desc &d, uint32_t i);
+// SmoothPlastic::parameters_changed (src/bsdfs/plastic.cpp:192-207) in float32, as the plugin's scalar constructor computes it
+struct PlasticConstants { float inv_eta_2, fdr_int, fdr_ext, specular_sampling_weight; };
+PlasticConstants plastic_constants(float eta, float d_mean, float s_mean);
+// Texture::mean() of an RGB value or a checkerboard (src/spectra/srgb.cpp:117-122, src/textures/checkerboard.cpp:112-114)
+float texture_mean(const lrt_texture_desc &T);
 
 // spp: samples of ONE pass; spp_total = n_passes * spp (integrator.cpp:176-184,275-293)
 struct ResolvedOpts { int integrator, max_depth, rr_depth, hide_emitters; uint32_t spp, seed, tile_rank, tile_count; uint32_t spp_total = 0, n_passes = 1, pass = 0; };
