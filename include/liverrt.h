@@ -445,6 +445,18 @@ LRT_API lrt_status lrt_phase_probe(lrt_scene *scene, int medium, const float *wi
 LRT_API lrt_status lrt_medium_probe(lrt_scene *scene, int medium, const float *o, const float *d, const float *maxt, const float *sample,
                                     const uint32_t *channel, uint32_t n, float *out, int device);
 
+/* Test hook [v120]: the front and the back end of every lane, one call per lane: the perspective sensor's ray as generate_camera_path asks
+ * for it (csrc/kernels.h camera_ray), the film-to-sample map, a sample's filter footprint (csrc/film.h film_footprint) and the
+ * reconstruction filter (rfilter_eval).  in: 5 floats per lane: [0..1] the adjusted position sample (ax, ay) handed to
+ * PerspectiveCamera::sample_ray, [2..3] a film position (spx, spy) in pixels, [4] a filter argument x.
+ * out: LRT_SENSOR_PROBE_FLOATS floats per lane:
+ *   [0..2] ray origin, [3..5] ray direction, [6] maxt of sample_ray(ax, ay);
+ *   [7..8] fma(spx, scale_x, offset_x), fma(spy, scale_y, offset_y): the film-to-sample map (scale = 1 / crop_size, offset = -crop_offset * scale);
+ *   [9..10] the footprint origin of a sample at (spx, spy) in film pixels, stored as floats, [11..12] relx, rely: the filter argument of the
+ *   footprint's first column and row (cell k has rel + k);  [13] the filter at x;  [14] the footprint's cells per side;  [15] 0. */
+#define LRT_SENSOR_PROBE_FLOATS 16
+LRT_API lrt_status lrt_sensor_probe(lrt_scene *scene, const float *in, uint32_t n, float *out, int device);
+
 /* SoA ray queries (layout mirrors RayHit of src/render/scene_native.inl:135-142).
  * Miss: t = +inf, prim = 0xffffffff.  any_hit: only t (0 on hit, +inf on miss). */
 typedef struct { const float *ox, *oy, *oz, *dx, *dy, *dz, *tmax; } lrt_rays_soa;

@@ -529,6 +529,17 @@ class Scene:
                                               channel.ctypes.data_as(C.POINTER(C.c_uint32)), n, out.ctypes.data_as(FP), int(device)))
         return _lib.medium_probe_fields(out)
 
+    def sensor_probe(self, inputs, device=0):
+        """lrt_sensor_probe (test hook): per lane (inputs: n x 5 = ax, ay, spx, spy, x) the sensor's ray at the adjusted position sample
+        (ax, ay), the film-to-sample map and the filter footprint of a sample at the film position (spx, spy), and the reconstruction filter
+        at x.  Returns a dict of arrays: o, d (n x 3), maxt, adjusted (n x 2), origin (n x 2, int), rel (n x 2), weight, fcount (int), and
+        raw (n x LRT_SENSOR_PROBE_FLOATS, every float as returned)."""
+        a = np.ascontiguousarray(inputs, np.float32).reshape(-1, 5)
+        out = np.zeros((a.shape[0], _lib.SENSOR_PROBE_FLOATS), np.float32)
+        FP = C.POINTER(C.c_float)
+        _lib.check(self._lib.lrt_sensor_probe(self._h, a.ctypes.data_as(FP), a.shape[0], out.ctypes.data_as(FP), int(device)))
+        return _lib.sensor_probe_fields(out)
+
     def bsdf_probe(self, o, d, sample, wo_query, device=0):
         """lrt_bsdf_probe (test hook): per ray (o, d) (n x 3 each) the closest hit without a ray offset, its surface interaction, the hit
         shape's BSDF sampled with sample (n x 3: s1, s2.x, s2.y) as the integrators do, and its eval / pdf at the world direction

@@ -17,6 +17,7 @@ EMITTER = {"area": 0, "envmap": 1, "constant": 2, "point": 3, "spot": 4, "direct
 PROBE_FLOATS = 20      # include/liverrt.h LRT_PROBE_FLOATS (lrt_emitter_probe)
 MEDIUM_PROBE_FLOATS = 22 # include/liverrt.h LRT_MEDIUM_PROBE_FLOATS (lrt_medium_probe)
 PHASE_PROBE_FLOATS = 7 # include/liverrt.h LRT_PHASE_PROBE_FLOATS (lrt_phase_probe)
+SENSOR_PROBE_FLOATS = 16 # include/liverrt.h LRT_SENSOR_PROBE_FLOATS (lrt_sensor_probe)
 BSDF_PROBE_FLOATS = 30 # include/liverrt.h LRT_BSDF_PROBE_FLOATS (lrt_bsdf_probe)
 
 
@@ -228,6 +229,8 @@ def lib():
     L.lrt_phase_probe.restype = C.c_int
     L.lrt_medium_probe.argtypes = [C.c_void_p, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_uint32), C.c_uint32, P(C.c_float), C.c_int]
     L.lrt_medium_probe.restype = C.c_int
+    L.lrt_sensor_probe.argtypes = [C.c_void_p, P(C.c_float), C.c_uint32, P(C.c_float), C.c_int]
+    L.lrt_sensor_probe.restype = C.c_int
     L.lrt_param_set.argtypes = [C.c_void_p, C.c_char_p, P(C.c_float), C.c_int]
     L.lrt_param_get.argtypes = [C.c_void_p, C.c_char_p, P(C.c_float), C.c_int]
     L.lrt_image_read.argtypes = [C.c_char_p, P(C.c_int), P(C.c_int), P(C.c_int), P(P(C.c_float))]
@@ -266,7 +269,7 @@ def lib():
 
 EXPORTED_SYMBOLS = ["lrt_last_error", "lrt_version", "lrt_scene_load_xml", "lrt_scene_load_xml_string", "lrt_scene_from_desc",
                     "lrt_scene_desc_get", "lrt_scene_free", "lrt_render", "lrt_render_multi", "lrt_render_backward_multi", "lrt_math_eval", "lrt_render_stats_get", "lrt_film_develop",
-                    "lrt_render_samples", "lrt_render_backward", "lrt_render_backward_grid", "lrt_trace", "lrt_emitter_probe", "lrt_envmap_probe", "lrt_bsdf_probe", "lrt_phase_probe", "lrt_medium_probe", "lrt_param_set", "lrt_param_get",
+                    "lrt_render_samples", "lrt_render_backward", "lrt_render_backward_grid", "lrt_trace", "lrt_emitter_probe", "lrt_envmap_probe", "lrt_bsdf_probe", "lrt_phase_probe", "lrt_medium_probe", "lrt_sensor_probe", "lrt_param_set", "lrt_param_get",
                     "lrt_image_read", "lrt_image_free", "lrt_image_write_exr", "lrt_image_write_png",
                     "lrt_vae_model_create", "lrt_vae_model_free", "lrt_vae_scatter",
                     "lrt_scene_aov_get", "lrt_aov_channel_name", "lrt_render_aov", "lrt_render_aov_samples", "lrt_image_write_exr_channels",
@@ -285,6 +288,12 @@ def medium_probe_fields(out):
     """The record of lrt_medium_probe / orc_medium_probe (n x LRT_MEDIUM_PROBE_FLOATS) as a dict of arrays"""
     return {"valid": out[:, 0] != 0, "t": out[:, 1], "p": out[:, 2:5], "mint": out[:, 5], "sigma_t": out[:, 6:9], "sigma_s": out[:, 9:12],
             "sigma_n": out[:, 12:15], "combined": out[:, 15:18], "local": out[:, 18:21], "grid": out[:, 21], "raw": out}
+
+
+def sensor_probe_fields(out):
+    """The record of lrt_sensor_probe / orc_sensor_probe (n x LRT_SENSOR_PROBE_FLOATS) as a dict of arrays"""
+    return {"o": out[:, 0:3], "d": out[:, 3:6], "maxt": out[:, 6], "adjusted": out[:, 7:9], "origin": out[:, 9:11].astype("int64"),
+            "rel": out[:, 11:13], "weight": out[:, 13], "fcount": out[:, 14].astype("int64"), "raw": out}
 
 
 def check(status):

@@ -31,7 +31,7 @@ static lrt_status fail(lrt_status st, const std::string &msg) { g_error = msg; r
 extern "C" {
 
 const char *lrt_last_error(void) { return g_error.c_str(); }
-int lrt_version(void) { return 119; }    // 1.19: the conductor, plastic and twosided BSDFs; 1.18: lrt_medium_probe; a singular volume to_world and an empty use_grid_bbox header box are refused; 1.17: spot and directional emitters (lrt_emitter_desc::cutoff_angle / beam_width / texture); 1.16: tabulated / Rayleigh / blended phase functions (lrt_scene_desc.phases), lrt_phase_probe, lrt_math_eval fn 11 (cbrt); 1.15: lrt_render_stats::n_proven (the struct grows by 8 bytes); 1.14: the roughdielectric BSDF, lrt_math_eval fn 9 (erf) / 10 (erfinv); 1.13: lrt_bsdf_probe; 1.12: lrt_render_backward_grid, "<id>.sigma_t.data" in lrt_param_set / lrt_param_get; 1.11: lrt_envmap_probe; 1.10: the moment integrator (lrt_render_moment, lrt_render_moment_samples, lrt_scene_moment_get, lrt_moment_channel_name); 1.9: the guided denoiser (lrt_denoiser_create / lrt_denoise / lrt_denoiser_free), lrt_image_read_named; 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
+int lrt_version(void) { return 120; }    // 1.20: lrt_sensor_probe; a camera to_world with scale factors and a film whose size plus filter radius leaves the footprint key's range are refused; 1.19: the conductor, plastic and twosided BSDFs; 1.18: lrt_medium_probe; a singular volume to_world and an empty use_grid_bbox header box are refused; 1.17: spot and directional emitters (lrt_emitter_desc::cutoff_angle / beam_width / texture); 1.16: tabulated / Rayleigh / blended phase functions (lrt_scene_desc.phases), lrt_phase_probe, lrt_math_eval fn 11 (cbrt); 1.15: lrt_render_stats::n_proven (the struct grows by 8 bytes); 1.14: the roughdielectric BSDF, lrt_math_eval fn 9 (erf) / 10 (erfinv); 1.13: lrt_bsdf_probe; 1.12: lrt_render_backward_grid, "<id>.sigma_t.data" in lrt_param_set / lrt_param_get; 1.11: lrt_envmap_probe; 1.10: the moment integrator (lrt_render_moment, lrt_render_moment_samples, lrt_scene_moment_get, lrt_moment_channel_name); 1.9: the guided denoiser (lrt_denoiser_create / lrt_denoise / lrt_denoiser_free), lrt_image_read_named; 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
 
 static std::vector<std::pair<std::string, std::string>> parse_defines(const char *const *defines, int n) {
     std::vector<std::pair<std::string, std::string>> r;
@@ -149,6 +149,7 @@ static void validate_desc(const lrt_scene_desc &d) {
     if (F.width <= 0 || F.height <= 0 || F.crop_width <= 0 || F.crop_height <= 0 || F.crop_offset_x < 0 || F.crop_offset_y < 0 ||
         F.crop_offset_x + F.crop_width > F.width || F.crop_offset_y + F.crop_height > F.height) bad("Invalid crop window specification!");
     if (F.rfilter < LRT_RFILTER_BOX || F.rfilter > LRT_RFILTER_TENT || (F.rfilter != LRT_RFILTER_BOX && !(F.rfilter_param > 0.f))) bad("invalid reconstruction filter");
+    try { validate_sensor_film(d); } catch (const std::runtime_error &e) { bad(e.what()); }
     if (d.integrator.type < LRT_INTEGRATOR_PATH || d.integrator.type > LRT_INTEGRATOR_VOLPATHMIS) bad("invalid integrator type");
     if (d.integrator.max_depth < -1 || d.integrator.rr_depth <= 0) bad("invalid max_depth / rr_depth");
     if (d.sampler_type > LRT_SAMPLER_LD || d.sample_count == 0) bad("invalid sampler");
@@ -430,6 +431,15 @@ lrt_status lrt_medium_probe(lrt_scene *scene, int medium, const float *o, const 
     LRT_TRY
         ensure_device(scene, device);
         device_medium_probe(scene->dev, medium, o, d, maxt, sample, channel, n, out);
+        return LRT_OK;
+    LRT_CATCH
+}
+
+lrt_status lrt_sensor_probe(lrt_scene *scene, const float *in, uint32_t n, float *out, int device) {
+    if (!scene || ((!in || !out) && n)) return fail(LRT_ERR_INVALID, "lrt_sensor_probe: null argument");
+    LRT_TRY
+        ensure_device(scene, device);
+        device_sensor_probe(scene->dev, in, n, out);
         return LRT_OK;
     LRT_CATCH
 }

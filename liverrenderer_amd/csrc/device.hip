@@ -1131,16 +1131,19 @@ void device_bsdf_probe(DeviceScene *D, const float *o, const float *d, const flo
 // one whose first argument already selects what a lane evaluates.  fn = LRT_MATH_PHASE_PROBE + m (device_phase_probe only; lrt_math_eval
 // refuses it): `y` is the scene record, `x` holds 9 floats per lane (wi, sample, wo_query), `out` takes LRT_PHASE_PROBE_FLOATS per lane
 // for medium m, out2 is not written.  lrt_medium_probe runs here in the same way: fn = LRT_MATH_MEDIUM_PROBE + m (device_medium_probe only),
-// `x` holds 9 floats per lane (o, d, maxt, sample, channel), `out` takes LRT_MEDIUM_PROBE_FLOATS per lane.
+// `x` holds 9 floats per lane (o, d, maxt, sample, channel), `out` takes LRT_MEDIUM_PROBE_FLOATS per lane.  And lrt_sensor_probe:
+// fn = LRT_MATH_SENSOR_PROBE (device_sensor_probe only), `x` holds 5 floats per lane, `out` takes LRT_SENSOR_PROBE_FLOATS per lane.
 #define LRT_MATH_PHASE_PROBE 0x100
+#define LRT_MATH_SENSOR_PROBE 0x20000000
 #define LRT_MATH_MEDIUM_PROBE 0x40000000
 __global__ void k_math_eval(int fn, const float *__restrict__ x, const float *__restrict__ y, uint32_t n, float *__restrict__ out, float *__restrict__ out2) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (fn >= LRT_MATH_PHASE_PROBE) {
         SceneRef sc = *(ScenePtr) (const void *) y;
+        if (fn >= LRT_MATH_MEDIUM_PROBE) { medium_probe_lane(sc, fn - LRT_MATH_MEDIUM_PROBE, x + 9 * (size_t) i, out + (size_t) LRT_MEDIUM_PROBE_FLOATS * i); return; }
+        if (fn >= LRT_MATH_SENSOR_PROBE) { sensor_probe_lane(sc, x + 5 * (size_t) i, out + (size_t) LRT_SENSOR_PROBE_FLOATS * i); return; }
         const float *in = x + 9 * (size_t) i;
-        if (fn >= LRT_MATH_MEDIUM_PROBE) { medium_probe_lane(sc, fn - LRT_MATH_MEDIUM_PROBE, in, out + (size_t) LRT_MEDIUM_PROBE_FLOATS * i); return; }
         phase_probe_lane(sc, fn - LRT_MATH_PHASE_PROBE, in, in + 3, in + 6, out + (size_t) LRT_PHASE_PROBE_FLOATS * i);
         return;
     }
@@ -1208,6 +1211,20 @@ void device_medium_probe(DeviceScene *D, int medium, const float *o, const float
     k_math_eval<<<(n + 255) / 256, 256, 0, st>>>(LRT_MATH_MEDIUM_PROBE + medium, in.p, (const float *) D->d_sc, n, dout.p, nullptr);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * LRT_MEDIUM_PROBE_FLOATS * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Test hook (include/liverrt.h lrt_sensor_probe): sensor_probe_lane (kernels.h) on the scene's device image, through k_math_eval's selector
+// LRT_MATH_SENSOR_PROBE (above)
+void device_sensor_probe(DeviceScene *D, const float *in5, uint32_t n, float *out) {
+    HIP_CHECK(hipSetDevice(D->device));
+    if (!n) return;
+    hipStream_t st = D->stream;
+    DevTmp in, dout((size_t) n * LRT_SENSOR_PROBE_FLOATS);
+    in.upload(in5, (size_t) n * 5, st);
+    k_math_eval<<<(n + 255) / 256, 256, 0, st>>>(LRT_MATH_SENSOR_PROBE, in.p, (const float *) D->d_sc, n, dout.p, nullptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * LRT_SENSOR_PROBE_FLOATS * 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
 }
 

@@ -20,6 +20,7 @@ void device_render_moment_samples(DeviceScene *D, const lrt_scene_desc &d, const
 void device_render_samples(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out, lrt_render_stats &stats);
 void device_trace(DeviceScene *D, const lrt_rays_soa *rays, const lrt_hits_soa *hits, uint32_t n, int any_hit);
 void device_envmap_probe(DeviceScene *D, const float *dir, uint32_t n, float *out);   // test hook: the environment emitter's pdf and radiance at given directions
+void device_sensor_probe(DeviceScene *D, const float *in5, uint32_t n, float *out);   // test hook: the sensor's ray, the film footprint, the reconstruction filter
 void device_medium_probe(DeviceScene *D, int medium, const float *o, const float *d, const float *maxt, const float *sample, const uint32_t *channel, uint32_t n, float *out);   // test hook: free-flight sampling in a medium, the grid lookup
 void device_phase_probe(DeviceScene *D, int medium, const float *wi, const float *sample, const float *wo_query, uint32_t n, float *out);   // test hook: a medium's phase function, sampled and evaluated
 void device_bsdf_probe(DeviceScene *D, const float *o, const float *d, const float *sample, const float *wo_query, uint32_t n, float *out);   // test hook: surface interaction and BSDF at given rays

@@ -12,7 +12,7 @@ template <typename FP> DEV float estrin10(float x, FP c) {
 DEV float rfilter_eval(FilmRef F, float x) {
     if (F.rfilter == LRT_RFILTER_GAUSSIAN) return fmax_(estrin10(sqr(x), F.rf_coeff), 0.f);
     if (F.rfilter == LRT_RFILTER_TENT) return fmax_(0.f, 1.f - __builtin_fabsf(x * F.rf_inv_radius));
-    return (__builtin_fabsf(x) <= 0.5f) ? 1.f : 0.f;
+    return (x >= -0.5f && x < 0.5f) ? 1.f : 0.f;             // src/rfilters/box.cpp:42: half open
 }
 
 // Index of pixel (px, py) (film coordinates, as lane_to_pixel gives them) in the crop window's row-major film

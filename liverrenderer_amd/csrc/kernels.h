@@ -1098,6 +1098,19 @@ DEV void medium_probe_lane(SceneRef sc, int medium, const float *in, float *o) {
     }
 }
 
+// Test hook (lrt_sensor_probe), one lane: camera_ray at the adjusted position sample in[0..1] as generate_camera_path calls it, the
+// film-to-sample map and film_footprint at the film position in[2..3], rfilter_eval at in[4]; the record of include/liverrt.h.
+// (k_math_eval in device.hip runs it under its selector LRT_MATH_SENSOR_PROBE: the hook adds no kernel symbol.)
+DEV void sensor_probe_lane(SceneRef sc, const float *in, float *o) {
+    const Ray ray = camera_ray(sc, in[0], in[1]);
+    const float spx = in[2], spy = in[3];
+    const FilmFootprint fp = film_footprint(sc.film, 0, 0, spx, spy);            // (float) 0 + spx is spx
+    o[0] = ray.o.x; o[1] = ray.o.y; o[2] = ray.o.z; o[3] = ray.d.x; o[4] = ray.d.y; o[5] = ray.d.z; o[6] = ray.maxt;
+    o[7] = fma_(spx, sc.film.scale_x, sc.film.offset_x); o[8] = fma_(spy, sc.film.scale_y, sc.film.offset_y);
+    o[9] = (float) fp.pix; o[10] = (float) fp.piy; o[11] = fp.relx; o[12] = fp.rely;
+    o[13] = rfilter_eval(sc.film, in[4]); o[14] = (float) sc.film.fcount; o[15] = 0.f;
+}
+
 // Test hook (lrt_bsdf_probe): the surface code at a chosen ray, one per lane: a closest-hit query through the EXT tracer (spheres count),
 // no ray offset; the surface interaction; bsdf_sample with the lane's (s1, s2x, s2y) as path_iteration calls it; bsdf_eval and bsdf_pdf
 // at the world direction woq, brought into the shading frame as the integrators bring an emitter sample's direction.

@@ -865,6 +865,7 @@ struct Loader {
         if (result <= 0.0 || result >= 180.0) fail("The horizontal field of view must be in the range [0, 180]!");
         C.fov_x = (float) result;
         to_float(get_xform(*o, "to_world"), C.to_world);
+        validate_sensor_film(S.desc);                       // perspective.cpp:144-145 (has_scale); the footprint key's range
         C.medium = -1;
         for (auto &c : o->children) if (c.second->tag == "medium") C.medium = make_medium(c.second);
     }

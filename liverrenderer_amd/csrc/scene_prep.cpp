@@ -70,6 +70,22 @@ static void build_camera(const lrt_scene_desc &d, DCamera &cam, DFilm &film) {
     film.fn = (int) ceilf(film.rf_radius - .5f); film.fcount = 2 * film.fn + 1;
 }
 
+void validate_sensor_film(const lrt_scene_desc &d) {
+    const float *m = d.sensor.to_world;
+    for (int i = 0; i < 3; ++i) for (int j = i; j < 3; ++j) {            // transform.h:242-254, float32 as the plugin's scalar transform
+        float sum = 0.f;
+        for (int k = 0; k < 3; ++k) sum += m[4 * i + k] * m[4 * j + k];
+        if (!(std::fabs(sum - (i == j ? 1.f : 0.f)) <= 1e-3f)) throw std::runtime_error("Scale factors in the camera-to-world transformation are not allowed!");
+    }
+    const lrt_film_desc &F = d.film;
+    if (F.rfilter == LRT_RFILTER_BOX) return;
+    // FilmFootprint::key(): origins lie in [-fn, size - fn], each packed as (coordinate + 0x4000) in 16 bits
+    const float radius = F.rfilter == LRT_RFILTER_GAUSSIAN ? 4.f * F.rfilter_param : F.rfilter_param;
+    if (!(radius <= 16384.f) || std::max(F.width, F.height) > 0xbfff)
+        throw std::runtime_error("film footprint out of range: a gaussian or tent filter needs a radius of at most 16384 pixels and a film of at most 49151 pixels per side (radius " +
+                                 std::to_string(radius) + ", film " + std::to_string(F.width) + " x " + std::to_string(F.height) + ")");
+}
+
 static void inverse3(const float *m16, float *out9) {    // double-precision inverse of the linear part
     double m[3][3]; for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) m[i][j] = m16[4 * i + j];
     double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) + m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);

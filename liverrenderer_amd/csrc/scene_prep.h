@@ -93,6 +93,12 @@ void prepare_phases(const lrt_scene_desc &d, std::vector<DPhase> &phases, std::v
 // (lrt_scene_from_desc and the preparation share it); `unsupported: ...` for a bitmap texture, the plugin's own text for a uniform one.
 void validate_delta_emitter(const lrt_scene_desc &d, uint32_t i);
 
+// The sensor's to_world and the film's extent (the XML loader and lrt_scene_from_desc share it).  Throws the plugin's text for a
+// camera-to-world transform with scale factors (src/sensors/perspective.cpp:144-145; Transform::has_scale,
+// include/mitsuba/core/transform.h:242-254: |M M^T - I| > 1e-3 in an entry of the linear part, so a mirrored orthonormal frame passes),
+// and refuses by name a wide-filter film whose size plus footprint leaves what FilmFootprint::key() (film.h) packs into 16 bits per axis.
+void validate_sensor_film(const lrt_scene_desc &d);
+
 // BSDF i of the description, an LRT_BSDF_CONDUCTOR, _PLASTIC or _TWOSIDED: its texture and child indices and what the loader refuses
 // (lrt_scene_from_desc and the preparation share it).  Throws the text: the plugin's own where it has one, `unsupported: ...` for what is not built.
 void validate_smooth_bsdf(const lrt_scene_desc &d, uint32_t i);

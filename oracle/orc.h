@@ -96,6 +96,10 @@ int   orc_medium_probe(orc_scene *s, int medium, const float *o, const float *d,
 void  orc_envmap_sample(orc_scene *s, float u1, float u2, float ref[3], float d[3], float *pdf, float rgb[3]);
 float orc_envmap_pdf(orc_scene *s, const float d[3]);
 void  orc_envmap_eval(orc_scene *s, const float d[3], float rgb[3]);
+/* lrt_sensor_probe on the oracle: 5 floats in, LRT_SENSOR_PROBE_FLOATS floats out per lane, the layout of include/liverrt.h */
+void  orc_sensor_probe(orc_scene *s, const float *in, uint32_t n, float *out);
+/* lrt_film_develop on the oracle: any raw film of the scene's size */
+void  orc_film_develop(orc_scene *s, const float *film_raw, float *image);
 float orc_rfilter_eval(orc_scene *s, float x);
 void  orc_bio_sample_interaction(orc_scene *s, int medium, const float o[3], const float d[3], float maxt, float sample,
                                  uint32_t channel, float depth, int jit, float out[9]);

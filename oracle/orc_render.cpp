@@ -1287,7 +1287,9 @@ static void film_put(const Scene &S, float *film, const SampleOut &s) {
     int n = (int) ceilf(S.rf_radius - .5f), count = 2 * n + 1;
     int pix = (int) floorf(s.px) - n, piy = (int) floorf(s.py) - n;
     float relx = (float) pix + .5f - s.px, rely = (float) piy + .5f - s.py;
-    float wx[16], wy[16];
+    static thread_local std::vector<float> wbuf;            /* sized by the footprint: a Gaussian of stddev 2 has 17 cells per side */
+    if (wbuf.size() < 2 * (size_t) count) wbuf.resize(2 * (size_t) count);
+    float *wx = wbuf.data(), *wy = wx + count;
     for (int i = 0; i < count; ++i) { wx[i] = S.rfilter_eval(relx); wy[i] = S.rfilter_eval(rely); relx += 1.f; rely += 1.f; }
     for (int ys = 0; ys < count; ++ys) {
         int y = piy - F.crop_offset_y + ys;
@@ -1553,6 +1555,24 @@ extern "C" int orc_medium_probe(orc_scene *s, int medium, const float *o, const 
     }
     return 0;
 }
+/* The oracle's side of lrt_sensor_probe (include/liverrt.h): sample_ray at (ax, ay), render_lane's film-to-sample map and film_put's
+   footprint arithmetic at (spx, spy), rfilter_eval at x; 5 floats in, LRT_SENSOR_PROBE_FLOATS out per lane. */
+extern "C" void orc_sensor_probe(orc_scene *s, const float *in, uint32_t n, float *out) {
+    const Scene &S = s->s; const lrt_film_desc &F = S.d.film;
+    const float sclx = 1.f / (float) F.crop_width, scly = 1.f / (float) F.crop_height;
+    const float offx = -(float) F.crop_offset_x * sclx, offy = -(float) F.crop_offset_y * scly;
+    const int fn = (int) ceilf(S.rf_radius - .5f), count = 2 * fn + 1;
+    for (uint32_t i = 0; i < n; ++i) {
+        const float *p = in + 5 * (size_t) i; float *q = out + (size_t) LRT_SENSOR_PROBE_FLOATS * i;
+        const Ray r = sample_ray(S, p[0], p[1]);
+        const float spx = p[2], spy = p[3];
+        const int pix = (int) floorf(spx) - fn, piy = (int) floorf(spy) - fn;
+        q[0] = r.o.x; q[1] = r.o.y; q[2] = r.o.z; q[3] = r.d.x; q[4] = r.d.y; q[5] = r.d.z; q[6] = r.maxt;
+        q[7] = fmaf(spx, sclx, offx); q[8] = fmaf(spy, scly, offy);
+        q[9] = (float) pix; q[10] = (float) piy; q[11] = (float) pix + .5f - spx; q[12] = (float) piy + .5f - spy;
+        q[13] = S.rfilter_eval(p[4]); q[14] = (float) count; q[15] = 0.f;
+    }
+}
 extern "C" void orc_envmap_sample(orc_scene *s, float u1, float u2, float ref[3], float d[3], float *pdf, float rgb[3]) {
     DirSample ds; V3 w = sample_emitter_direction(s->s, V3(ref[0], ref[1], ref[2]), u1, u2, &ds);
     d[0] = ds.d.x; d[1] = ds.d.y; d[2] = ds.d.z; *pdf = ds.pdf; rgb[0] = w.x; rgb[1] = w.y; rgb[2] = w.z;
@@ -1564,6 +1584,8 @@ extern "C" float orc_envmap_pdf(orc_scene *s, const float d[3]) {
 extern "C" void orc_envmap_eval(orc_scene *s, const float d[3], float rgb[3]) {
     V3 v = emitter_eval_env(s->s, V3(d[0], d[1], d[2])); rgb[0] = v.x; rgb[1] = v.y; rgb[2] = v.z;
 }
+/* film_develop on any raw film of the scene's size (lrt_film_develop on the oracle) */
+extern "C" void orc_film_develop(orc_scene *s, const float *film_raw, float *image) { film_develop(s->s, film_raw, image); }
 extern "C" float orc_rfilter_eval(orc_scene *s, float x) { return s->s.rfilter_eval(x); }
 /* bio media: out = { t, transmittance rgb, p xyz, bio type, candidate distance } of the 5-argument sample_interaction */
 extern "C" void orc_bio_sample_interaction(orc_scene *s, int medium, const float o[3], const float d[3], float maxt, float sample,

@@ -401,7 +401,7 @@ float Scene::rfilter_eval(float x) const {
     switch (d.film.rfilter) {
         case LRT_RFILTER_GAUSSIAN: return fmaxf(estrin10(sqr(x), rf_coeff), 0.f);
         case LRT_RFILTER_TENT: return fmaxf(0.f, 1.f - fabsf(x * rf_inv_radius));
-        default: return (fabsf(x) <= 0.5f) ? 1.f : 0.f;
+        default: return (x >= -0.5f && x < 0.5f) ? 1.f : 0.f;          /* src/rfilters/box.cpp:42: half open */
     }
 }
 

@@ -78,6 +78,10 @@ def lib():
     L.orc_bsdf_probe.argtypes = [C.c_void_p, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), C.c_uint32, P(C.c_float)]
     L.orc_bsdf_probe.restype = None
     L.orc_medium_probe.argtypes = [C.c_void_p, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_uint32), C.c_uint32, P(C.c_float)]
+    L.orc_sensor_probe.argtypes = [C.c_void_p, P(C.c_float), C.c_uint32, P(C.c_float)]
+    L.orc_sensor_probe.restype = None
+    L.orc_film_develop.argtypes = [C.c_void_p, P(C.c_float), P(C.c_float)]
+    L.orc_film_develop.restype = None
     L.orc_rfilter_eval.argtypes = [C.c_void_p, C.c_float]
     L.orc_rfilter_eval.restype = C.c_float
     L.orc_sample_ray.argtypes = [C.c_void_p, C.c_float, C.c_float, P(C.c_float), P(C.c_float), P(C.c_float)]
@@ -212,6 +216,21 @@ class OrcScene:
         if self._L.orc_medium_probe(self._h, int(medium), _fp(o), _fp(d), _fp(maxt), _fp(sample), channel.ctypes.data_as(C.POINTER(C.c_uint32)), n, _fp(out)) != 0:
             raise RuntimeError(self._L.orc_last_error().decode())
         return _lib.medium_probe_fields(out)
+
+    def sensor_probe(self, inputs):
+        """orc_sensor_probe: the oracle's twin of Scene.sensor_probe, the same dict of arrays"""
+        a = np.ascontiguousarray(inputs, np.float32).reshape(-1, 5)
+        out = np.zeros((a.shape[0], _lib.SENSOR_PROBE_FLOATS), np.float32)
+        self._L.orc_sensor_probe(self._h, _fp(a), a.shape[0], _fp(out))
+        return _lib.sensor_probe_fields(out)
+
+    def develop(self, film_raw):
+        """orc_film_develop: the oracle's twin of Scene.develop"""
+        h, w, c = self.film_shape
+        raw = np.ascontiguousarray(film_raw, np.float32).reshape(h, w, self.raw_channels)
+        img = np.empty((h, w, c), np.float32)
+        self._L.orc_film_develop(self._h, _fp(raw), _fp(img))
+        return img
 
     def envmap_sample_n(self, samples, ref=(0, 0, 0)):
         """envmap_sample at n samples (n, 2): directions (n, 3), pdfs (n,), weights (n, 3)"""

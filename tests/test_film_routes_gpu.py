@@ -5,7 +5,8 @@ Routes: colour (lrt_render: finish_paths_wave for the box filter, k_splat_lanes 
 3-wide and a 1-wide AOV (k_aov), and the PRB adjoint, whose weight film (k_splat_lanes<true>) and footprint loop (lane_delta_L) show in
 the gradients of test_prb_closed_form.case_filter's scene.
 Filters: box, tent radius 1 (3 x 3 cells), the default Gaussian (5 x 5) and a Gaussian of stddev 1: 9 x 9 = 81 cells, two chunks of the
-walk and wider than the film, so that every footprint is cut by the bounds test.
+walk and wider than the film, so that every footprint is cut by the bounds test; and (colour, moment) a Gaussian of stddev 2: 17 x 17 = 289
+cells, five chunks, far wider than the film.
 Switches: pixel_format rgb / rgba, a 5 x 3 crop window at (2, 1), tile shards 0 / 2 and 1 / 2 summed, samples_per_pass = 1 (three
 passes), 4 samples per pixel.  Each switch appears with each route that has it.
 
@@ -35,8 +36,8 @@ pytestmark = pytest.mark.gpu
 W, H, W_TILES = 9, 5, 33
 CROP = dict(crop_offset_x=2, crop_offset_y=1, crop_width=5, crop_height=3)
 FILTERS = {"box": {"type": "box"}, "tent": {"type": "tent", "radius": 1.0}, "gaussian": {"type": "gaussian"},
-           "gaussian1": {"type": "gaussian", "stddev": 1.0}}
-FOOTPRINT = {"box": 1, "tent": 3, "gaussian": 5, "gaussian1": 9}
+           "gaussian1": {"type": "gaussian", "stddev": 1.0}, "gaussian2": {"type": "gaussian", "stddev": 2.0}}
+FOOTPRINT = {"box": 1, "tent": 3, "gaussian": 5, "gaussian1": 9, "gaussian2": 17}
 XYZ = np.array([[0.412453, 0.357580, 0.180423], [0.212671, 0.715160, 0.072169], [0.019334, 0.119193, 0.950227]])
 
 
@@ -107,7 +108,7 @@ def assert_box_weight(raw, wi, c):
 
 # ------------------------------------------------------------------------------------------------------------ colour
 @pytest.mark.parametrize("c", [case("box"), case("box", "rgba", tiles=True), case("tent", "rgba", crop=True), case("gaussian", tiles=True),
-                               case("gaussian", spp=4), case("gaussian1", "rgba"), case("gaussian1", spass=1)])
+                               case("gaussian", spp=4), case("gaussian1", "rgba"), case("gaussian1", spass=1), case("gaussian2", "rgba")])
 def test_colour_film(mi, orc, c):
     sc = cornell(mi, c)
     raw = render_raw(sc, c)
@@ -119,7 +120,7 @@ def test_colour_film(mi, orc, c):
 
 # ------------------------------------------------------------------------------------------------------------ moment
 @pytest.mark.parametrize("c", [case("box", "rgba", crop=True), case("tent", tiles=True), case("gaussian", "rgba", spp=4), case("gaussian1"),
-                               case("gaussian1", "rgba", spass=1)])
+                               case("gaussian1", "rgba", spass=1), case("gaussian2")])
 def test_moment_film(mi, orc, c):
     from test_moment_gpu import oracle_jitter
     sc = cornell(mi, c, lambda inner: {"type": "moment", "img": inner})
