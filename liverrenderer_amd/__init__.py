@@ -475,41 +475,39 @@ class Scene:
         _lib.check(self._lib.lrt_trace(self._h, C.byref(rays), C.byref(hits), n, int(any_hit)))
         return t, u, v, prim
 
+    def _probe(self, name, inputs, out_width, alloc=np.empty, medium=None, device=0):
+        """One call of the test hook lrt_<name>.  inputs: (argument name, array, floats per lane, dtype) in the C function's order;
+        returns the raw n x out_width block, allocated with `alloc`."""
+        cols = [np.ascontiguousarray(a, dtype=dt).reshape(-1, w) for _, a, w, dt in inputs]
+        n = cols[0].shape[0]
+        if any(c.shape[0] != n for c in cols):
+            names = [i[0] for i in inputs]
+            raise ValueError("%s: %s and %s must have the same number of rows" % (name, ", ".join(names[:-1]), names[-1]))
+        out = alloc((n, out_width), dtype=np.float32)
+        ptr = lambda a: a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))
+        _lib.check(getattr(self._lib, "lrt_" + name)(self._h, *([] if medium is None else [int(medium)]), *map(ptr, cols), n, ptr(out), int(device)))
+        return out
+
     def emitter_probe(self, ref_p, sample, device=0):
         """lrt_emitter_probe (test hook): the device's Scene::sample_emitter_direction at ref_p (n x 3) with sample (n x 2), then a ray
         query along the sampled direction and the integrators' emitter pdf / emission at its hit.  Returns a dict of arrays:
         p, n, d (n x 3), dist, pdf, weight (n x 3), emitter (int), hit_shape (int, -1: miss), hit_pdf, hit_le (n x 3)."""
-        ref_p = np.ascontiguousarray(ref_p, dtype=np.float32).reshape(-1, 3)
-        sample = np.ascontiguousarray(sample, dtype=np.float32).reshape(-1, 2)
-        if ref_p.shape[0] != sample.shape[0]:
-            raise ValueError("emitter_probe: ref_p and sample must have the same number of rows")
-        n = ref_p.shape[0]
-        out = np.empty((n, _lib.PROBE_FLOATS), dtype=np.float32)
-        FP = C.POINTER(C.c_float)
-        _lib.check(self._lib.lrt_emitter_probe(self._h, ref_p.ctypes.data_as(FP), sample.ctypes.data_as(FP), n, out.ctypes.data_as(FP), int(device)))
+        out = self._probe("emitter_probe", [("ref_p", ref_p, 3, np.float32), ("sample", sample, 2, np.float32)], _lib.PROBE_FLOATS, device=device)
         return {"p": out[:, 0:3], "n": out[:, 3:6], "d": out[:, 6:9], "dist": out[:, 9], "pdf": out[:, 10], "weight": out[:, 11:14],
                 "emitter": out[:, 14].astype(np.int32), "hit_shape": out[:, 15].astype(np.int32), "hit_pdf": out[:, 16], "hit_le": out[:, 17:20]}
 
     def envmap_probe(self, directions, device=0):
         """lrt_envmap_probe (test hook): the environment emitter at world directions (n x 3), as the integrators evaluate it for a
         ray that leaves the scene.  Returns (pdf (n), radiance (n x 3)): Scene::pdf_emitter_direction of the miss, the emitter's eval."""
-        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
-        out = np.empty((d.shape[0], 4), dtype=np.float32)
-        FP = C.POINTER(C.c_float)
-        _lib.check(self._lib.lrt_envmap_probe(self._h, d.ctypes.data_as(FP), d.shape[0], out.ctypes.data_as(FP), int(device)))
+        out = self._probe("envmap_probe", [("directions", directions, 3, np.float32)], 4, device=device)
         return out[:, 0].copy(), out[:, 1:4].copy()
 
     def phase_probe(self, medium, wi, sample, wo_query, device=0):
         """lrt_phase_probe (test hook): the phase function of medium `medium` (an index into desc.media) as the EXT render kernels call it,
         per lane: PhaseFunction::sample(wi, sample = (s1, s2x, s2y)) and eval_pdf(wi, wo_query) (n x 3 each).  Returns a dict of arrays:
         wo (n x 3), weight, pdf, eval, eval_pdf (n each)."""
-        a = [np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (wi, sample, wo_query)]
-        n = a[0].shape[0]
-        if any(x.shape[0] != n for x in a):
-            raise ValueError("phase_probe: wi, sample and wo_query must have the same number of rows")
-        out = np.zeros((n, _lib.PHASE_PROBE_FLOATS), np.float32)
-        FP = C.POINTER(C.c_float)
-        _lib.check(self._lib.lrt_phase_probe(self._h, int(medium), *[x.ctypes.data_as(FP) for x in a], n, out.ctypes.data_as(FP), int(device)))
+        out = self._probe("phase_probe", [("wi", wi, 3, np.float32), ("sample", sample, 3, np.float32), ("wo_query", wo_query, 3, np.float32)],
+                          _lib.PHASE_PROBE_FLOATS, np.zeros, medium, device)
         return {"wo": out[:, 0:3], "weight": out[:, 3], "pdf": out[:, 4], "eval": out[:, 5], "eval_pdf": out[:, 6]}
 
     def medium_probe(self, medium, o, d, maxt, sample, channel, device=0):
@@ -517,16 +515,8 @@ class Scene:
         it, per lane: Medium::sample_interaction(ray(o, d, maxt), sample, channel) (o, d: n x 3; maxt, sample, channel: n).  A lane with
         maxt = NaN evaluates the grid at the local point o alone.  Returns a dict of arrays: valid (bool), t, p, mint, sigma_t, sigma_s,
         sigma_n, combined (n x 3 each), local (n x 3), grid, and raw (n x LRT_MEDIUM_PROBE_FLOATS, every float as returned)."""
-        o, d = (np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (o, d))
-        maxt, sample = (np.ascontiguousarray(x, np.float32).reshape(-1) for x in (maxt, sample))
-        channel = np.ascontiguousarray(channel, np.uint32).reshape(-1)
-        n = o.shape[0]
-        if any(x.shape[0] != n for x in (d, maxt, sample, channel)):
-            raise ValueError("medium_probe: o, d, maxt, sample and channel must have the same number of rows")
-        out = np.zeros((n, _lib.MEDIUM_PROBE_FLOATS), np.float32)
-        FP = C.POINTER(C.c_float)
-        _lib.check(self._lib.lrt_medium_probe(self._h, int(medium), *[x.ctypes.data_as(FP) for x in (o, d, maxt, sample)],
-                                              channel.ctypes.data_as(C.POINTER(C.c_uint32)), n, out.ctypes.data_as(FP), int(device)))
+        out = self._probe("medium_probe", [("o", o, 3, np.float32), ("d", d, 3, np.float32), ("maxt", maxt, 1, np.float32), ("sample", sample, 1, np.float32),
+                                           ("channel", channel, 1, np.uint32)], _lib.MEDIUM_PROBE_FLOATS, np.zeros, medium, device)
         return _lib.medium_probe_fields(out)
 
     def sensor_probe(self, inputs, device=0):
@@ -534,24 +524,15 @@ class Scene:
         (ax, ay), the film-to-sample map and the filter footprint of a sample at the film position (spx, spy), and the reconstruction filter
         at x.  Returns a dict of arrays: o, d (n x 3), maxt, adjusted (n x 2), origin (n x 2, int), rel (n x 2), weight, fcount (int), and
         raw (n x LRT_SENSOR_PROBE_FLOATS, every float as returned)."""
-        a = np.ascontiguousarray(inputs, np.float32).reshape(-1, 5)
-        out = np.zeros((a.shape[0], _lib.SENSOR_PROBE_FLOATS), np.float32)
-        FP = C.POINTER(C.c_float)
-        _lib.check(self._lib.lrt_sensor_probe(self._h, a.ctypes.data_as(FP), a.shape[0], out.ctypes.data_as(FP), int(device)))
-        return _lib.sensor_probe_fields(out)
+        return _lib.sensor_probe_fields(self._probe("sensor_probe", [("inputs", inputs, 5, np.float32)], _lib.SENSOR_PROBE_FLOATS, np.zeros, device=device))
 
     def bsdf_probe(self, o, d, sample, wo_query, device=0):
         """lrt_bsdf_probe (test hook): per ray (o, d) (n x 3 each) the closest hit without a ray offset, its surface interaction, the hit
         shape's BSDF sampled with sample (n x 3: s1, s2.x, s2.y) as the integrators do, and its eval / pdf at the world direction
         wo_query (n x 3).  Returns a dict of arrays: shape (int, -1: miss), t, p, n, sh_n, uv, wi (local), wo (world), wo_z (local),
         pdf, eta, type (int), weight, eval, eval_pdf, and raw (n x LRT_BSDF_PROBE_FLOATS, every float as returned)."""
-        a = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3) for x in (o, d, sample, wo_query)]
-        n = a[0].shape[0]
-        if any(x.shape[0] != n for x in a):
-            raise ValueError("bsdf_probe: o, d, sample and wo_query must have the same number of rows")
-        out = np.empty((n, _lib.BSDF_PROBE_FLOATS), dtype=np.float32)
-        FP = C.POINTER(C.c_float)
-        _lib.check(self._lib.lrt_bsdf_probe(self._h, *[x.ctypes.data_as(FP) for x in a], n, out.ctypes.data_as(FP), int(device)))
+        out = self._probe("bsdf_probe", [("o", o, 3, np.float32), ("d", d, 3, np.float32), ("sample", sample, 3, np.float32), ("wo_query", wo_query, 3, np.float32)],
+                          _lib.BSDF_PROBE_FLOATS, device=device)
         return _lib.bsdf_probe_fields(out)
 
     # -- parameters (mi.traverse) -------------------------------------------

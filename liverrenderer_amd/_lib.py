@@ -220,17 +220,12 @@ def lib():
     L.lrt_render_backward_grid.argtypes = [C.c_void_p, P(RenderOpts), C.c_void_p, P(ParamGrads), C.c_void_p]
     L.lrt_render_backward_grid.restype = C.c_int
     L.lrt_trace.argtypes = [C.c_void_p, P(RaysSoA), P(HitsSoA), C.c_uint32, C.c_int]
-    L.lrt_emitter_probe.argtypes = [C.c_void_p, P(C.c_float), P(C.c_float), C.c_uint32, P(C.c_float), C.c_int]
-    L.lrt_envmap_probe.argtypes = [C.c_void_p, P(C.c_float), C.c_uint32, P(C.c_float), C.c_int]
-    L.lrt_envmap_probe.restype = C.c_int
-    L.lrt_bsdf_probe.argtypes = [C.c_void_p, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), C.c_uint32, P(C.c_float), C.c_int]
-    L.lrt_bsdf_probe.restype = C.c_int
-    L.lrt_phase_probe.argtypes = [C.c_void_p, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), C.c_uint32, P(C.c_float), C.c_int]
-    L.lrt_phase_probe.restype = C.c_int
-    L.lrt_medium_probe.argtypes = [C.c_void_p, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_uint32), C.c_uint32, P(C.c_float), C.c_int]
-    L.lrt_medium_probe.restype = C.c_int
-    L.lrt_sensor_probe.argtypes = [C.c_void_p, P(C.c_float), C.c_uint32, P(C.c_float), C.c_int]
-    L.lrt_sensor_probe.restype = C.c_int
+    # the probes: (scene, [medium,] one pointer per input array, n, out, device); F: float *, U: uint32_t *
+    F, U = P(C.c_float), P(C.c_uint32)
+    for name, medium, arrays in (("lrt_emitter_probe", 0, [F, F]), ("lrt_envmap_probe", 0, [F]), ("lrt_bsdf_probe", 0, [F, F, F, F]),
+                                 ("lrt_phase_probe", 1, [F, F, F]), ("lrt_medium_probe", 1, [F, F, F, F, U]), ("lrt_sensor_probe", 0, [F])):
+        getattr(L, name).argtypes = [C.c_void_p] + [C.c_int] * medium + arrays + [C.c_uint32, F, C.c_int]
+        getattr(L, name).restype = C.c_int
     L.lrt_param_set.argtypes = [C.c_void_p, C.c_char_p, P(C.c_float), C.c_int]
     L.lrt_param_get.argtypes = [C.c_void_p, C.c_char_p, P(C.c_float), C.c_int]
     L.lrt_image_read.argtypes = [C.c_char_p, P(C.c_int), P(C.c_int), P(C.c_int), P(P(C.c_float))]
@@ -260,7 +255,7 @@ def lib():
     for name in ("lrt_denoiser_create", "lrt_denoise", "lrt_denoiser_get", "lrt_image_read_named", "lrt_scene_moment_get", "lrt_render_moment", "lrt_render_moment_samples"):
         getattr(L, name).restype = C.c_int
     for name in ("lrt_image_read", "lrt_image_write_exr", "lrt_image_write_png", "lrt_scene_load_xml", "lrt_scene_load_xml_string", "lrt_scene_from_desc", "lrt_render", "lrt_render_multi", "lrt_render_backward_multi", "lrt_math_eval", "lrt_render_stats_get",
-                 "lrt_film_develop", "lrt_render_samples", "lrt_render_backward", "lrt_trace", "lrt_emitter_probe", "lrt_param_set", "lrt_param_get",
+                 "lrt_film_develop", "lrt_render_samples", "lrt_render_backward", "lrt_trace", "lrt_param_set", "lrt_param_get",
                  "lrt_image_write_exr_channels", "lrt_scene_aov_get", "lrt_render_aov", "lrt_render_aov_samples"):
         getattr(L, name).restype = C.c_int
     _lib = L

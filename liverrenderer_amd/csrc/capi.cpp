@@ -387,61 +387,47 @@ lrt_status lrt_trace(lrt_scene *scene, const lrt_rays_soa *rays, const lrt_hits_
     LRT_CATCH
 }
 
-lrt_status lrt_emitter_probe(lrt_scene *scene, const float *ref_p, const float *sample, uint32_t n, float *out, int device) {
-    if (!scene || ((!ref_p || !sample || !out) && n)) return fail(LRT_ERR_INVALID, "lrt_emitter_probe: null argument");
+// The frame of the six probe entry points: the null and medium checks, then device_probe.  `columns`: the inputs in the order of the
+// kind's lane record (probes.h).  medium: the index for the kinds that take one (phase, medium), null for the others.
+static lrt_status probe_call(const char *fn, ProbeKind kind, lrt_scene *scene, const int *medium, std::initializer_list<ProbeColumn> columns, uint32_t n, float *out, int device) {
+    bool null = !scene || (!out && n);
+    for (const ProbeColumn &c : columns) null = null || (!c.p && n);
+    if (null) return fail(LRT_ERR_INVALID, std::string(fn) + ": null argument");
+    if (medium && (*medium < 0 || (size_t) *medium >= scene->st.media.size())) return fail(LRT_ERR_INVALID, std::string(fn) + ": no such medium");
     LRT_TRY
         ensure_device(scene, device);
-        device_emitter_probe(scene->dev, ref_p, sample, n, out);
+        device_probe(scene->dev, kind, medium ? *medium : 0, columns, n, out);
         return LRT_OK;
     LRT_CATCH
+}
+
+lrt_status lrt_emitter_probe(lrt_scene *scene, const float *ref_p, const float *sample, uint32_t n, float *out, int device) {
+    return probe_call("lrt_emitter_probe", PROBE_EMITTER, scene, nullptr, { { ref_p, 3 }, { sample, 2 } }, n, out, device);
 }
 
 lrt_status lrt_envmap_probe(lrt_scene *scene, const float *dir, uint32_t n, float *out, int device) {
-    if (!scene || ((!dir || !out) && n)) return fail(LRT_ERR_INVALID, "lrt_envmap_probe: null argument");
-    LRT_TRY
-        ensure_device(scene, device);
-        device_envmap_probe(scene->dev, dir, n, out);
-        return LRT_OK;
-    LRT_CATCH
+    return probe_call("lrt_envmap_probe", PROBE_ENVMAP, scene, nullptr, { { dir, 3 } }, n, out, device);
 }
 
 lrt_status lrt_bsdf_probe(lrt_scene *scene, const float *o, const float *d, const float *sample, const float *wo_query, uint32_t n, float *out, int device) {
-    if (!scene || ((!o || !d || !sample || !wo_query || !out) && n)) return fail(LRT_ERR_INVALID, "lrt_bsdf_probe: null argument");
-    LRT_TRY
-        ensure_device(scene, device);
-        device_bsdf_probe(scene->dev, o, d, sample, wo_query, n, out);
-        return LRT_OK;
-    LRT_CATCH
+    return probe_call("lrt_bsdf_probe", PROBE_BSDF, scene, nullptr, { { o, 3 }, { d, 3 }, { sample, 3 }, { wo_query, 3 } }, n, out, device);
 }
 
 lrt_status lrt_phase_probe(lrt_scene *scene, int medium, const float *wi, const float *sample, const float *wo_query, uint32_t n, float *out, int device) {
-    if (!scene || ((!wi || !sample || !wo_query || !out) && n)) return fail(LRT_ERR_INVALID, "lrt_phase_probe: null argument");
-    if (medium < 0 || (size_t) medium >= scene->st.media.size()) return fail(LRT_ERR_INVALID, "lrt_phase_probe: no such medium");
-    LRT_TRY
-        ensure_device(scene, device);
-        device_phase_probe(scene->dev, medium, wi, sample, wo_query, n, out);
-        return LRT_OK;
-    LRT_CATCH
+    return probe_call("lrt_phase_probe", PROBE_PHASE, scene, &medium, { { wi, 3 }, { sample, 3 }, { wo_query, 3 } }, n, out, device);
 }
 
 lrt_status lrt_medium_probe(lrt_scene *scene, int medium, const float *o, const float *d, const float *maxt, const float *sample, const uint32_t *channel,
                             uint32_t n, float *out, int device) {
-    if (!scene || ((!o || !d || !maxt || !sample || !channel || !out) && n)) return fail(LRT_ERR_INVALID, "lrt_medium_probe: null argument");
-    if (medium < 0 || (size_t) medium >= scene->st.media.size()) return fail(LRT_ERR_INVALID, "lrt_medium_probe: no such medium");
     LRT_TRY
-        ensure_device(scene, device);
-        device_medium_probe(scene->dev, medium, o, d, maxt, sample, channel, n, out);
-        return LRT_OK;
+        std::vector<float> ch;                                   // the lane record carries the channel as a float, clamped to 2
+        if (channel) for (uint32_t i = 0; i < n; ++i) ch.push_back((float) std::min<uint32_t>(channel[i], 2u));
+        return probe_call("lrt_medium_probe", PROBE_MEDIUM, scene, &medium, { { o, 3 }, { d, 3 }, { maxt, 1 }, { sample, 1 }, { channel ? ch.data() : nullptr, 1 } }, n, out, device);
     LRT_CATCH
 }
 
 lrt_status lrt_sensor_probe(lrt_scene *scene, const float *in, uint32_t n, float *out, int device) {
-    if (!scene || ((!in || !out) && n)) return fail(LRT_ERR_INVALID, "lrt_sensor_probe: null argument");
-    LRT_TRY
-        ensure_device(scene, device);
-        device_sensor_probe(scene->dev, in, n, out);
-        return LRT_OK;
-    LRT_CATCH
+    return probe_call("lrt_sensor_probe", PROBE_SENSOR, scene, nullptr, { { in, 5 } }, n, out, device);
 }
 
 static lrt_medium_desc *find_medium(lrt_scene *s, const char *key, const char **rest) {

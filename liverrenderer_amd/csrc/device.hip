@@ -9,6 +9,7 @@
 #include "kernels_aov.h"
 #include "kernels_denoise.h"
 #include "kernels_moment.h"
+#include "probes.h"
 #include <functional>
 #include "scene_prep.h"
 #include <cmath>
@@ -247,6 +248,11 @@ static TraceLdsFn trace_lds_kernel(bool any_hit, bool ext) {            // k_tra
 static RenderFn moment_splat_kernel(bool wide, bool alpha) {            // k_moment_splat<WIDE, ALPHA> for a reconstruction filter and a film
     static const RenderFn t[2][2] = { { k_moment_splat<false, false>, k_moment_splat<false, true> }, { k_moment_splat<true, false>, k_moment_splat<true, true> } };
     return t[wide][alpha];
+}
+typedef decltype(&k_probe<PROBE_EMITTER>) ProbeFn;
+static ProbeFn probe_kernel(ProbeKind kind) {                           // k_probe<KIND> (probes.h): one instance per row of kProbes
+    static const ProbeFn t[PROBE_KINDS] = { k_probe<PROBE_EMITTER>, k_probe<PROBE_ENVMAP>, k_probe<PROBE_BSDF>, k_probe<PROBE_PHASE>, k_probe<PROBE_MEDIUM>, k_probe<PROBE_SENSOR> };
+    return t[kind];
 }
 
 DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
@@ -1083,70 +1089,36 @@ void device_render_backward_multi(std::vector<DeviceScene *> &devs, MultiContext
     stats = total;
 }
 
-// Test hook (include/liverrt.h lrt_emitter_probe): k_emitter_probe (kernels.h) on the scene's device image
-void device_emitter_probe(DeviceScene *D, const float *ref_p, const float *sample, uint32_t n, float *out) {
+// Test hooks (include/liverrt.h lrt_*_probe; probes.h): probe `kind` on the scene's device image, `n` lanes.  `columns` are the caller's
+// input arrays in the order of the kind's lane record; they are packed into lane records here and uploaded once.  arg: kProbes' note.
+void device_probe(DeviceScene *D, ProbeKind kind, int arg, std::initializer_list<ProbeColumn> columns, uint32_t n, float *out) {
+    const ProbeRow &P = kProbes[kind];
     HIP_CHECK(hipSetDevice(D->device));
+    if (P.needs_env && D->sc.env.emitter < 0) throw std::runtime_error(std::string(P.name) + ": the scene has no environment emitter");
     if (!n) return;
+    int width = 0; for (const ProbeColumn &c : columns) width += c.width;
+    if (width != P.in) throw std::logic_error(std::string(P.name) + ": the columns do not add up to the lane record");
+    std::vector<float> packed((size_t) n * P.in);            // (lives until the synchronise below: the upload reads it asynchronously)
+    int at = 0;
+    for (const ProbeColumn &c : columns) {
+        for (size_t i = 0; i < n; ++i) std::copy_n(c.p + i * c.width, c.width, packed.data() + i * P.in + at);
+        at += c.width;
+    }
     hipStream_t st = D->stream;
-    DevTmp dr, ds, dout((size_t) n * LRT_PROBE_FLOATS);
-    dr.upload(ref_p, (size_t) n * 3, st); ds.upload(sample, (size_t) n * 2, st);
-    k_emitter_probe<<<(n + LRT_BLOCK - 1) / LRT_BLOCK, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, dr.p, ds.p, n, dout.p);
+    DevTmp in, dout((size_t) n * P.out);
+    in.upload(packed.data(), packed.size(), st);
+    probe_kernel(kind)<<<(n + LRT_BLOCK - 1) / LRT_BLOCK, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, arg, in.p, n, dout.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * LRT_PROBE_FLOATS * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-}
-
-// Test hook (include/liverrt.h lrt_envmap_probe): k_envmap_probe (kernels.h) on the scene's device image
-void device_envmap_probe(DeviceScene *D, const float *dir, uint32_t n, float *out) {
-    HIP_CHECK(hipSetDevice(D->device));
-    if (D->sc.env.emitter < 0) throw std::runtime_error("lrt_envmap_probe: the scene has no environment emitter");
-    if (!n) return;
-    hipStream_t st = D->stream;
-    DevTmp dd, dout((size_t) n * 4);
-    dd.upload(dir, (size_t) n * 3, st);
-    k_envmap_probe<<<(n + LRT_BLOCK - 1) / LRT_BLOCK, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, dd.p, n, dout.p);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * 4 * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-}
-
-// Test hook (include/liverrt.h lrt_bsdf_probe): k_bsdf_probe (kernels.h) on the scene's device image
-void device_bsdf_probe(DeviceScene *D, const float *o, const float *d, const float *sample, const float *wo_query, uint32_t n, float *out) {
-    HIP_CHECK(hipSetDevice(D->device));
-    if (!n) return;
-    hipStream_t st = D->stream;
-    DevTmp in[4], dout((size_t) n * LRT_BSDF_PROBE_FLOATS);
-    const float *src[4] = { o, d, sample, wo_query };
-    for (int k = 0; k < 4; ++k) in[k].upload(src[k], (size_t) n * 3, st);
-    k_bsdf_probe<<<(n + LRT_BLOCK - 1) / LRT_BLOCK, LRT_BLOCK, 0, st>>>((ScenePtr) D->d_sc, in[0].p, in[1].p, in[2].p, in[3].p, n, dout.p);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * LRT_BSDF_PROBE_FLOATS * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * P.out * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
 }
 
 // Test hook (include/liverrt.h lrt_math_eval): the transcendental kernels of csrc/dmath.h evaluated on the device, one lane per value.
 // orc_math.h holds the same polynomials written a second time, so bit-equality of the render lanes says nothing about their accuracy:
 // tests/test_parity_gpu.py bounds the DEVICE values against float64 and checks them bit for bit against the oracle's twins.
-// The kernel is also where lrt_phase_probe runs: the set of compiled kernels is pinned (tests/golden/kernel_names.txt), and this kernel is the
-// one whose first argument already selects what a lane evaluates.  fn = LRT_MATH_PHASE_PROBE + m (device_phase_probe only; lrt_math_eval
-// refuses it): `y` is the scene record, `x` holds 9 floats per lane (wi, sample, wo_query), `out` takes LRT_PHASE_PROBE_FLOATS per lane
-// for medium m, out2 is not written.  lrt_medium_probe runs here in the same way: fn = LRT_MATH_MEDIUM_PROBE + m (device_medium_probe only),
-// `x` holds 9 floats per lane (o, d, maxt, sample, channel), `out` takes LRT_MEDIUM_PROBE_FLOATS per lane.  And lrt_sensor_probe:
-// fn = LRT_MATH_SENSOR_PROBE (device_sensor_probe only), `x` holds 5 floats per lane, `out` takes LRT_SENSOR_PROBE_FLOATS per lane.
-#define LRT_MATH_PHASE_PROBE 0x100
-#define LRT_MATH_SENSOR_PROBE 0x20000000
-#define LRT_MATH_MEDIUM_PROBE 0x40000000
 __global__ void k_math_eval(int fn, const float *__restrict__ x, const float *__restrict__ y, uint32_t n, float *__restrict__ out, float *__restrict__ out2) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    if (fn >= LRT_MATH_PHASE_PROBE) {
-        SceneRef sc = *(ScenePtr) (const void *) y;
-        if (fn >= LRT_MATH_MEDIUM_PROBE) { medium_probe_lane(sc, fn - LRT_MATH_MEDIUM_PROBE, x + 9 * (size_t) i, out + (size_t) LRT_MEDIUM_PROBE_FLOATS * i); return; }
-        if (fn >= LRT_MATH_SENSOR_PROBE) { sensor_probe_lane(sc, x + 5 * (size_t) i, out + (size_t) LRT_SENSOR_PROBE_FLOATS * i); return; }
-        const float *in = x + 9 * (size_t) i;
-        phase_probe_lane(sc, fn - LRT_MATH_PHASE_PROBE, in, in + 3, in + 6, out + (size_t) LRT_PHASE_PROBE_FLOATS * i);
-        return;
-    }
     float a = 0.f, b = 0.f;
     switch (fn) {
         case 0: a = m_log(x[i]); break;
@@ -1175,57 +1147,6 @@ void device_math_eval(int fn, const float *x, const float *y, uint32_t n, float 
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpy(out, d1.p, (size_t) n * 4, hipMemcpyDeviceToHost));
     if (out2) HIP_CHECK(hipMemcpy(out2, d2.p, (size_t) n * 4, hipMemcpyDeviceToHost));
-}
-
-// Test hook (include/liverrt.h lrt_phase_probe): phase_probe_lane (kernels.h) on the scene's device image, through k_math_eval's selector
-// LRT_MATH_PHASE_PROBE (above)
-void device_phase_probe(DeviceScene *D, int medium, const float *wi, const float *sample, const float *wo_query, uint32_t n, float *out) {
-    HIP_CHECK(hipSetDevice(D->device));
-    if (medium < 0 || (size_t) medium >= D->h_media.size()) throw std::invalid_argument("lrt_phase_probe: no such medium");
-    if (!n) return;
-    hipStream_t st = D->stream;
-    std::vector<float> packed((size_t) n * 9);               // per lane: wi, sample, wo_query
-    for (size_t i = 0; i < n; ++i) for (int c = 0; c < 3; ++c) { packed[9 * i + c] = wi[3 * i + c]; packed[9 * i + 3 + c] = sample[3 * i + c]; packed[9 * i + 6 + c] = wo_query[3 * i + c]; }
-    DevTmp in, dout((size_t) n * LRT_PHASE_PROBE_FLOATS);
-    in.upload(packed.data(), packed.size(), st);
-    k_math_eval<<<(n + 255) / 256, 256, 0, st>>>(LRT_MATH_PHASE_PROBE + medium, in.p, (const float *) D->d_sc, n, dout.p, nullptr);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * LRT_PHASE_PROBE_FLOATS * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-}
-
-// Test hook (include/liverrt.h lrt_medium_probe): medium_probe_lane (kernels.h) on the scene's device image, through k_math_eval's selector
-// LRT_MATH_MEDIUM_PROBE (above)
-void device_medium_probe(DeviceScene *D, int medium, const float *o, const float *d, const float *maxt, const float *sample, const uint32_t *channel, uint32_t n, float *out) {
-    HIP_CHECK(hipSetDevice(D->device));
-    if (medium < 0 || (size_t) medium >= D->h_media.size()) throw std::invalid_argument("lrt_medium_probe: no such medium");
-    if (!n) return;
-    hipStream_t st = D->stream;
-    std::vector<float> packed((size_t) n * 9);               // per lane: o, d, maxt, sample, channel
-    for (size_t i = 0; i < n; ++i) {
-        for (int c = 0; c < 3; ++c) { packed[9 * i + c] = o[3 * i + c]; packed[9 * i + 3 + c] = d[3 * i + c]; }
-        packed[9 * i + 6] = maxt[i]; packed[9 * i + 7] = sample[i]; packed[9 * i + 8] = (float) std::min<uint32_t>(channel[i], 2u);
-    }
-    DevTmp in, dout((size_t) n * LRT_MEDIUM_PROBE_FLOATS);
-    in.upload(packed.data(), packed.size(), st);
-    k_math_eval<<<(n + 255) / 256, 256, 0, st>>>(LRT_MATH_MEDIUM_PROBE + medium, in.p, (const float *) D->d_sc, n, dout.p, nullptr);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * LRT_MEDIUM_PROBE_FLOATS * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-}
-
-// Test hook (include/liverrt.h lrt_sensor_probe): sensor_probe_lane (kernels.h) on the scene's device image, through k_math_eval's selector
-// LRT_MATH_SENSOR_PROBE (above)
-void device_sensor_probe(DeviceScene *D, const float *in5, uint32_t n, float *out) {
-    HIP_CHECK(hipSetDevice(D->device));
-    if (!n) return;
-    hipStream_t st = D->stream;
-    DevTmp in, dout((size_t) n * LRT_SENSOR_PROBE_FLOATS);
-    in.upload(in5, (size_t) n * 5, st);
-    k_math_eval<<<(n + 255) / 256, 256, 0, st>>>(LRT_MATH_SENSOR_PROBE, in.p, (const float *) D->d_sc, n, dout.p, nullptr);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t) n * LRT_SENSOR_PROBE_FLOATS * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
 }
 
 // ---- guided denoiser (kernels_denoise.h)

@@ -2,6 +2,7 @@
 // translation unit (device.hip).  All functions throw std::runtime_error.
 #pragma once
 #include "../../include/liverrt.h"
+#include <initializer_list>
 #include <vector>
 
 namespace lrt {
@@ -19,12 +20,10 @@ void device_render_moment(DeviceScene *D, const lrt_scene_desc &d, const lrt_ren
 void device_render_moment_samples(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out, lrt_render_stats &stats);
 void device_render_samples(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out, lrt_render_stats &stats);
 void device_trace(DeviceScene *D, const lrt_rays_soa *rays, const lrt_hits_soa *hits, uint32_t n, int any_hit);
-void device_envmap_probe(DeviceScene *D, const float *dir, uint32_t n, float *out);   // test hook: the environment emitter's pdf and radiance at given directions
-void device_sensor_probe(DeviceScene *D, const float *in5, uint32_t n, float *out);   // test hook: the sensor's ray, the film footprint, the reconstruction filter
-void device_medium_probe(DeviceScene *D, int medium, const float *o, const float *d, const float *maxt, const float *sample, const uint32_t *channel, uint32_t n, float *out);   // test hook: free-flight sampling in a medium, the grid lookup
-void device_phase_probe(DeviceScene *D, int medium, const float *wi, const float *sample, const float *wo_query, uint32_t n, float *out);   // test hook: a medium's phase function, sampled and evaluated
-void device_bsdf_probe(DeviceScene *D, const float *o, const float *d, const float *sample, const float *wo_query, uint32_t n, float *out);   // test hook: surface interaction and BSDF at given rays
-void device_emitter_probe(DeviceScene *D, const float *ref_p, const float *sample, uint32_t n, float *out);   // test hook: emitter sampling of the EXT instances
+// test hooks (probes.h): one piece of the shading code per lane.  The kinds are named here because capi.cpp names them and cannot see device code.
+enum ProbeKind { PROBE_EMITTER, PROBE_ENVMAP, PROBE_BSDF, PROBE_PHASE, PROBE_MEDIUM, PROBE_SENSOR, PROBE_KINDS };
+struct ProbeColumn { const float *p; int width; };   // one input array of a probe call: `width` floats per lane
+void device_probe(DeviceScene *D, ProbeKind kind, int arg, std::initializer_list<ProbeColumn> columns, uint32_t n, float *out);
 // network stage of the learned subsurface model (kernels_vae.h): host arrays in, host arrays out
 void device_vae_scatter(const float *blob, uint32_t n, const float *in_pos, const float *in_dir, const float *poly, const float albedo[3], float g, float ior,
                         const float sigma_t[3], float fit_scale, uint32_t seed, float *out_pos, float *out_absorption, int device);

@@ -643,7 +643,7 @@ DEV float shadow_terminator(V3 pn, V3 wo) {       // src/bsdfs/normalmap_helpers
 }
 
 // ------------------------------------------------- roughdielectric (src/bsdfs/roughdielectric.cpp)
-// Compiled into the EXT instances, k_bsdf_probe and k_math_eval alone (leaf_sample / leaf_eval / leaf_pdf below).
+// Compiled into the EXT instances, the bsdf probe (probes.h) and k_math_eval (fn 9, 10) alone (leaf_sample / leaf_eval / leaf_pdf below).
 // erf: |x| < 1 the odd polynomial of Cephes' single-precision erff (ndtrf.c, table T), beyond it Abramowitz & Stegun 7.1.26
 // (|error| <= 1.5e-7).  erfinv: M. Giles, "Approximating the erfinv function" (GPU Computing Gems, Jade edition, 2012), the
 // single-precision pair of polynomials in w = -log((1 - x)(1 + x)).  Both stand in for Dr.Jit's dr::erf / dr::erfinv
@@ -872,7 +872,7 @@ DEV void rough_eval_pdf(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, V3 wo,
 }
 
 // ------------------------------------------------- conductor, plastic, twosided (src/bsdfs/conductor.cpp, plastic.cpp, twosided.cpp)
-// Compiled into the EXT instances, k_bsdf_probe and the EXT aov kernels alone, like the roughdielectric.  X: the BSDF's row of DScene::bsdf_ext.
+// Compiled into the EXT instances, the bsdf probe (probes.h) and the EXT aov kernels alone, like the roughdielectric.  X: the BSDF's row of DScene::bsdf_ext.
 DEV BSDFSample bsdf_sample_zero() { BSDFSample bs; bs.wo = V3(0.f); bs.pdf = 0.f; bs.eta = 0.f; bs.type = 0; bs.weight = V3(0.f); return bs; }   // dr::zeros<BSDFSample3f>
 // include/mitsuba/render/fresnel.h:92-117, one channel.  eta = 0, k = 1 (the plugin's defaults, a perfect mirror) gives exactly 1: temp_1 = -(1 + sin^2),
 // a_2_pb_2 = sqrt(temp_1^2) = -temp_1, a = 0, so r_s = term_1 / term_1 and r_p = r_s * term_3 / term_3.
@@ -953,7 +953,7 @@ DEV int twosided_child(SceneRef sc, int b, const DBsdf &B, float wi_z) {
 
 // Leaf BSDFs (diffuse / dielectric / null; EXT: roughdielectric, conductor and plastic too), evaluated in the frame `wi` is given in.
 // DIELECTRIC: the caller has proven that the leaf is a dielectric (the 64-byte-record kernels, closed_records (b) in device.hip): no dispatch.
-// EXT: the scene may hold a roughdielectric, a conductor or a plastic (the EXT instances, k_bsdf_probe); without it their code is not compiled in.
+// EXT: the scene may hold a roughdielectric, a conductor or a plastic (the EXT instances, the bsdf probe of probes.h); without it their code is not compiled in.
 // b: the leaf's index, for its row of DScene::bsdf_ext (EXT alone reads it).
 template <bool DIELECTRIC = false, bool EXT = false>
 DEV BSDFSample leaf_sample(SceneRef sc, const DBsdf &B, const SI &si, V3 wi, float s1, float s2x, float s2y, int b = -1) {
@@ -1507,8 +1507,8 @@ DEV void phase_sample(const DMedium &M, V3 wi, float s2x, float s2y, V3 *wo, flo
 DEV float phase_eval(const DMedium &M, V3 wi, V3 wo) { return M.phase == LRT_PHASE_HG ? hg_eval(M.g, dot(wo, wi)) : kInvFourPi; }
 
 // ------------------------------------------------- tabulated, Rayleigh and blended phase functions
-// (src/phase/tabphase.cpp, rayleigh.cpp, blendphase.cpp; DPhase in device_types.h).  Compiled into the EXT instances and k_math_eval (fn 11, and the
-// phase probe it hosts) alone: phase_sample<false> / phase_eval<false> are the two functions above.
+// (src/phase/tabphase.cpp, rayleigh.cpp, blendphase.cpp; DPhase in device_types.h).  Compiled into the EXT instances, the phase probe (probes.h) and k_math_eval
+// (fn 11) alone: phase_sample<false> / phase_eval<false> are the two functions above.
 // cbrt stands in for Dr.Jit's dr::cbrt (rayleigh.cpp:63-64): exp(log|x| / 3) and one Newton step on y^3 = |x| with the residual formed by an
 // fma; measured against float64 through lrt_math_eval fn 11: at most 1 ulp over the normal floats.  +-0, inf and NaN
 // return x; subnormal arguments are not served (the Rayleigh inversion's arguments lie in [0.236, 4.24]).
