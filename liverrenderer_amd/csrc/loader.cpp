@@ -19,6 +19,7 @@
 // checkerboard.  A directional light's `direction` becomes the to_world the plugin builds from it.
 #include "host_scene.h"
 #include "scene_prep.h"
+#include "scene_check.h"
 #include "xml.h"
 #include "image_io.h"
 #include <map>
@@ -383,12 +384,12 @@ struct Loader {
         B.diffuse_reflectance = B.nested_back = -1;
         if (o->type == "diffuse") {
             B.type = LRT_BSDF_DIFFUSE; B.reflectance = texture_or_rgb(*o, "reflectance", .5f);
-            if (S.textures[B.reflectance].type == LRT_TEX_BITMAP) fail("unsupported: a bitmap texture as diffuse reflectance (bitmaps are supported as bump-map heights only)");
+            refuse_bitmap(S.textures[B.reflectance], "diffuse reflectance");
         }
         else if (o->type == "dielectric") {
             B.type = LRT_BSDF_DIELECTRIC;
             float ii = lookup_ior(*o, "int_ior", "bk7"), ei = lookup_ior(*o, "ext_ior", "air");
-            if (ii < 0 || ei < 0) fail("The interior and exterior indices of refraction must be positive!");
+            if (ii < 0 || ei < 0) fail(text::ior_positive);
             if (has(*o, "specular_reflectance") || has(*o, "specular_transmittance")) fail("dielectric: specular_reflectance/transmittance are not supported");
             B.eta = ii / ei;
         } else if (o->type == "bumpmap") {
@@ -404,7 +405,7 @@ struct Loader {
             auto spec_tex = [&](const char *k) {
                 if (!has(*o, k) && !child(*o, "texture", k)) return -1;
                 int t = texture_or_rgb(*o, k, 1.f);
-                if (S.textures[t].type == LRT_TEX_BITMAP) fail("unsupported: a bitmap texture as roughdielectric " + std::string(k) + " (bitmaps are supported as bump-map heights only)");
+                refuse_bitmap(S.textures[t], "roughdielectric " + std::string(k));
                 return t;
             };
             B.specular_reflectance = spec_tex("specular_reflectance"); B.specular_transmittance = spec_tex("specular_transmittance");
@@ -426,25 +427,25 @@ struct Loader {
         else if (o->type == "conductor") {           // src/bsdfs/conductor.cpp:224-239
             B.type = LRT_BSDF_CONDUCTOR;
             B.specular_reflectance = texture_or_rgb(*o, "specular_reflectance", 1.f);
-            if (S.textures[B.specular_reflectance].type == LRT_TEX_BITMAP) fail("unsupported: a bitmap texture as conductor specular_reflectance (bitmaps are supported as bump-map heights only)");
+            refuse_bitmap(S.textures[B.specular_reflectance], "conductor specular_reflectance");
             for (const char *k : { "eta", "k" })
                 if (child(*o, "texture", k)) fail("unsupported: a texture as conductor \"" + std::string(k) + "\" (a textured index of refraction is not built)");
             const std::string material = get_string(*o, "material", "none");
             if (has(*o, "eta") || material == "none") {
                 get_rgb(*o, "eta", 0.f, B.eta_rgb); get_rgb(*o, "k", 1.f, B.k_rgb);
                 if (material != "none") fail("Should specify either (eta, k) or material, not both.");
-                for (int c = 0; c < 3; ++c) if (B.eta_rgb[c] == 0.f && B.k_rgb[c] == 0.f) fail("conductor with eta = k = 0 in a channel (no index of refraction: its Fresnel term is 0 / 0 at normal incidence; the plugin's default is eta = 0, k = 1)");
+                for (int c = 0; c < 3; ++c) if (B.eta_rgb[c] == 0.f && B.k_rgb[c] == 0.f) fail(text::conductor_no_index);
             } else fail("unsupported: conductor material \"" + material + "\" (the measured .spd tables and their conversion to RGB are not built; give eta and k)");
         }
         else if (o->type == "plastic") {             // src/bsdfs/plastic.cpp:157-182
             B.type = LRT_BSDF_PLASTIC;
             float ii = lookup_ior(*o, "int_ior", "polypropylene"), ei = lookup_ior(*o, "ext_ior", "air");
-            if (ii < 0 || ei < 0) fail("The interior and exterior indices of refraction must be positive!");
+            if (ii < 0 || ei < 0) fail(text::ior_positive);
             B.eta = ii / ei;
             B.diffuse_reflectance = texture_or_rgb(*o, "diffuse_reflectance", .5f);
             if (has(*o, "specular_reflectance") || child(*o, "texture", "specular_reflectance")) B.specular_reflectance = texture_or_rgb(*o, "specular_reflectance", 1.f);
             for (int t : { B.diffuse_reflectance, B.specular_reflectance })
-                if (t >= 0 && S.textures[t].type == LRT_TEX_BITMAP) fail("unsupported: a bitmap texture as plastic diffuse_reflectance / specular_reflectance (bitmaps are supported as bump-map heights only)");
+                if (t >= 0) refuse_bitmap(S.textures[t], "plastic diffuse_reflectance / specular_reflectance");
             B.nonlinear = get_bool(*o, "nonlinear", false) ? 1 : 0;
         }
         else if (o->type == "twosided") {            // src/bsdfs/twosided.cpp:74-104
@@ -452,14 +453,14 @@ struct Loader {
             int n = 0, ch[2] = { -1, -1 };
             for (auto &c : o->children) if (c.second->tag == "bsdf") {
                 if (n >= 2) fail("At most two nested BSDFs can be specified!");
-                if (c.second->type == "bumpmap" || c.second->type == "twosided") fail("unsupported: a " + c.second->type + " nested in a twosided BSDF (its children are diffuse, conductor or plastic)");
+                if (c.second->type == "bumpmap" || c.second->type == "twosided") fail(text::twosided_child(c.second->type));
                 ch[n++] = make_bsdf(c.second);
             }
-            if (n == 0) fail("A nested one-sided material is required!");
+            if (n == 0) fail(text::twosided_no_child);
             if (get_bool(*o, "allow_transmission", false)) fail("unsupported: twosided with allow_transmission = true");
             for (int k = 0; k < n; ++k) {
                 const int t = S.bsdfs[ch[k]].type;
-                if (t == LRT_BSDF_DIELECTRIC || t == LRT_BSDF_ROUGHDIELECTRIC || t == LRT_BSDF_NULL) fail("Only materials without a transmission component can be nested!");
+                if (t == LRT_BSDF_DIELECTRIC || t == LRT_BSDF_ROUGHDIELECTRIC || t == LRT_BSDF_NULL) fail(text::twosided_transmission);
             }
             B.nested = ch[0]; B.nested_back = n == 2 ? ch[1] : ch[0];
         }
@@ -468,11 +469,12 @@ struct Loader {
     }
     // One entry of the phase table (lrt_phase_desc): tabphase, rayleigh, blendphase, and isotropic / hg as a blend's children.
     // src/phase/tabphase.cpp:44-67, rayleigh.cpp:41-48, blendphase.cpp:70-92
+    float hg_g(const Obj &ph) { const float g = get_float(ph, "g", 0.8f); if (!hg_g_valid(g)) fail(kHgRangeText); return g; }      // src/phase/hg.cpp:43-46
     int make_phase(const Obj &ph, bool top) {
         lrt_phase_desc Q{}; Q.child[0] = Q.child[1] = -1;
         std::vector<float> data;
         if (ph.type == "isotropic") Q.type = LRT_PHASE_ISOTROPIC;
-        else if (ph.type == "hg") { Q.type = LRT_PHASE_HG; Q.g = get_float(ph, "g", 0.8f); if (!(Q.g > -1.f && Q.g < 1.f)) fail("The asymmetry parameter must lie in the interval (-1, 1)!"); }
+        else if (ph.type == "hg") { Q.type = LRT_PHASE_HG; Q.g = hg_g(ph); }
         else if (ph.type == "rayleigh") Q.type = LRT_PHASE_RAYLEIGH;
         else if (ph.type == "tabphase") {
             Q.type = LRT_PHASE_TABULATED;
@@ -487,9 +489,9 @@ struct Loader {
                 try { data.push_back((float) std::stod(tok)); } catch (...) { fail("Could not parse floating point value '" + tok + "'"); }
             }
             PhaseTable T; phase_table(data.data(), data.size(), T);      // the reference's constructor errors
-            if (!(T.integral > 0.f) || !std::isfinite(T.integral)) fail("ContinuousDistribution: no probability mass found!");
+            if (!(T.integral > 0.f) || !std::isfinite(T.integral)) fail(text::no_probability_mass);
         } else if (ph.type == "blendphase") {
-            if (!top) fail("unsupported: a blendphase as the child of a blendphase (one level is built)");
+            if (!top) fail(text::blend_in_blend);
             Q.type = LRT_PHASE_BLEND;
             int n = 0;
             for (auto &c : ph.children) if (c.second->tag == "phase") {
@@ -529,7 +531,7 @@ struct Loader {
         M.sample_emitters = get_bool(*o, "sample_emitters", !parenchyma);
         M.phase = LRT_PHASE_ISOTROPIC; M.g = 0.f; M.phase_index = -1;
         if (ObjP ph = child(*o, "phase")) {
-            if (ph->type == "hg") { M.phase = LRT_PHASE_HG; M.g = get_float(*ph, "g", 0.8f); if (!(M.g > -1.f && M.g < 1.f)) fail("The asymmetry parameter must lie in the interval (-1, 1)!"); }
+            if (ph->type == "hg") { M.phase = LRT_PHASE_HG; M.g = hg_g(*ph); }      // (no entry of the phase table: the medium keeps its `g` key and its kernels)
             else if (ph->type == "tabphase" || ph->type == "rayleigh" || ph->type == "blendphase") M.phase_index = make_phase(*ph, true);   // an entry of the phase table
             else if (ph->type != "isotropic") fail("unsupported phase function \"" + ph->type + "\"");
         }
@@ -716,7 +718,7 @@ struct Loader {
             }
             else if (ch->tag == "emitter") {
                 if (ch->type != "area") fail("only area emitters can be attached to shapes");
-                if (sd.kind == LRT_SHAPE_SPHERE) fail("unsupported: an area emitter on a sphere (area emitters are supported on rectangles and triangle meshes)");
+                if (sd.kind == LRT_SHAPE_SPHERE) fail(text::emitter_on_sphere);
                 if (has(*ch, "to_world")) fail("Found a 'to_world' transformation -- this is not allowed. The area light inherits this transformation from its parent shape.");
                 if (sd.kind == LRT_SHAPE_MESH) {        // the sampling table is built again with the device scene; here it only validates the mesh
                     MeshEmitterTable tab;
@@ -753,18 +755,18 @@ struct Loader {
             E.type = LRT_EMITTER_SPOT; E.texture = -1;
             if (child(*o, "texture", "intensity")) fail("The parameter 'intensity' cannot be spatially varying (e.g. bitmap type)!");
             get_rgb(*o, "intensity", 1.f, E.radiance);
-            if (has(*o, "texture")) fail("The parameter 'texture' must be spatially varying (e.g. bitmap type)!");      // a colour: Properties makes a uniform texture of it
+            if (has(*o, "texture")) fail(text::spot_texture_uniform);      // a colour: Properties makes a uniform texture of it
             if (ObjP t = child(*o, "texture", "texture")) {
-                if (t->type == "bitmap") fail("unsupported: a bitmap texture as the spot emitter's 'texture' (bitmaps are held as one luminance float per texel, for bump maps only; a checkerboard is supported)");
+                if (t->type == "bitmap") fail(text::spot_texture_bitmap);
                 E.texture = make_texture(t);
-                if (S.textures[E.texture].type != LRT_TEX_CHECKERBOARD) fail("The parameter 'texture' must be spatially varying (e.g. bitmap type)!");
+                if (S.textures[E.texture].type != LRT_TEX_CHECKERBOARD) fail(text::spot_texture_uniform);
             }
             E.cutoff_angle = get_float(*o, "cutoff_angle", 20.0f);
             E.beam_width = get_float(*o, "beam_width", E.cutoff_angle * 3.0f / 4.0f);
             to_float(get_xform(*o, "to_world"), E.to_world);
             S.emitters.push_back(E); S.emdata.push_back(std::move(data));
             S.fix_pointers();                   // (the check below reads the description)
-            validate_delta_emitter(S.desc, (uint32_t) S.emitters.size() - 1);
+            check_delta_emitter(S.desc, (uint32_t) S.emitters.size() - 1);
             return;
         }
         else if (o->type == "directional") {    // src/emitters/directional.cpp:65-90; not an environment emitter
@@ -791,7 +793,7 @@ struct Loader {
             get_rgb(*o, "irradiance", 1.f, E.radiance);
             S.emitters.push_back(E); S.emdata.push_back(std::move(data));
             S.fix_pointers();
-            validate_delta_emitter(S.desc, (uint32_t) S.emitters.size() - 1);
+            check_delta_emitter(S.desc, (uint32_t) S.emitters.size() - 1);
             return;
         }
         else if (o->type == "envmap") {         // src/emitters/envmap.cpp:109-236
@@ -804,7 +806,7 @@ struct Loader {
             for (size_t p = 0; p < (size_t) im.width * im.height; ++p)
                 for (int c = 0; c < 3; ++c) { float v = im.data[p * im.channels + (im.channels >= 3 ? c : 0)]; if (im.srgb) v = srgb_to_linear(v); data[p * 3 + c] = v; }
         } else fail("unsupported emitter type \"" + o->type + "\"");
-        for (auto &e : S.emitters) if (e.type == LRT_EMITTER_ENVMAP || e.type == LRT_EMITTER_CONSTANT) fail("Only one environment emitter can be specified per scene.");
+        for (auto &e : S.emitters) if (e.type == LRT_EMITTER_ENVMAP || e.type == LRT_EMITTER_CONSTANT) fail(text::one_environment);
         S.emitters.push_back(E); S.emdata.push_back(std::move(data));
     }
 
@@ -829,7 +831,7 @@ struct Loader {
             if (get_bool(*film, "sample_border", false)) fail("hdrfilm: sample_border is not supported");
         } else { F.crop_width = F.width; F.crop_height = F.height; }
         if (F.crop_width <= 0 || F.crop_height <= 0 || F.crop_offset_x < 0 || F.crop_offset_y < 0 || F.crop_offset_x + F.crop_width > F.width || F.crop_offset_y + F.crop_height > F.height)
-            fail("Invalid crop window specification!");
+            fail(text::crop_window);
         S.desc.sample_count = 4; S.desc.sampler_seed = 0; S.desc.sampler_type = LRT_SAMPLER_INDEPENDENT;
         if (sampler) {
             if (sampler->type != "independent" && sampler->type != "ldsampler") fail("unsupported sampler type \"" + sampler->type + "\"");
@@ -862,10 +864,10 @@ struct Loader {
         else if (axis == "y") result = (180.0 / M_PI) * (2.0 * atan(tan(0.5 * fov * M_PI / 180.0) * aspect));
         else if (axis == "diagonal") { double diag = 2.0 * tan(0.5 * fov * M_PI / 180.0), width = diag / sqrt(1.0 + 1.0 / (aspect * aspect)); result = (180.0 / M_PI) * (2.0 * atan(width * 0.5)); }
         else fail("The 'fov_axis' parameter must be set to one of 'smaller', 'larger', 'diagonal', 'x', or 'y'!");
-        if (result <= 0.0 || result >= 180.0) fail("The horizontal field of view must be in the range [0, 180]!");
+        if (result <= 0.0 || result >= 180.0) fail(text::fov_range);
         C.fov_x = (float) result;
         to_float(get_xform(*o, "to_world"), C.to_world);
-        validate_sensor_film(S.desc);                       // perspective.cpp:144-145 (has_scale); the footprint key's range
+        check_camera_footprint(S.desc);                     // perspective.cpp:144-145 (has_scale); the footprint key's range
         C.medium = -1;
         for (auto &c : o->children) if (c.second->tag == "medium") C.medium = make_medium(c.second);
     }
@@ -1031,34 +1033,16 @@ struct Loader {
         }
         if (!have_sensor) fail("the scene has no sensor");
         for (auto &o : objs) if (o->tag == "integrator" && (o->type == "aov" || o->type == "moment")) make_integrator(o);
-        bool ext = false;                       // spheres / point / mesh emitters: prbvolpath's adjoint is built for triangles and rectangle / infinite emitters
-        for (auto &sh : S.shapes) ext = ext || sh.kind == LRT_SHAPE_SPHERE;
-        for (auto &e : S.emitters) ext = ext || e.type == LRT_EMITTER_POINT || (e.type == LRT_EMITTER_AREA && S.shapes[e.shape].kind == LRT_SHAPE_MESH);
-        bool delta_em = false;                  // spot / directional emitters: the EXT instances as well, and no adjoint either
-        for (auto &e : S.emitters) delta_em = delta_em || e.type == LRT_EMITTER_SPOT || e.type == LRT_EMITTER_DIRECTIONAL;
-        bool phase_ext = false;                 // a tabulated / Rayleigh / blended phase function on a medium that a shape or the sensor references (scene_prep.cpp)
-        auto ext_medium = [&](int m) { return m >= 0 && S.media[m].phase_index >= 0; };
-        for (auto &sh : S.shapes) phase_ext = phase_ext || ext_medium(sh.interior_medium) || ext_medium(sh.exterior_medium);
-        phase_ext = phase_ext || ext_medium(S.desc.sensor.medium);
-        bool rough = false;                     // a roughdielectric on a shape, nested or not: it runs on the EXT instances too (scene_prep.cpp)
-        for (auto &sh : S.shapes) if (sh.bsdf >= 0) {
-            const lrt_bsdf_desc &B = S.bsdfs[sh.bsdf];
-            rough = rough || B.type == LRT_BSDF_ROUGHDIELECTRIC || (B.type == LRT_BSDF_BUMPMAP && S.bsdfs[B.nested].type == LRT_BSDF_ROUGHDIELECTRIC);
-        }
-        bool smooth = false;                    // a conductor / plastic / twosided on a shape, nested or not: the EXT instances as well (scene_prep.cpp)
-        for (auto &sh : S.shapes) if (sh.bsdf >= 0) {
-            const lrt_bsdf_desc *B = &S.bsdfs[sh.bsdf];
-            if (B->type == LRT_BSDF_BUMPMAP) B = &S.bsdfs[B->nested];
-            smooth = smooth || B->type == LRT_BSDF_CONDUCTOR || B->type == LRT_BSDF_PLASTIC || B->type == LRT_BSDF_TWOSIDED;
-        }
+        S.fix_pointers();
+        // prbvolpath's adjoint is built for the base kernels' objects only (scene_check.h: SceneFeatures); the first group met is named
         bool prb = S.desc.integrator.type == LRT_INTEGRATOR_PRBVOLPATH;
         for (int k = 0; S.has_aov && k < S.aov.n_integrators; ++k) prb = prb || S.aov.integrators[k].type == LRT_INTEGRATOR_PRBVOLPATH;
-        if (ext && prb) fail("unsupported: prbvolpath on a scene with sphere shapes, point emitters or area emitters on meshes");
-        if (delta_em && prb) fail("unsupported: prbvolpath on a scene with a spot or directional emitter (no adjoint is built for them)");
-        if (rough && prb) fail("unsupported: prbvolpath on a scene with a roughdielectric BSDF (no adjoint is built for it)");
-        if (smooth && prb) fail("unsupported: prbvolpath on a scene with a conductor / plastic / twosided BSDF (no adjoint is built for them)");
-        if (phase_ext && prb) fail("unsupported: prbvolpath on a scene with a tabulated / Rayleigh / blended phase function (no adjoint is built for them)");
-        S.fix_pointers();
+        const SceneFeatures F = scene_features(S.desc);
+        if (prb && (F.sphere || F.point_emitter || F.mesh_emitter)) fail("unsupported: prbvolpath on a scene with sphere shapes, point emitters or area emitters on meshes");
+        if (prb && F.delta_emitter) fail("unsupported: prbvolpath on a scene with a spot or directional emitter (no adjoint is built for them)");
+        if (prb && F.rough_bsdf) fail("unsupported: prbvolpath on a scene with a roughdielectric BSDF (no adjoint is built for it)");
+        if (prb && F.smooth_bsdf) fail("unsupported: prbvolpath on a scene with a conductor / plastic / twosided BSDF (no adjoint is built for them)");
+        if (prb && F.phase_entry) fail("unsupported: prbvolpath on a scene with a tabulated / Rayleigh / blended phase function (no adjoint is built for them)");
     }
 };
 

@@ -1,6 +1,7 @@
 // Host half of the scene upload (scene_prep.h): the device image of an lrt_scene_desc as host arrays, the media tables, the resolved
 // render options, the tile lists and the proof predicate of the 64-byte records.  Plain host arithmetic, no HIP runtime call.
 #include "scene_prep.h"
+#include "scene_check.h"
 #include <functional>
 #include <cmath>
 #include <cstring>
@@ -70,22 +71,6 @@ static void build_camera(const lrt_scene_desc &d, DCamera &cam, DFilm &film) {
     film.fn = (int) ceilf(film.rf_radius - .5f); film.fcount = 2 * film.fn + 1;
 }
 
-void validate_sensor_film(const lrt_scene_desc &d) {
-    const float *m = d.sensor.to_world;
-    for (int i = 0; i < 3; ++i) for (int j = i; j < 3; ++j) {            // transform.h:242-254, float32 as the plugin's scalar transform
-        float sum = 0.f;
-        for (int k = 0; k < 3; ++k) sum += m[4 * i + k] * m[4 * j + k];
-        if (!(std::fabs(sum - (i == j ? 1.f : 0.f)) <= 1e-3f)) throw std::runtime_error("Scale factors in the camera-to-world transformation are not allowed!");
-    }
-    const lrt_film_desc &F = d.film;
-    if (F.rfilter == LRT_RFILTER_BOX) return;
-    // FilmFootprint::key(): origins lie in [-fn, size - fn], each packed as (coordinate + 0x4000) in 16 bits
-    const float radius = F.rfilter == LRT_RFILTER_GAUSSIAN ? 4.f * F.rfilter_param : F.rfilter_param;
-    if (!(radius <= 16384.f) || std::max(F.width, F.height) > 0xbfff)
-        throw std::runtime_error("film footprint out of range: a gaussian or tent filter needs a radius of at most 16384 pixels and a film of at most 49151 pixels per side (radius " +
-                                 std::to_string(radius) + ", film " + std::to_string(F.width) + " x " + std::to_string(F.height) + ")");
-}
-
 static void inverse3(const float *m16, float *out9) {    // double-precision inverse of the linear part
     double m[3][3]; for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) m[i][j] = m16[4 * i + j];
     double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) + m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
@@ -93,27 +78,6 @@ static void inverse3(const float *m16, float *out9) {    // double-precision inv
     out9[0] = (float) ((m[1][1] * m[2][2] - m[1][2] * m[2][1]) * id); out9[1] = (float) ((m[0][2] * m[2][1] - m[0][1] * m[2][2]) * id); out9[2] = (float) ((m[0][1] * m[1][2] - m[0][2] * m[1][1]) * id);
     out9[3] = (float) ((m[1][2] * m[2][0] - m[1][0] * m[2][2]) * id); out9[4] = (float) ((m[0][0] * m[2][2] - m[0][2] * m[2][0]) * id); out9[5] = (float) ((m[0][2] * m[1][0] - m[0][0] * m[1][2]) * id);
     out9[6] = (float) ((m[1][0] * m[2][1] - m[1][1] * m[2][0]) * id); out9[7] = (float) ((m[0][1] * m[2][0] - m[0][0] * m[2][1]) * id); out9[8] = (float) ((m[0][0] * m[1][1] - m[0][1] * m[1][0]) * id);
-}
-
-// A spot or directional emitter of a description (scene_prep.h).  The plugin only asserts cutoff >= beam in debug builds (spot.cpp:111);
-// here every value that would put an infinity or a NaN into the device table is refused by name.
-void validate_delta_emitter(const lrt_scene_desc &d, uint32_t i) {
-    const lrt_emitter_desc &E = d.emitters[i];
-    const char *who = E.type == LRT_EMITTER_SPOT ? "spot emitter" : "directional emitter";
-    double m[3][3]; bool finite = true;
-    for (int k = 0; k < 16; ++k) finite = finite && std::isfinite(E.to_world[k]);
-    for (int a = 0; a < 3; ++a) { for (int b = 0; b < 3; ++b) m[a][b] = E.to_world[4 * a + b]; finite = finite && std::isfinite(E.radiance[a]); }
-    const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) + m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
-    if (!finite || !(std::fabs(det) > 0.0) || !std::isfinite(1.0 / det)) throw std::runtime_error(std::string(who) + ": to_world must be finite and invertible, the value finite");
-    if (E.type != LRT_EMITTER_SPOT) return;
-    if (!(E.beam_width > 0.f) || !(E.beam_width <= E.cutoff_angle) || !(E.cutoff_angle <= 180.f))
-        throw std::runtime_error("spot emitter: 0 < beam_width <= cutoff_angle <= 180 degrees is required (beam_width " + std::to_string(E.beam_width) + ", cutoff_angle " + std::to_string(E.cutoff_angle) + ")");
-    if (E.texture < -1 || E.texture >= (int32_t) d.n_textures) throw std::runtime_error("spot emitter references an invalid texture");
-    if (E.texture < 0) return;
-    if (d.textures[E.texture].type == LRT_TEX_BITMAP)
-        throw std::runtime_error("unsupported: a bitmap texture as the spot emitter's 'texture' (bitmaps are held as one luminance float per texel, for bump maps only; a checkerboard is supported)");
-    if (d.textures[E.texture].type != LRT_TEX_CHECKERBOARD) throw std::runtime_error("The parameter 'texture' must be spatially varying (e.g. bitmap type)!");    // spot.cpp:98-100
-    if (!(E.cutoff_angle < 90.f)) throw std::runtime_error("spot emitter: cutoff_angle must be below 90 degrees when a texture is given (uv_factor = tan(cutoff_angle) must be positive and finite)");
 }
 
 static uint32_t log2i_ceil(uint32_t v) { uint32_t r = 0; while ((1u << r) < v) ++r; return r; }
@@ -419,33 +383,6 @@ float texture_mean(const lrt_texture_desc &T) {
     if (T.type == LRT_TEX_CHECKERBOARD) return .5f * (mean3(T.color0) + mean3(T.color1));   // checkerboard.cpp:112-114
     return mean3(T.color0);
 }
-void validate_smooth_bsdf(const lrt_scene_desc &d, uint32_t i) {
-    const lrt_bsdf_desc &B = d.bsdfs[i];
-    auto bad = [](const std::string &m) { throw std::runtime_error(m); };
-    auto tex = [&](int32_t t, bool required, const char *what) {
-        if (t < (required ? 0 : -1) || t >= (int32_t) d.n_textures) bad(std::string(what) + " references an invalid texture");
-        if (t >= 0 && d.textures[t].type == LRT_TEX_BITMAP) bad(std::string("unsupported: a bitmap texture as ") + what + " (bitmaps are supported as bump-map heights only)");
-    };
-    if (B.type == LRT_BSDF_CONDUCTOR) {
-        tex(B.specular_reflectance, true, "conductor specular_reflectance");
-        for (int k = 0; k < 3; ++k) if (!std::isfinite(B.eta_rgb[k]) || !std::isfinite(B.k_rgb[k])) bad("conductor with an index of refraction that is not finite");
-        // eta = k = 0 is no index of refraction: fresnel_conductor is 0 / 0 at normal incidence (term_3 = term_4 = 0, fresnel.h:111-114).  A zero-filled
-        // tail of the description lands here, so a conductor has to state its index (the plugin's default is 0 + 1i).
-        for (int k = 0; k < 3; ++k) if (B.eta_rgb[k] == 0.f && B.k_rgb[k] == 0.f) bad("conductor with eta = k = 0 in a channel (no index of refraction: its Fresnel term is 0 / 0 at normal incidence; the plugin's default is eta = 0, k = 1)");
-    } else if (B.type == LRT_BSDF_PLASTIC) {
-        if (!(B.eta > 0.f) || !std::isfinite(B.eta)) bad("The interior and exterior indices of refraction must be positive!");
-        tex(B.diffuse_reflectance, true, "plastic diffuse_reflectance"); tex(B.specular_reflectance, false, "plastic specular_reflectance");
-    } else if (B.type == LRT_BSDF_TWOSIDED) {
-        if (B.nested < 0) bad("A nested one-sided material is required!");
-        for (int32_t c : { B.nested, B.nested_back < 0 ? B.nested : B.nested_back }) {      // (nested_back = -1: one child)
-            if (c < 0 || (uint32_t) c >= d.n_bsdfs) bad("twosided references an invalid nested bsdf");
-            const int t = d.bsdfs[c].type;
-            if (t == LRT_BSDF_DIELECTRIC || t == LRT_BSDF_ROUGHDIELECTRIC || t == LRT_BSDF_NULL) bad("Only materials without a transmission component can be nested!");
-            if (t == LRT_BSDF_BUMPMAP || t == LRT_BSDF_TWOSIDED) bad(std::string("unsupported: a ") + (t == LRT_BSDF_BUMPMAP ? "bumpmap" : "twosided") + " nested in a twosided BSDF (its children are diffuse, conductor or plastic)");
-        }
-    }
-}
-
 void prepare_geometry(const lrt_scene_desc &d, const PrepOptions &opt, PreparedScene &P) {
     DScene &sc = P.sc;
     memset(&sc, 0, sizeof(sc));                          // the record is uploaded byte for byte: its padding is cleared too
@@ -468,36 +405,12 @@ void prepare_geometry(const lrt_scene_desc &d, const PrepOptions &opt, PreparedS
         for (int a = 0; a < 3; ++a) inv[4 * a + 3] = -(inv[4 * a] * md[3] + inv[4 * a + 1] * md[7] + inv[4 * a + 2] * md[11]);
         for (int k = 0; k < 12; ++k) o.to_object[k] = (float) inv[k];
         o.shape = i; o.flip_normals = s.flip_normals;
-        if (!(o.radius > 0.f) || !std::isfinite(o.radius)) throw std::runtime_error("sphere with a zero or invalid radius");
+        check_sphere_radius(o.radius);
         spheres.push_back(o);
     }
     sc.n_spheres = (uint32_t) spheres.size();
-    for (uint32_t i = 0; i < d.n_emitters; ++i) {
-        const lrt_emitter_desc &e = d.emitters[i];
-        if (e.type == LRT_EMITTER_POINT || e.type == LRT_EMITTER_SPOT || e.type == LRT_EMITTER_DIRECTIONAL || (e.type == LRT_EMITTER_AREA && e.shape >= 0 && (uint32_t) e.shape < d.n_shapes && d.shapes[e.shape].kind == LRT_SHAPE_MESH)) P.ext = true;
-    }
-    if (!spheres.empty()) P.ext = true;
-    // A roughdielectric on a shape, nested or not, runs on the EXT instances (an unreferenced one changes nothing: the scene keeps its kernels)
-    for (uint32_t i = 0; i < d.n_shapes; ++i) {
-        const int32_t b = d.shapes[i].bsdf;
-        if (b < 0 || (uint32_t) b >= d.n_bsdfs) continue;
-        const lrt_bsdf_desc &B = d.bsdfs[b];
-        if (B.type == LRT_BSDF_ROUGHDIELECTRIC || (B.type == LRT_BSDF_BUMPMAP && B.nested >= 0 && (uint32_t) B.nested < d.n_bsdfs && d.bsdfs[B.nested].type == LRT_BSDF_ROUGHDIELECTRIC)) P.ext = true;
-    }
-    // So does a conductor, a plastic or a twosided on a shape, alone or under a bumpmap (again, an unreferenced one changes nothing)
-    for (uint32_t i = 0; i < d.n_shapes; ++i) {
-        const int32_t b = d.shapes[i].bsdf;
-        if (b < 0 || (uint32_t) b >= d.n_bsdfs) continue;
-        const lrt_bsdf_desc *B = &d.bsdfs[b];
-        if (B->type == LRT_BSDF_BUMPMAP && B->nested >= 0 && (uint32_t) B->nested < d.n_bsdfs) B = &d.bsdfs[B->nested];
-        if (B->type == LRT_BSDF_CONDUCTOR || B->type == LRT_BSDF_PLASTIC || B->type == LRT_BSDF_TWOSIDED) P.ext = P.smooth_bsdf = true;
-    }
-    // So does a tabulated / Rayleigh / blended phase function on a medium that a shape or the sensor references (again, an unreferenced one changes nothing)
-    {
-        auto ext_medium = [&](int32_t m) { return m >= 0 && (uint32_t) m < d.n_media && medium_has_phase_entry(d, (uint32_t) m); };
-        if (ext_medium(d.sensor.medium)) P.ext = true;
-        for (uint32_t i = 0; i < d.n_shapes; ++i) if (ext_medium(d.shapes[i].interior_medium) || ext_medium(d.shapes[i].exterior_medium)) P.ext = true;
-    }
+    const SceneFeatures features = scene_features(d);      // any of them: the EXT kernel instances (scene_check.h)
+    P.ext = features.any(); P.smooth_bsdf = features.smooth_bsdf;
     // ---- acceleration structure
     // Leaf size: the smallest of 2, 3, 4, 6, 8, 12, 16 triangles whose BVH image fits the LDS next to the traversal stacks (fatter
     // leaves = fewer nodes: more triangle tests per leaf, but every fetch of the traversal stays in LDS; Liver-MultiMesh's two meshes
@@ -585,26 +498,15 @@ void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedSc
              : B.type == LRT_BSDF_PLASTIC ? (PREP_F_DELTA | PREP_F_SMOOTH) : PREP_F_NULL;
     };
     bool any_smooth_bsdf = false;
-    for (uint32_t i = 0; i < d.n_bsdfs; ++i) if (d.bsdfs[i].type == LRT_BSDF_CONDUCTOR || d.bsdfs[i].type == LRT_BSDF_PLASTIC || d.bsdfs[i].type == LRT_BSDF_TWOSIDED) { validate_smooth_bsdf(d, i); any_smooth_bsdf = true; }
+    for (uint32_t i = 0; i < d.n_bsdfs; ++i) if (d.bsdfs[i].type == LRT_BSDF_CONDUCTOR || d.bsdfs[i].type == LRT_BSDF_PLASTIC || d.bsdfs[i].type == LRT_BSDF_TWOSIDED) { check_smooth_bsdf(d, i); any_smooth_bsdf = true; }
     if (any_smooth_bsdf) P.bsdf_ext.assign(d.n_bsdfs, DBsdfExt{});
     for (uint32_t i = 0; i < d.n_bsdfs; ++i) {
         const lrt_bsdf_desc &B = d.bsdfs[i];
         DBsdf &o = bsdfs[i]; memset(&o, 0, sizeof(o));
         o.type = B.type; o.reflectance = B.reflectance; o.nested = B.nested; o.texture = B.texture; o.eta = B.eta; o.scale = B.scale;
-        if (B.type == LRT_BSDF_BUMPMAP) {
-            if (B.nested < 0 || (uint32_t) B.nested >= d.n_bsdfs || d.bsdfs[B.nested].type == LRT_BSDF_BUMPMAP) throw std::runtime_error("bumpmap: invalid nested BSDF");
-            if (d.bsdfs[B.nested].type == LRT_BSDF_TWOSIDED) throw std::runtime_error("unsupported: a twosided BSDF nested in a bumpmap");
-            bsdfs[i].flags = leaf_flags((uint32_t) B.nested);
-        } else bsdfs[i].flags = leaf_flags(i);
-        if (B.type == LRT_BSDF_DIFFUSE && (B.reflectance < 0 || (uint32_t) B.reflectance >= d.n_textures || d.textures[B.reflectance].type == LRT_TEX_BITMAP))
-            throw std::runtime_error("unsupported: a bitmap texture as diffuse reflectance (bitmaps are supported as bump-map heights only)");
+        bsdfs[i].flags = leaf_flags(B.type == LRT_BSDF_BUMPMAP ? (uint32_t) B.nested : i);      // (indices and nesting: check_bsdf, or the loader, has seen them)
         if (B.type == LRT_BSDF_NULL) sc.has_null_bsdf = 1;
         if (B.type == LRT_BSDF_ROUGHDIELECTRIC) {     // the fields share the words a roughdielectric leaves unused (device_types.h)
-            for (int32_t t : { B.specular_reflectance, B.specular_transmittance }) {
-                if (t < -1 || t >= (int32_t) d.n_textures) throw std::runtime_error("roughdielectric references an invalid texture");
-                if (t >= 0 && d.textures[t].type == LRT_TEX_BITMAP)
-                    throw std::runtime_error("unsupported: a bitmap texture as roughdielectric specular_reflectance / specular_transmittance");
-            }
             bsdfs[i].specular_reflectance = B.specular_reflectance; bsdfs[i].specular_transmittance = B.specular_transmittance;
             bsdfs[i].alpha_u = std::max(B.alpha_u, 1e-4f); bsdfs[i].alpha_v = std::max(B.alpha_v, 1e-4f);      // MicrofacetDistribution::configure (microfacet.h:425-428)
             bsdfs[i].micro = (B.distribution == 1 ? LRT_MICRO_GGX : 0) | (B.sample_visible ? LRT_MICRO_VISIBLE : 0);
@@ -636,13 +538,13 @@ void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedSc
         } else { E.bsphere_c[0] = E.bsphere_c[1] = E.bsphere_c[2] = 0.f; E.bsphere_r = ray_eps; }
     }
     // ---- media: what the scene as a whole needs to know about them (the tables themselves: prepare_media)
-    if (d.n_media > 64) throw std::runtime_error("at most 64 media are supported");
+    check_media_count(d);
     prepare_phases(d, P.phases, P.phase_pool);
     for (uint32_t i = 0; i < d.n_media; ++i) {
         const lrt_medium_desc &M = d.media[i];
         if (M.type == LRT_MEDIUM_HOMOGENEOUS || M.type == LRT_MEDIUM_HETEROGENEOUS) P.has_non_bio = true;
         if (M.type != LRT_MEDIUM_HETEROGENEOUS) continue;
-        if (!M.grid_data || M.grid_res[0] < 1 || M.grid_res[1] < 1 || M.grid_res[2] < 1 || !(M.grid_max > 0.f)) throw std::runtime_error("heterogeneous medium without a valid grid");
+        check_medium_grid(M);                                   // stricter than check_medium: grid_max > 0
         P.has_het = true;
     }
     for (uint32_t i = 0; i < d.n_shapes; ++i) for (int m : { d.shapes[i].interior_medium, d.shapes[i].exterior_medium })
@@ -655,8 +557,7 @@ void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedSc
         o.type = S.type; o.shape = S.shape; o.scale = S.scale; for (int k = 0; k < 3; ++k) o.radiance[k] = S.radiance[k];
         if (S.type == LRT_EMITTER_AREA) {
             P.has_area_emitter = true;
-            const lrt_shape_desc &sd = d.shapes[S.shape];
-            if (sd.kind == LRT_SHAPE_SPHERE) throw std::runtime_error("unsupported: an area emitter on a sphere (area emitters are supported on rectangles and triangle meshes)");
+            const lrt_shape_desc &sd = d.shapes[S.shape];      // (a rectangle or a mesh: check_emitter, or the loader, has refused a sphere)
             if (sd.kind == LRT_SHAPE_MESH) {                   // src/render/mesh.cpp:449-482: the area table and its CDF (host_scene.h)
                 MeshEmitterTable T; mesh_emitter_table(d.positions, d.faces, sd.first_face, sd.n_faces, "shapes[" + std::to_string(S.shape) + "]", T);
                 DMeshEmitter &M = mesh_em[i];
@@ -677,7 +578,7 @@ void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedSc
             memcpy(o.to_world, S.to_world, sizeof(float) * 12);
         } else if (S.type == LRT_EMITTER_SPOT || S.type == LRT_EMITTER_DIRECTIONAL) {
             if (P.delta_emitters.empty()) P.delta_emitters.assign(d.n_emitters, DDeltaEmitter{});
-            validate_delta_emitter(d, i);
+            check_delta_emitter(d, i);
             DDeltaEmitter &D = P.delta_emitters[i]; D.texture = -1;
             memcpy(o.to_world, S.to_world, sizeof(float) * 12);
             if (S.type == LRT_EMITTER_SPOT) {                   // src/emitters/spot.cpp:104-112, in float32 as the plugin's ScalarFloat members
@@ -783,45 +684,16 @@ void phase_table(const float *values, size_t size, PhaseTable &out) {
         if (y0 < 0. || y1 < 0.) throw std::runtime_error("ContinuousDistribution: entries must be non-negative!");
         else if (value > 0.) { if (vx == (uint32_t) -1) vx = (uint32_t) i; vy = (uint32_t) i; }
     }
-    if (vx == (uint32_t) -1 || vy == (uint32_t) -1) throw std::runtime_error("ContinuousDistribution: no probability mass found!");
+    if (vx == (uint32_t) -1 || vy == (uint32_t) -1) throw std::runtime_error(text::no_probability_mass);
     out.valid_x = vx; out.valid_y = vy;
     out.integral = out.cdf[vy]; out.normalization = 1.f / out.integral;
     out.interval_size = (float) interval_size; out.inv_interval_size = 1.f / out.interval_size;
 }
 
-void validate_phases(const lrt_scene_desc &d) {
-    auto bad = [](const std::string &m) { throw std::runtime_error("phase table: " + m); };
-    if (d.n_phases && !d.phases) bad("null array");
-    for (uint32_t i = 0; i < d.n_phases; ++i) {
-        const lrt_phase_desc &Q = d.phases[i];
-        if (Q.type < LRT_PHASE_ISOTROPIC || Q.type > LRT_PHASE_BLEND) bad("invalid phase function");
-        if (Q.type == LRT_PHASE_HG && !(Q.g > -1.f && Q.g < 1.f)) bad("The asymmetry parameter must lie in the interval (-1, 1)!");
-        if (Q.type == LRT_PHASE_TABULATED) {
-            if (Q.n_values && !Q.values) bad("tabulated phase function without values");
-            for (uint32_t k = 0; k < Q.n_values; ++k) if (!std::isfinite(Q.values[k])) bad("tabulated phase function with a value that is not finite");
-            PhaseTable T; phase_table(Q.values, Q.n_values, T);
-            if (!(T.integral > 0.f) || !std::isfinite(T.integral)) bad("ContinuousDistribution: no probability mass found!");
-        }
-        if (Q.type == LRT_PHASE_BLEND) {
-            if (!(Q.weight == Q.weight)) bad("blendphase with a weight that is not a number");
-            for (int32_t c : { Q.child[0], Q.child[1] }) {
-                if (c < 0 || (uint32_t) c >= d.n_phases) bad("blendphase references an invalid child");
-                if (d.phases[c].type == LRT_PHASE_BLEND) throw std::runtime_error("unsupported: a blendphase as the child of a blendphase (one level is built)");
-            }
-        }
-    }
-    for (uint32_t m = 0; m < d.n_media && d.n_phases; ++m) {
-        const int32_t ix = d.media[m].phase_index;
-        if (ix < -1 || ix >= (int32_t) d.n_phases) bad("medium references an invalid entry");
-        // (isotropic / hg entries are a blend's children: a medium that scatters by one of them says so in `phase` / `g`, keeps its parameter key and its kernels)
-        if (ix >= 0 && d.phases[ix].type < LRT_PHASE_TABULATED) bad("medium references an isotropic / hg entry (a medium's entry is tabulated, rayleigh or blend; use the medium's `phase` / `g`)");
-    }
-}
-
 void prepare_phases(const lrt_scene_desc &d, std::vector<DPhase> &phases, std::vector<float> &pool) {
     phases.clear(); pool.clear();
     if (!d.n_phases) return;
-    validate_phases(d);
+    check_phase_table(d);
     phases.resize(d.n_phases);
     for (uint32_t i = 0; i < d.n_phases; ++i) {
         const lrt_phase_desc &Q = d.phases[i]; DPhase &o = phases[i]; memset(&o, 0, sizeof(o));
@@ -957,3 +829,7 @@ bool closed_records(const lrt_scene_desc &d, int sensor_medium) {
 }
 
 } // namespace lrt
+
+// The scene checks are compiled as part of this unit: the preparation, the loader and the ABI all call them, and the host programs under tests/
+// that build the preparation from an explicit source list (scene_prep.cpp, bvh.cpp, loader.cpp, xml.cpp, image_io.cpp) keep linking as they are.
+#include "scene_check.cpp"

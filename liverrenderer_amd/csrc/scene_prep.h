@@ -52,6 +52,8 @@ struct PreparedScene {
 // The two halves of prepare_scene, for a caller that has work to start in between (device.hip launches k_build_dist_grid after the first, so that
 // the kernel runs while the host prepares the rest, as it always did).  prepare_geometry: spheres, `ext`, the BVH with its leaf-size search,
 // the LDS image, the root leaf and counts, the distance field's geometry.  prepare_shading: everything else; it reads P.spheres for the bounds.
+// Precondition of all three: the description has passed the XML loader or validate_scene_desc (scene_check.h).  They follow its indices (a bumpmap's
+// child, texture and shape references) without looking at them again.
 void prepare_geometry(const lrt_scene_desc &d, const PrepOptions &opt, PreparedScene &P);
 void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedScene &P);
 PreparedScene prepare_scene(const lrt_scene_desc &d, const PrepOptions &opt);
@@ -80,28 +82,11 @@ void prepare_media(const lrt_scene_desc &d, float bsphere_r, std::vector<DMedium
 // ("needs at least two entries", "entries must be non-negative", "no probability mass found").
 struct PhaseTable { std::vector<float> cdf; float interval_size = 0.f, inv_interval_size = 0.f, integral = 0.f, normalization = 0.f; uint32_t valid_x = 0, valid_y = 0; };
 void phase_table(const float *values, size_t n, PhaseTable &out);
-// Every index, count and value of the description's phase table and of the media's indices into it (lrt_scene_from_desc and the upload
-// share it); `unsupported: ...` for a blend as a blend's child.
-void validate_phases(const lrt_scene_desc &d);
 // does medium m scatter by an entry of the table?  (n_phases = 0: the indices are not read)
 inline bool medium_has_phase_entry(const lrt_scene_desc &d, uint32_t m) { return d.n_phases > 0 && d.media[m].phase_index >= 0; }
-// DScene::phases and phase_pool: an entry per description entry, the tabulated ones with their interval records and cdf
+// DScene::phases and phase_pool: an entry per description entry, the tabulated ones with their interval records and cdf (after check_phase_table)
 void prepare_phases(const lrt_scene_desc &d, std::vector<DPhase> &phases, std::vector<float> &pool);
 
-// Emitter i of the description, an LRT_EMITTER_SPOT or LRT_EMITTER_DIRECTIONAL: a finite, invertible to_world; a spot's angles
-// (0 < beam_width <= cutoff_angle <= 180, cutoff_angle < 90 with a texture) and its texture's index and type.  Throws the text
-// (lrt_scene_from_desc and the preparation share it); `unsupported: ...` for a bitmap texture, the plugin's own text for a uniform one.
-void validate_delta_emitter(const lrt_scene_desc &d, uint32_t i);
-
-// The sensor's to_world and the film's extent (the XML loader and lrt_scene_from_desc share it).  Throws the plugin's text for a
-// camera-to-world transform with scale factors (src/sensors/perspective.cpp:144-145; Transform::has_scale,
-// include/mitsuba/core/transform.h:242-254: |M M^T - I| > 1e-3 in an entry of the linear part, so a mirrored orthonormal frame passes),
-// and refuses by name a wide-filter film whose size plus footprint leaves what FilmFootprint::key() (film.h) packs into 16 bits per axis.
-void validate_sensor_film(const lrt_scene_desc &d);
-
-// BSDF i of the description, an LRT_BSDF_CONDUCTOR, _PLASTIC or _TWOSIDED: its texture and child indices and what the loader refuses
-// (lrt_scene_from_desc and the preparation share it).  Throws the text: the plugin's own where it has one, `unsupported: ...` for what is not built.
-void validate_smooth_bsdf(const lrt_scene_desc &d, uint32_t i);
 // SmoothPlastic::parameters_changed (src/bsdfs/plastic.cpp:192-207) in float32, as the plugin's scalar constructor computes it
 struct PlasticConstants { float inv_eta_2, fdr_int, fdr_ext, specular_sampling_weight; };
 PlasticConstants plastic_constants(float eta, float d_mean, float s_mean);
