@@ -307,6 +307,8 @@ typedef struct {
                                  goes on, an emitter hit that needs its MIS weight); the render then fails  [v108] */
     uint64_t n_proven;        /* 64-byte records: records read whose segment was proven free of surfaces (by the distance
                                  field or the per-face cone table) and ran without a ray query; 0 for every other kernel  [v115] */
+    uint64_t n_primary_entry; /* 64-byte records: camera lanes whose first ray query started below the BVH's root, or was skipped because no
+                                 triangle projects into the pixel (the per-pixel primary entry); 0 for every other kernel  [v121] */
 } lrt_render_stats;
 
 typedef struct {
@@ -321,7 +323,7 @@ typedef struct {
 typedef struct lrt_scene lrt_scene;
 
 LRT_API const char *lrt_last_error(void);
-LRT_API int         lrt_version(void);   /* 119: the conductor, plastic and twosided BSDFs (LRT_BSDF_CONDUCTOR / _PLASTIC / _TWOSIDED, the fields after `specular_transmittance` of lrt_bsdf_desc); 118: lrt_medium_probe; the loader refuses a singular volume to_world and an empty use_grid_bbox header box; 117: spot and directional emitters (LRT_EMITTER_SPOT / _DIRECTIONAL, lrt_emitter_desc grows by cutoff_angle, beam_width, texture: rebuild hosts against this header); 116: tabulated, Rayleigh and blended phase functions (lrt_phase_desc, lrt_scene_desc.phases, lrt_medium_desc.phase_index), lrt_phase_probe, lrt_math_eval fn 11; 115: lrt_render_stats.n_proven appended (lrt_render_stats_get writes 8 bytes more: rebuild hosts against this header); 114: the roughdielectric BSDF (LRT_BSDF_ROUGHDIELECTRIC, the fields after `scale` of lrt_bsdf_desc), lrt_math_eval fn 9 / 10; 113: lrt_bsdf_probe; 112:lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
+LRT_API int         lrt_version(void);   /* 121: lrt_render_stats.n_primary_entry appended (lrt_render_stats_get writes 8 bytes more: rebuild hosts against this header); 119: the conductor, plastic and twosided BSDFs (LRT_BSDF_CONDUCTOR / _PLASTIC / _TWOSIDED, the fields after `specular_transmittance` of lrt_bsdf_desc); 118: lrt_medium_probe; the loader refuses a singular volume to_world and an empty use_grid_bbox header box; 117: spot and directional emitters (LRT_EMITTER_SPOT / _DIRECTIONAL, lrt_emitter_desc grows by cutoff_angle, beam_width, texture: rebuild hosts against this header); 116: tabulated, Rayleigh and blended phase functions (lrt_phase_desc, lrt_scene_desc.phases, lrt_medium_desc.phase_index), lrt_phase_probe, lrt_math_eval fn 11; 115: lrt_render_stats.n_proven appended (lrt_render_stats_get writes 8 bytes more: rebuild hosts against this header); 114: the roughdielectric BSDF (LRT_BSDF_ROUGHDIELECTRIC, the fields after `scale` of lrt_bsdf_desc), lrt_math_eval fn 9 / 10; 113: lrt_bsdf_probe; 112:lrt_render_backward_grid, "<id>.sigma_t.data" parameter keys; 111: lrt_envmap_probe; 110: the moment integrator (lrt_render_moment, lrt_moment_desc); 109: the guided denoiser (lrt_denoiser_create, lrt_denoise, lrt_denoiser_free); 108: lrt_render_stats.record_bytes / n_closed_guard; 107: area emitters on triangle meshes, lrt_emitter_probe; 106: spheres, point emitters */
 
 LRT_API lrt_status lrt_scene_load_xml(const char *path, const char *const *defines,
                                       int n_defines, lrt_scene **out);
@@ -343,6 +345,11 @@ LRT_API void       lrt_scene_free(lrt_scene *scene);
 LRT_API lrt_status lrt_render(lrt_scene *scene, const lrt_render_opts *opts,
                               float *film_raw, float *image);
 LRT_API lrt_status lrt_render_stats_get(const lrt_scene *scene, lrt_render_stats *out);
+/* The per-pixel primary entry of the scene's device image [v121]: out[y * crop_w + x] = the 16-bit item at which a camera ray of that pixel starts
+ * its BVH traversal in the 64-byte-record volpath kernels: 0 = the root (also: the image has no table), 0x8000 | s = the leaf whose first
+ * triangle slot is s, 0xffff = no triangle can be hit, any other value = that inner node.  n_pixels must be crop_w * crop_h.  Test access. */
+LRT_API lrt_status lrt_primary_entry_get(lrt_scene *scene, uint16_t *out, uint64_t n_pixels, int device);
+
 LRT_API lrt_status lrt_film_develop(lrt_scene *scene, const float *film_raw, float *image,
                                     int on_device);
 

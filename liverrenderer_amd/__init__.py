@@ -458,6 +458,13 @@ class Scene:
         return {"sigma_t": np.array(out.d_sigma_t[:], dtype=np.float32), "albedo": np.array(out.d_albedo[:], dtype=np.float32),
                 "g": float(out.d_g), "sigma_t_data": res}
 
+    def primary_entry(self, device=0):
+        """The per-pixel primary entry of the device image (lrt_primary_entry_get): uint16 (crop_h, crop_w); all zero when the image has no table."""
+        h, w, _ = self.film_shape()
+        out = np.zeros((h, w), dtype=np.uint16)
+        _lib.check(self._lib.lrt_primary_entry_get(self._h, out.ctypes.data, h * w, device))
+        return out
+
     def stats(self):
         s = _lib.RenderStats()
         _lib.check(self._lib.lrt_render_stats_get(self._h, C.byref(s)))

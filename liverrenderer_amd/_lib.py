@@ -126,7 +126,7 @@ class RenderOpts(C.Structure):
 class RenderStats(C.Structure):
     _fields_ = [("n_samples", C.c_uint64), ("n_iter", C.c_uint64), ("n_shadow", C.c_uint64), ("n_launches", C.c_uint64),
                 ("n_records", C.c_uint64), ("kernel_ms", C.c_double), ("total_ms", C.c_double), ("lds_resident", C.c_uint64),
-                ("record_bytes", C.c_uint64), ("n_closed_guard", C.c_uint64), ("n_proven", C.c_uint64)]
+                ("record_bytes", C.c_uint64), ("n_closed_guard", C.c_uint64), ("n_proven", C.c_uint64), ("n_primary_entry", C.c_uint64)]
 
 
 class ParamGrads(C.Structure):
@@ -215,6 +215,7 @@ def lib():
     L.lrt_math_eval.argtypes = [C.c_int, P(C.c_float), P(C.c_float), C.c_uint32, P(C.c_float), P(C.c_float), C.c_int]
     L.lrt_render_stats_get.argtypes = [C.c_void_p, P(RenderStats)]
     L.lrt_film_develop.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.lrt_primary_entry_get.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
     L.lrt_render_samples.argtypes = [C.c_void_p, P(RenderOpts), C.c_uint64, C.c_uint32, C.c_void_p]
     L.lrt_render_backward.argtypes = [C.c_void_p, P(RenderOpts), C.c_void_p, P(ParamGrads)]
     L.lrt_render_backward_grid.argtypes = [C.c_void_p, P(RenderOpts), C.c_void_p, P(ParamGrads), C.c_void_p]
@@ -269,7 +270,7 @@ EXPORTED_SYMBOLS = ["lrt_last_error", "lrt_version", "lrt_scene_load_xml", "lrt_
                     "lrt_vae_model_create", "lrt_vae_model_free", "lrt_vae_scatter",
                     "lrt_scene_aov_get", "lrt_aov_channel_name", "lrt_render_aov", "lrt_render_aov_samples", "lrt_image_write_exr_channels",
                     "lrt_denoiser_create", "lrt_denoise", "lrt_denoiser_free", "lrt_denoiser_get", "lrt_image_read_named", "lrt_image_free_names",
-                    "lrt_scene_moment_get", "lrt_moment_channel_name", "lrt_render_moment", "lrt_render_moment_samples"]
+                    "lrt_scene_moment_get", "lrt_moment_channel_name", "lrt_render_moment", "lrt_render_moment_samples", "lrt_primary_entry_get"]
 
 
 def bsdf_probe_fields(out):

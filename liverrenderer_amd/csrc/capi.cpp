@@ -32,7 +32,7 @@ static lrt_status fail(lrt_status st, const std::string &msg) { g_error = msg; r
 extern "C" {
 
 const char *lrt_last_error(void) { return g_error.c_str(); }
-int lrt_version(void) { return 120; }    // 1.20: lrt_sensor_probe; a camera to_world with scale factors and a film whose size plus filter radius leaves the footprint key's range are refused; 1.19: the conductor, plastic and twosided BSDFs; 1.18: lrt_medium_probe; a singular volume to_world and an empty use_grid_bbox header box are refused; 1.17: spot and directional emitters (lrt_emitter_desc::cutoff_angle / beam_width / texture); 1.16: tabulated / Rayleigh / blended phase functions (lrt_scene_desc.phases), lrt_phase_probe, lrt_math_eval fn 11 (cbrt); 1.15: lrt_render_stats::n_proven (the struct grows by 8 bytes); 1.14: the roughdielectric BSDF, lrt_math_eval fn 9 (erf) / 10 (erfinv); 1.13: lrt_bsdf_probe; 1.12: lrt_render_backward_grid, "<id>.sigma_t.data" in lrt_param_set / lrt_param_get; 1.11: lrt_envmap_probe; 1.10: the moment integrator (lrt_render_moment, lrt_render_moment_samples, lrt_scene_moment_get, lrt_moment_channel_name); 1.9: the guided denoiser (lrt_denoiser_create / lrt_denoise / lrt_denoiser_free), lrt_image_read_named; 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
+int lrt_version(void) { return 121; }    // 1.21: lrt_render_stats::n_primary_entry (the per-pixel primary entry of the 64-byte-record volpath kernels; LRT_NO_PRIMARY_ENTRY); 1.20: lrt_sensor_probe; a camera to_world with scale factors and a film whose size plus filter radius leaves the footprint key's range are refused; 1.19: the conductor, plastic and twosided BSDFs; 1.18: lrt_medium_probe; a singular volume to_world and an empty use_grid_bbox header box are refused; 1.17: spot and directional emitters (lrt_emitter_desc::cutoff_angle / beam_width / texture); 1.16: tabulated / Rayleigh / blended phase functions (lrt_scene_desc.phases), lrt_phase_probe, lrt_math_eval fn 11 (cbrt); 1.15: lrt_render_stats::n_proven (the struct grows by 8 bytes); 1.14: the roughdielectric BSDF, lrt_math_eval fn 9 (erf) / 10 (erfinv); 1.13: lrt_bsdf_probe; 1.12: lrt_render_backward_grid, "<id>.sigma_t.data" in lrt_param_set / lrt_param_get; 1.11: lrt_envmap_probe; 1.10: the moment integrator (lrt_render_moment, lrt_render_moment_samples, lrt_scene_moment_get, lrt_moment_channel_name); 1.9: the guided denoiser (lrt_denoiser_create / lrt_denoise / lrt_denoiser_free), lrt_image_read_named; 1.8: lrt_render_stats.record_bytes, n_closed_guard; 1.7: area emitters on triangle meshes, lrt_emitter_probe; 1.6: sphere shapes and point emitters; 1.5: the aov integrator (lrt_render_aov, lrt_aov_desc), named multi-channel EXR writer; 1.2: bio media fields in lrt_medium_desc, biovolpath integrators, grad_medium in lrt_render_opts; 1.3: lrt_render_stats.lds_resident; 1.4: lrt_render_multi / lrt_render_backward_multi, PRB through heterogeneous media
 
 static std::vector<std::pair<std::string, std::string>> parse_defines(const char *const *defines, int n) {
     std::vector<std::pair<std::string, std::string>> r;
@@ -293,6 +293,18 @@ lrt_status lrt_trace(lrt_scene *scene, const lrt_rays_soa *rays, const lrt_hits_
     LRT_TRY
         ensure_device(scene, -1);
         device_trace(scene->dev, rays, hits, n, any_hit);
+        return LRT_OK;
+    LRT_CATCH
+}
+
+lrt_status lrt_primary_entry_get(lrt_scene *scene, uint16_t *out, uint64_t n_pixels, int device) {
+    if (!scene || (!out && n_pixels)) return fail(LRT_ERR_INVALID, "lrt_primary_entry_get: null argument");
+    LRT_TRY
+        ensure_device(scene, device);
+        const std::vector<uint16_t> &t = device_primary_entry(scene->dev);
+        const uint64_t want = (uint64_t) scene->st.desc.film.crop_width * (uint64_t) scene->st.desc.film.crop_height;
+        if (n_pixels != want) return fail(LRT_ERR_INVALID, "lrt_primary_entry_get: n_pixels is not the crop window's pixel count");
+        for (uint64_t i = 0; i < n_pixels; ++i) out[i] = t.empty() ? (uint16_t) 0 : t[i];
         return LRT_OK;
     LRT_CATCH
 }

@@ -63,7 +63,7 @@ static lrt_render_opts default_opts() { return lrt_render_opts{ -1, -2, -1, -1, 
 static void add_stats(lrt_render_stats &total, const lrt_render_stats &s) {
     total.n_samples += s.n_samples; total.n_iter += s.n_iter; total.n_shadow += s.n_shadow; total.n_launches += s.n_launches;
     total.n_records += s.n_records; total.kernel_ms += s.kernel_ms; total.total_ms += s.total_ms;
-    total.record_bytes = s.record_bytes; total.n_closed_guard += s.n_closed_guard; total.n_proven += s.n_proven;
+    total.record_bytes = s.record_bytes; total.n_closed_guard += s.n_closed_guard; total.n_proven += s.n_proven; total.n_primary_entry += s.n_primary_entry;
 }
 
 #define LRT_LAUNCH_SLOTS 64
@@ -86,6 +86,7 @@ struct DeviceScene {
     double *d_grads = nullptr; float *wfilm = nullptr; size_t wfilm_floats = 0; float *grad_image = nullptr; size_t grad_floats = 0;
     DCounters *counters = nullptr;
     DCounters *h_counters = nullptr;       // pinned
+    std::vector<uint16_t> primary_tab;     // host copy of DScene::primary_tab (lrt_primary_entry_get)
     float *film = nullptr; size_t film_floats = 0;
     float *image = nullptr; size_t image_floats = 0;
     unsigned long long *pass_state[2] = { nullptr, nullptr }; size_t pass_state_lanes[2] = { 0, 0 };   // multi-pass renders: per-lane PCG32 states
@@ -324,6 +325,8 @@ DeviceScene *device_scene_create(const lrt_scene_desc &d, int device) {
     sc.delta_emitters = P.delta_emitters.empty() ? nullptr : up(P.delta_emitters);
     sc.bsdf_ext = P.bsdf_ext.empty() ? nullptr : up(P.bsdf_ext);
     sc.cone_tab = P.cone_tab.empty() ? nullptr : (const uint2 *) up(P.cone_tab);      // (sc.cone_enabled: set by the preparation with the table)
+    sc.primary_tab = P.primary_tab.empty() ? nullptr : (const uint16_t *) up(P.primary_tab);      // (sc.primary_enabled alike; the preparation has validated every item)
+    D->primary_tab = P.primary_tab;
     sc.phases = P.phases.empty() ? nullptr : up(P.phases);
     sc.phase_pool = P.phase_pool.empty() ? nullptr : up(P.phase_pool);
     sc.env_data = (const float4 *) up(P.env_data);
@@ -566,6 +569,7 @@ static void run_wavefront(DeviceScene *D, const lrt_scene_desc &d, const Resolve
     finish_stats(D, log, e_begin, e_end, n_lanes, stats);
     stats.n_closed_guard = D->h_counters->n_closed_guard;
     stats.n_proven = D->h_counters->n_proven;
+    stats.n_primary_entry = D->h_counters->n_primary_entry;
     if (stats.n_closed_guard)
         throw std::runtime_error("64-byte path records: " + std::to_string(stats.n_closed_guard) + " trips broke the premise of the layout (radiance before a path's last trip, "
                                  "or an emitter hit that needs its MIS weight); the scene test in closed_records() is wrong for this scene: LRT_NO_CLOSED_RECORDS=1 renders it with 80-byte records");
@@ -671,6 +675,8 @@ void device_render_moment_samples(DeviceScene *D, const lrt_scene_desc &d, const
     HIP_CHECK(hipMemcpyAsync(out, d_m, (size_t) n * 24, hipMemcpyDeviceToHost, D->stream));
     HIP_CHECK(hipStreamSynchronize(D->stream));
 }
+
+const std::vector<uint16_t> &device_primary_entry(const DeviceScene *D) { return D->primary_tab; }
 
 void device_develop(DeviceScene *D, const float *film_raw, float *image, int on_device) {
     HIP_CHECK(hipSetDevice(D->device));
@@ -1063,7 +1069,7 @@ void device_render_multi(std::vector<DeviceScene *> &devs, MultiContext *&ctx, c
     develop_and_download(D0, films[0], film_raw, image, film_floats, image_floats, on_device);
     lrt_render_stats total{};
     for (auto &x : st) { total.n_samples += x.n_samples; total.n_iter += x.n_iter; total.n_shadow += x.n_shadow; total.n_launches += x.n_launches; total.n_records += x.n_records;
-                         total.kernel_ms = std::max(total.kernel_ms, x.kernel_ms); total.lds_resident = x.lds_resident; total.record_bytes = x.record_bytes; total.n_closed_guard += x.n_closed_guard; total.n_proven += x.n_proven; }
+                         total.kernel_ms = std::max(total.kernel_ms, x.kernel_ms); total.lds_resident = x.lds_resident; total.record_bytes = x.record_bytes; total.n_closed_guard += x.n_closed_guard; total.n_proven += x.n_proven; total.n_primary_entry += x.n_primary_entry; }
     total.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     stats = total;
 }

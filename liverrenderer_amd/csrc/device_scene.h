@@ -20,6 +20,8 @@ void device_render_moment(DeviceScene *D, const lrt_scene_desc &d, const lrt_ren
 void device_render_moment_samples(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out, lrt_render_stats &stats);
 void device_render_samples(DeviceScene *D, const lrt_scene_desc &d, const lrt_render_opts *opts, uint64_t lane_begin, uint32_t n, float *out, lrt_render_stats &stats);
 void device_trace(DeviceScene *D, const lrt_rays_soa *rays, const lrt_hits_soa *hits, uint32_t n, int any_hit);
+// the per-pixel primary entry the device image holds, as the host built it (scene_prep.h: build_primary_entry); empty: the image has no table
+const std::vector<uint16_t> &device_primary_entry(const DeviceScene *D);
 // test hooks (probes.h): one piece of the shading code per lane.  The kinds are named here because capi.cpp names them and cannot see device code.
 enum ProbeKind { PROBE_EMITTER, PROBE_ENVMAP, PROBE_BSDF, PROBE_PHASE, PROBE_MEDIUM, PROBE_SENSOR, PROBE_KINDS };
 struct ProbeColumn { const float *p; int width; };   // one input array of a probe call: `width` floats per lane

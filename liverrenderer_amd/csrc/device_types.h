@@ -206,11 +206,14 @@ struct DScene {
     const DMeshEmitter *mesh_emitters;   // n_emitters entries (the EXT instances only read them)
     const float *mesh_emitter_tab;       // every mesh emitter's pmf and cdf
     const uint2 *cone_tab;               // per face and side (2 * face + side): the free lengths of LRT_CONE_BINS direction cones as binary16, rounded down (scene_prep.cpp: build_cone_table); null: none
-    int32_t cone_enabled, pad_cone;      // the closed-records volpath kernels only read the table
+    int32_t cone_enabled, primary_enabled;   // the closed-records volpath kernels only read the two tables (primary_tab: at the end of the record)
     const DPhase *phases;                // tabulated / Rayleigh / blended phase functions and a blend's children (DMedium::phase_ext; the EXT instances only read them)
     const float *phase_pool;             // every tabulated entry's interval records and cdf
     const DDeltaEmitter *delta_emitters; // n_emitters entries: spot and directional emitters (the EXT instances only read them); null: the scene has neither
     const DBsdfExt *bsdf_ext;            // one row per BSDF: conductor / plastic / twosided (the EXT instances only read them); null: the scene has none of them
+    // per pixel of the crop window (y * film.width + x): the work item at which trace_lds may start a camera ray's closest-hit traversal, 0xffff: no
+    // triangle can be hit (scene_prep.cpp: build_primary_entry); null: none.  Last, so that every other field keeps its offset.
+    const uint16_t *primary_tab;
 };
 
 // Direction bins of DScene::cone_tab: bin k holds the directions whose cosine to the side's geometric normal is at least LRT_CONE_COSk
@@ -292,6 +295,7 @@ struct DCounters {             // device-resident queue / statistics words
     unsigned long long prof_wg[6];   // LRT_DEBUG_LAUNCH: workgroup timeline, 100 MHz ticks: sum of start, sum of (loop start - start), sum of end, max end, min start + 2^62 trick see kernels.h, sum of barrier waits of thread 0
     unsigned long long n_closed_guard;   // 64-byte-record kernels: trips that broke the layout's premise (radiance before the last trip, an emitter hit that needs MIS)
     unsigned long long n_proven;   // path records loaded from region A: their segment was proven free of surfaces (the 64-byte-record volpath kernels only)
+    unsigned long long n_primary_entry;   // fresh camera lanes whose first ray query did not start at the root, "none" included (DScene::primary_tab; the 64-byte-record volpath kernels only)
 };
 
 // LDS image of the scene for the persistent traversal kernel: [nodes | verts (float4) | tris (4 x u16)] copied verbatim

@@ -112,6 +112,7 @@ struct GlobalTracer {                      // BVH in global memory (any scene si
     static constexpr bool kExt = false;    // (ExtTracer below: spheres, point emitters and area emitters on meshes)
     SceneRef sc; int *stack;
     DEV Hit closest(const Ray &r) const { return trace<false>(sc, r, stack); }
+    DEV Hit closest_from(const Ray &r, uint32_t) const { return trace<false>(sc, r, stack); }      // (the entry is an item of the LDS image: this tracer starts at its root)
     DEV Hit any(const Ray &r) const { return trace<true>(sc, r, stack); }
     DEV SI surface(SceneRef s, const Ray &r, const Hit &h) const;
 };
@@ -152,10 +153,13 @@ __device__ unsigned long long g_trav[8];            // developer counters: [ANY 
 #else
 #define LRT_TRAV_COUNT(k)
 #endif
+// `start`: the work item the traversal begins at: 0, the root, or what the host has proven for this ray (DScene::primary_tab: an inner node or a leaf
+// whose subtree holds every triangle the ray can hit first; 0xffff: there is none)
 template <bool ANY_HIT, int STRIDE>
-DEV Hit trace_lds(const LdsScene &L, const Ray &r, uint16_t *__restrict__ stack /* &lds_stack[threadIdx.x] */) {
+DEV Hit trace_lds(const LdsScene &L, const Ray &r, uint16_t *__restrict__ stack /* &lds_stack[threadIdx.x] */, uint32_t start = 0u) {
     Hit best; best.t = kInf; best.u = best.v = 0.f; best.prim = 0xffffffffu;
     if (L.n_faces == 0) return best;
+    if (start == 0xffffu) return best;
     const V3 o = r.o, d = r.d;
     if (L.root_is_leaf) {
         for (uint32_t i = 0; i < L.root_count; ++i) test_tri_lds(L, L.tris[L.root_first + i], L.root_first + i, o, d, r.maxt, best);
@@ -174,7 +178,7 @@ DEV Hit trace_lds(const LdsScene &L, const Ray &r, uint16_t *__restrict__ stack 
     const float ox = -o.x * ix, oy = -o.y * iy, oz = -o.z * iz;
     const f32x2 vix = { ix, ix }, viy = { iy, iy }, viz = { iz, iz }, vox = { ox, ox }, voy = { oy, oy }, voz = { oz, oz };
     const uint32_t DONE = 0x10000u;
-    int sp = 0; uint32_t cur = 0;
+    int sp = 0; uint32_t cur = start;
     for (;;) {
         while (cur < 0x8000u) {
             LRT_TRAV_COUNT(0)
@@ -222,6 +226,7 @@ struct LdsTracer {
     static constexpr bool kExt = false;
     const LdsScene &L; uint16_t *stack;
     DEV Hit closest(const Ray &r) const { return trace_lds<false, STRIDE>(L, r, stack); }
+    DEV Hit closest_from(const Ray &r, uint32_t start) const { return trace_lds<false, STRIDE>(L, r, stack, start); }     // (trace_lds: `start`)
     DEV Hit any(const Ray &r) const { return trace_lds<true, STRIDE>(L, r, stack); }
     DEV SI surface(SceneRef s, const Ray &r, const Hit &h) const;
 };

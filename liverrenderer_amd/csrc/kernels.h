@@ -117,11 +117,14 @@ DEV Ray camera_ray(SceneRef sc, float ax, float ay) {
 
 // A fresh camera path for rank-local lane index j (integrator.cpp:321-338,449-470; volpath.cpp:93-140 /
 // path.cpp:95-170 up to the loop).
-template <bool LD>
-DEV PathState generate_camera_path(SceneRef sc, RpRef rp, const uint32_t *__restrict__ pixel_list, uint64_t j) {
+// ENTRY (the 64-byte-record volpath kernels): *entry = the pixel's item of DScene::primary_tab when the scene has the table, asked for as soon as the
+// pixel is known, so that the sampler seeding and the camera arithmetic hide the load
+template <bool LD, bool ENTRY = false>
+DEV PathState generate_camera_path(SceneRef sc, RpRef rp, const uint32_t *__restrict__ pixel_list, uint64_t j, uint32_t *entry = nullptr) {
     uint32_t lane;                               // slot_to_lane, written out: the call changes the render kernels' code
     if (pixel_list) { uint32_t pj = (rp.log2_spp != 0xffffffffu) ? (uint32_t) (j >> rp.log2_spp) : (uint32_t) (j / rp.spp); lane = pixel_list[pj] * rp.spp + (uint32_t) (j - (uint64_t) pj * rp.spp); }
     else lane = (uint32_t) j;
+    if (ENTRY && sc.primary_enabled) *entry = sc.primary_tab[(rp.log2_spp != 0xffffffffu) ? (lane >> rp.log2_spp) : (lane / rp.spp)];      // (lane_to_pixel's index)
     SamplerT<LD> rng = lane_rng_pass_start<LD>(rp, lane, j);
     int px, py; lane_to_pixel(sc, rp, lane, &px, &py);
     float jx, jy; rng.next2(jx, jy);
@@ -249,7 +252,7 @@ struct WaveCount {
 // measured at 2.5 % on C3: it keeps the phase function and the emitter value alive through the march.  DESIGN.md section 6c.)
 template <bool HET, bool CLOSED = false, typename SMP, typename TR, typename CNT>
 DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const TR &tr, CNT &n_shadow, CNT &n_extra, bool fresh = false, StampClock *clk = nullptr,
-                           unsigned long long *guard = nullptr) {
+                           unsigned long long *guard = nullptr, uint32_t entry = 0u) {
     constexpr bool PRE = !HET;
     uint32_t depth = s.flags & PF_DEPTH_MASK;
     bool proven_empty = (s.flags & PF_NOHIT) != 0;
@@ -417,7 +420,8 @@ DEV bool volpath_iteration(SceneRef sc, RpRef rp, PathState &s, SMP &rng, const 
     bool intersect = active_surface && !escaped_medium;   // medium lanes already hold si (PRE: its hit, and the ray is still the one queried)
     if (PRE) {
         Hit h = hkeep;
-        if (intersect) h = tr.closest(ray);
+        // (CLOSED: `entry` is the camera ray's start item on a fresh lane and 0, the root, on every other: one traversal serves both)
+        if (intersect) { if constexpr (CLOSED) h = tr.closest_from(ray, entry); else h = tr.closest(ray); }
         if (active_surface) si = tr.surface(sc, ray, h);
     } else if (intersect) { Hit h = tr.closest(ray); si = tr.surface(sc, ray, h); }
     if (active_surface) {
@@ -720,6 +724,7 @@ k_render(ScenePtr scp, LaunchPtr lp) {
     WaveCount wc_shadow{ &s_cnt[0] }, wc_extra{ &s_cnt[1] };
     uint32_t n_shadow = 0, n_extra = 0, n_trips = 0, n_loaded = 0;
     uint32_t n_proven = 0;                                    // CLOSED: records loaded from region A, a per-wave sum of tile populations like n_loaded
+    uint32_t n_primary = 0;                                   // CLOSED: fresh lanes whose ray query does not start at the root, a per-wave sum of ballots
     if (rp.profile & 1u) t_loop_start = wall_clock64();
     for (;;) {
         if (tid == 0) {
@@ -750,6 +755,7 @@ k_render(ScenePtr scp, LaunchPtr lp) {
 #endif
             bool had_path = false, alive = false;
             PathState s; s.flags = 0; s.lane = 0; s.res = V3(0.f);
+            uint32_t entry = 0u;                                        // CLOSED: where the lane's ray query starts (volpath_iteration)
             if (t < ta + tcl + tb) {
                 uint32_t i;
                 if (t < ta) { i = (t << 6) + lane_in_wave; had_path = i < n_a; }
@@ -760,7 +766,8 @@ k_render(ScenePtr scp, LaunchPtr lp) {
             } else {
                 const uint32_t i = ((t - ta - tcl - tb) << 6) + lane_in_wave;
                 had_path = i < fresh;
-                if (had_path) s = generate_camera_path<LD>(sc, rp, A.pixel_list, A.lane_begin + fresh_base + i);
+                if (had_path) s = generate_camera_path<LD, CLOSED>(sc, rp, A.pixel_list, A.lane_begin + fresh_base + i, &entry);
+                if (CLOSED && sc.primary_enabled) n_primary += (uint32_t) __popcll(__ballot(entry != 0u));
             }
             if (VP_LDS_COUNT) {
                 const uint32_t n_had = (uint32_t) __popcll(__ballot(had_path));       // every path of the tile runs one trip
@@ -790,7 +797,7 @@ k_render(ScenePtr scp, LaunchPtr lp) {
                     StampClock *const pclk = nullptr;
 #endif
                     unsigned long long *const guard = CLOSED ? &A.cnt->n_closed_guard : nullptr;
-                    alive = LDS_BVH ? volpath_iteration<false, CLOSED>(sc, rp, s, rng, tr_lds, wc_shadow, wc_extra, fresh_tile, pclk, guard) : volpath_iteration<false, CLOSED>(sc, rp, s, rng, tr_glb, wc_shadow, wc_extra, fresh_tile, pclk, guard);
+                    alive = LDS_BVH ? volpath_iteration<false, CLOSED>(sc, rp, s, rng, tr_lds, wc_shadow, wc_extra, fresh_tile, pclk, guard, entry) : volpath_iteration<false, CLOSED>(sc, rp, s, rng, tr_glb, wc_shadow, wc_extra, fresh_tile, pclk, guard, entry);
                 }
                 s.rng_state = rng.state;
                 if (!VP_LDS_COUNT) n_trips += 1;
@@ -838,6 +845,7 @@ k_render(ScenePtr scp, LaunchPtr lp) {
         if (n_trips) atomicAdd(&A.cnt->n_iter, (unsigned long long) n_trips);
         if (n_loaded) atomicAdd(&A.cnt->n_records, (unsigned long long) n_loaded);
         if (CLOSED && n_proven) atomicAdd(&A.cnt->n_proven, (unsigned long long) n_proven);
+        if (CLOSED && n_primary) atomicAdd(&A.cnt->n_primary_entry, (unsigned long long) n_primary);
     }
     if (VP_LDS_COUNT) {
         __syncthreads();

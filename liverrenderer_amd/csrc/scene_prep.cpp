@@ -20,6 +20,7 @@ PrepOptions PrepOptions::from_env() {
     if (getenv("LRT_DIST_GRID_RES")) o.dist_grid_res = std::max(8, std::min(256, atoi(getenv("LRT_DIST_GRID_RES"))));
     o.no_nee_reject = getenv("LRT_NO_NEE_REJECT") != nullptr;
     o.no_cone_proof = getenv("LRT_NO_CONE_PROOF") != nullptr;
+    o.no_primary_entry = getenv("LRT_NO_PRIMARY_ENTRY") != nullptr;
     return o;
 }
 
@@ -31,7 +32,7 @@ static void m4_ident(float *m) { for (int i = 0; i < 16; ++i) m[i] = (i % 5 == 0
 // include/mitsuba/render/sensor.h:234-269 + include/mitsuba/core/transform.h:393-410:
 // sample_to_camera = inverse of (scale * translate * scale * translate * perspective), built
 // from the analytic inverses exactly as Transform::inverse_transpose composes them.
-static void build_camera(const lrt_scene_desc &d, DCamera &cam, DFilm &film) {
+void build_camera(const lrt_scene_desc &d, DCamera &cam, DFilm &film) {
     const lrt_film_desc &F = d.film; const lrt_sensor_desc &C = d.sensor;
     float fw = (float) F.width, fh = (float) F.height;
     float rsx = (float) F.crop_width / fw, rsy = (float) F.crop_height / fh, rox = (float) F.crop_offset_x / fw, roy = (float) F.crop_offset_y / fh;
@@ -362,6 +363,199 @@ void build_cone_table(const lrt_scene_desc &d, std::vector<uint16_t> &out) {
     }
 }
 
+// ---- the per-pixel primary entry (scene_prep.h: build_primary_entry).  Float64 throughout; the margins below are for the device's float32.
+// Camera.  camera_ray forms r = s2c (a, b, 0, 1) with a = spx * scale_x + offset_x + ppo_x (b alike), divides by r.w and normalises: with a bottom row
+// (0, 0, *, w > 0) the direction is H (a, b, 1) up to a positive factor, H = columns 0, 1, 3 of s2c's first three rows.  So a point Y = to_world^-1 (X - eye)
+// of camera space lies on the ray through raster position (q0 / q2 - offset - ppo) / scale, q = H^-1 Y, and only points with q2 > 0 lie on a ray at all.
+// s = q2 grows along every ray, and on a plane 1 / s is affine in the raster position (the map is projective): its extremes over a box lie at the corners.
+// The ray starts at camera-space depth near_clip and ends at far_clip (near_t, far_t): t >= 0 is Y.z >= near_clip.
+// Footprint.  The lanes of pixel (px, py) sample [px, px + 1] x [py, py + 1], closed (px + jitter rounds up to px + 1 in float32); it is dilated by
+// delta = 1/16 pixel, eight times what camera_ray's float32 chain (1e-3 px at x = 1920) and Moeller-Trumbore's inclusive edge tests (1e-6 of a
+// triangle's extent) can move a hit across an edge.
+// Candidates.  Triangles whose projection meets the dilated footprint: bounding box, then the three edge functions moved outward by the box's support
+// (exact for a box and a triangle).  A triangle with a vertex nearer than near_clip (1 - 1e-3), or with q2 <= 0, is not projected: it is a candidate
+// of every pixel.  A projection of zero area keeps the bounding-box test only.
+// Occlusion.  T leaves the set when a candidate A covers the whole dilated footprint (its four corners inside A's projection shrunk by delta, A between
+// near_clip (1 + 1e-3) and far_clip (1 - 1e-3): the float32 test cannot miss A) and max s of A over the corners < min s of T's plane over the corners
+// by a relative 1e-4; never when T's plane reaches s <= 0 inside the footprint, and never on a tie (test_tri_lds breaks ties by face index).
+// Entry.  The lowest node or leaf whose subtree holds every slot left; none left: LRT_PRIMARY_NONE.
+namespace {
+struct PeTri {
+    double x[3], y[3];                                  // raster vertices
+    double ex[3], ey[3], ec[3], el[3];                  // edge functions ex * px + ey * py + ec, >= 0 inside; el = |(ex, ey)|
+    double gx, gy, g0;                                  // 1 / s as an affine function of the raster position
+    double lox, hix, loy, hiy;
+    bool projected, has_area, plane_ok, occluder;
+};
+void inverse3d(const double m[3][3], double o[3][3], double &det) {
+    det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) + m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+    const double id = 1.0 / det;
+    o[0][0] = (m[1][1] * m[2][2] - m[1][2] * m[2][1]) * id; o[0][1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) * id; o[0][2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) * id;
+    o[1][0] = (m[1][2] * m[2][0] - m[1][0] * m[2][2]) * id; o[1][1] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) * id; o[1][2] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) * id;
+    o[2][0] = (m[1][0] * m[2][1] - m[1][1] * m[2][0]) * id; o[2][1] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) * id; o[2][2] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) * id;
+}
+// The BVH as a tree of ids: inner node n -> n, leaf l -> n_nodes + l
+struct PeTree {
+    uint32_t n_nodes = 0; std::vector<int32_t> parent; std::vector<uint16_t> depth; std::vector<uint32_t> leaf_first, face_leaf;
+    bool ok = false;
+    explicit PeTree(const HostBVH &b, uint32_t n_faces) {
+        n_nodes = (uint32_t) (b.nodes.size() / 16); const size_t n_slots = b.tris.size() / 12;
+        if (!n_nodes || b.root_is_leaf) return;
+        parent.assign(n_nodes, -2); depth.assign(n_nodes, 0); face_leaf.assign(n_faces, 0xffffffffu);
+        std::vector<uint32_t> todo{ 0u }; parent[0] = -1;
+        while (!todo.empty()) {
+            const uint32_t n = todo.back(); todo.pop_back();
+            int32_t refs[4]; memcpy(refs, &b.nodes[16 * (size_t) n + 12], 16);
+            for (int c = 0; c < 2; ++c) {
+                if (refs[c] >= 0) {
+                    if ((uint32_t) refs[c] >= n_nodes || parent[refs[c]] != -2) return;
+                    parent[refs[c]] = (int32_t) n; depth[refs[c]] = (uint16_t) (depth[n] + 1); todo.push_back((uint32_t) refs[c]);
+                } else {
+                    const uint32_t first = (uint32_t) ~refs[c], count = (uint32_t) refs[2 + c];
+                    if (!count || (size_t) first + count > n_slots) return;
+                    const uint32_t id = n_nodes + (uint32_t) leaf_first.size();
+                    leaf_first.push_back(first); parent.push_back((int32_t) n); depth.push_back((uint16_t) (depth[n] + 1));
+                    for (uint32_t s = first; s < first + count; ++s) { uint32_t f; memcpy(&f, &b.tris[12 * (size_t) s + 3], 4); if (f >= n_faces) return; face_leaf[f] = id; }
+                }
+            }
+        }
+        ok = true;
+    }
+    int32_t lca(int32_t a, int32_t b) const {           // -1: the empty set
+        if (a < 0) return b;
+        if (b < 0) return a;
+        while (a != b) { if (depth[a] >= depth[b]) a = parent[a]; else b = parent[b]; }
+        return a;
+    }
+    uint16_t item(int32_t id) const { return id < 0 ? (uint16_t) LRT_PRIMARY_NONE : ((uint32_t) id >= n_nodes ? (uint16_t) (0x8000u | leaf_first[(uint32_t) id - n_nodes]) : (uint16_t) id); }
+};
+}
+
+bool primary_entry_valid(const HostBVH &bvh, const std::vector<uint16_t> &tab) {
+    const PeTree T(bvh, (uint32_t) (bvh.tris.size() / 12));           // (every face has one slot: a face index is below the slot count)
+    if (!T.ok || T.n_nodes > 0x8000u) return false;
+    std::vector<char> starts(0x8000u, 0);
+    for (uint32_t f : T.leaf_first) { if (f >= 0x7fffu) return false; starts[f] = 1; }
+    for (uint16_t it : tab) if (it != LRT_PRIMARY_NONE && !(it < 0x8000u ? it < T.n_nodes : starts[it & 0x7fffu])) return false;
+    return true;
+}
+
+void build_primary_entry(const lrt_scene_desc &d, const HostBVH &bvh, std::vector<uint16_t> &out, const PrimaryEntryTune &tune) {
+    out.clear();
+    const uint32_t nf = d.n_faces;
+    if (!nf || bvh.root_is_leaf) return;
+    for (size_t i = 0; i < 3 * (size_t) d.n_vertices; ++i) if (!std::isfinite(d.positions[i])) return;
+    DCamera cam; DFilm film; memset(&cam, 0, sizeof(cam)); memset(&film, 0, sizeof(film)); build_camera(d, cam, film);
+    const int W = film.width, Hh = film.height;
+    if (W <= 0 || Hh <= 0) return;
+    const float *m = cam.s2c;
+    if (m[12] != 0.f || m[13] != 0.f || !(m[15] > 0.f) || !(cam.near_clip > 0.f) || !(cam.far_clip > cam.near_clip)) return;
+    if (!(film.scale_x > 0.f) || !(film.scale_y > 0.f)) return;
+    const double Hm[3][3] = { { m[0], m[1], m[3] }, { m[4], m[5], m[7] }, { m[8], m[9], m[11] } };
+    const double Rm[3][3] = { { cam.to_world[0], cam.to_world[1], cam.to_world[2] }, { cam.to_world[4], cam.to_world[5], cam.to_world[6] }, { cam.to_world[8], cam.to_world[9], cam.to_world[10] } };
+    double Hi[3][3], Ri[3][3], dh, dr; inverse3d(Hm, Hi, dh); inverse3d(Rm, Ri, dr);
+    if (!std::isfinite(1.0 / dh) || !std::isfinite(1.0 / dr)) return;
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(cam.to_world[i])) return;
+    const PeTree tree(bvh, nf);
+    if (!tree.ok) return;
+    for (uint32_t f = 0; f < nf; ++f) if (tree.face_leaf[f] == 0xffffffffu) return;
+    const double eye[3] = { cam.to_world[3], cam.to_world[7], cam.to_world[11] };
+    const double offx = (double) film.offset_x + (double) cam.ppo_x, offy = (double) film.offset_y + (double) cam.ppo_y, isx = 1.0 / (double) film.scale_x, isy = 1.0 / (double) film.scale_y;
+    const double near_lo = (double) cam.near_clip * (1.0 - 1e-3), near_hi = (double) cam.near_clip * (1.0 + 1e-3), far_lo = (double) cam.far_clip * (1.0 - 1e-3);
+    const double delta = tune.delta, half = 0.5 + delta;
+    const int cox = film.crop_offset_x, coy = film.crop_offset_y;
+
+    std::vector<PeTri> T(nf);
+    int32_t everywhere = -1;                                 // the subtree of the triangles that are not projected
+    for (uint32_t f = 0; f < nf; ++f) {
+        PeTri &t = T[f]; t.projected = true; t.has_area = t.plane_ok = t.occluder = false;
+        double w[3], zmin = INFINITY, zmax = -INFINITY;
+        for (int j = 0; j < 3; ++j) {
+            const float *p = &d.positions[3 * (size_t) d.faces[3 * (size_t) f + j]];
+            const double Y[3] = { p[0] - eye[0], p[1] - eye[1], p[2] - eye[2] };
+            double c[3], q[3];
+            for (int a = 0; a < 3; ++a) c[a] = Ri[a][0] * Y[0] + Ri[a][1] * Y[1] + Ri[a][2] * Y[2];
+            for (int a = 0; a < 3; ++a) q[a] = Hi[a][0] * c[0] + Hi[a][1] * c[1] + Hi[a][2] * c[2];
+            if (!(c[2] >= near_lo) || !(q[2] > 0.0)) { t.projected = false; break; }
+            t.x[j] = (q[0] / q[2] - offx) * isx; t.y[j] = (q[1] / q[2] - offy) * isy; w[j] = 1.0 / q[2];
+            zmin = std::min(zmin, c[2]); zmax = std::max(zmax, c[2]);
+            if (!std::isfinite(t.x[j]) || !std::isfinite(t.y[j]) || !std::isfinite(w[j])) { t.projected = false; break; }
+        }
+        if (!t.projected) { everywhere = tree.lca(everywhere, (int32_t) tree.face_leaf[f]); continue; }
+        t.lox = std::min(t.x[0], std::min(t.x[1], t.x[2])); t.hix = std::max(t.x[0], std::max(t.x[1], t.x[2]));
+        t.loy = std::min(t.y[0], std::min(t.y[1], t.y[2])); t.hiy = std::max(t.y[0], std::max(t.y[1], t.y[2]));
+        const double area2 = (t.x[1] - t.x[0]) * (t.y[2] - t.y[0]) - (t.x[2] - t.x[0]) * (t.y[1] - t.y[0]), sg = area2 > 0.0 ? 1.0 : -1.0;
+        double lmax = 0.0;
+        for (int i = 0; i < 3; ++i) {
+            const int j = (i + 1) % 3;
+            t.ex[i] = -sg * (t.y[j] - t.y[i]); t.ey[i] = sg * (t.x[j] - t.x[i]); t.ec[i] = -(t.ex[i] * t.x[i] + t.ey[i] * t.y[i]);
+            t.el[i] = std::sqrt(t.ex[i] * t.ex[i] + t.ey[i] * t.ey[i]); lmax = std::max(lmax, t.el[i]);
+        }
+        t.has_area = area2 != 0.0 && std::isfinite(area2);
+        // the plane's 1 / s from its values at the vertices: only where the projection is no sliver (relative conditioning 1e6 at the worst)
+        t.plane_ok = t.has_area && std::fabs(area2) > 1e-6 * lmax * lmax;
+        if (t.plane_ok) {
+            t.gx = ((w[1] - w[0]) * (t.y[2] - t.y[0]) - (w[2] - w[0]) * (t.y[1] - t.y[0])) / area2;
+            t.gy = ((t.x[1] - t.x[0]) * (w[2] - w[0]) - (t.x[2] - t.x[0]) * (w[1] - w[0])) / area2;
+            t.g0 = w[0] - t.gx * t.x[0] - t.gy * t.y[0];
+            t.plane_ok = std::isfinite(t.gx) && std::isfinite(t.gy) && std::isfinite(t.g0);
+        }
+        t.occluder = t.plane_ok && zmin >= near_hi && zmax <= far_lo;
+    }
+    // the candidates of every pixel: count, then fill
+    const size_t npix = (size_t) W * (size_t) Hh;
+    auto for_pixels = [&](uint32_t f, auto &&fn) {
+        const PeTri &t = T[f];
+        const double x0 = std::ceil(t.lox - 1.0 - delta) - cox, x1 = std::floor(t.hix + delta) - cox, y0 = std::ceil(t.loy - 1.0 - delta) - coy, y1 = std::floor(t.hiy + delta) - coy;
+        if (!(x1 >= 0.0) || !(y1 >= 0.0) || !(x0 <= W - 1.0) || !(y0 <= Hh - 1.0)) return;
+        const int ix0 = (int) std::max(x0, 0.0), ix1 = (int) std::min(x1, W - 1.0), iy0 = (int) std::max(y0, 0.0), iy1 = (int) std::min(y1, Hh - 1.0);
+        double sup[3]; for (int i = 0; i < 3; ++i) sup[i] = half * (std::fabs(t.ex[i]) + std::fabs(t.ey[i]));
+        for (int y = iy0; y <= iy1; ++y) {
+            const double cy = (double) (y + coy) + 0.5;
+            for (int x = ix0; x <= ix1; ++x) {
+                const double cx = (double) (x + cox) + 0.5;
+                bool in = true;
+                if (t.has_area) for (int i = 0; i < 3; ++i) in = in && t.ex[i] * cx + t.ey[i] * cy + t.ec[i] + sup[i] >= 0.0;
+                if (in) fn((size_t) y * W + x);
+            }
+        }
+    };
+    std::vector<uint32_t> start(npix + 1, 0);
+    for (uint32_t f = 0; f < nf; ++f) if (T[f].projected) for_pixels(f, [&](size_t p) { ++start[p + 1]; });
+    for (size_t p = 0; p < npix; ++p) start[p + 1] += start[p];
+    std::vector<uint16_t> cand(start[npix]); std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+    for (uint32_t f = 0; f < nf; ++f) if (T[f].projected) for_pixels(f, [&](size_t p) { cand[fill[p]++] = (uint16_t) f; });   // (lds_image_fits: faces < 32768; the caller builds the table for LDS images only)
+    // occlusion and entry
+    out.assign(npix, 0);
+    for (int y = 0; y < Hh; ++y) for (int x = 0; x < W; ++x) {
+        const size_t p = (size_t) y * W + x; const uint32_t b = start[p], e = start[p + 1];
+        int32_t id = everywhere;
+        if (e - b == 1) id = tree.lca(id, (int32_t) tree.face_leaf[cand[b]]);
+        else if (e > b) {
+            const double cx = (double) (x + cox) + 0.5, cy = (double) (y + coy) + 0.5;
+            double cover = INFINITY;                         // the least, over the covering candidates, of max s over the footprint
+            for (uint32_t k = b; k < e; ++k) {
+                const PeTri &A = T[cand[k]];
+                if (!A.occluder) continue;
+                bool in = true;
+                for (int i = 0; i < 3; ++i) in = in && A.ex[i] * cx + A.ey[i] * cy + A.ec[i] - half * (std::fabs(A.ex[i]) + std::fabs(A.ey[i])) >= delta * A.el[i];
+                if (!in) continue;
+                const double gmin = A.gx * cx + A.gy * cy + A.g0 - half * (std::fabs(A.gx) + std::fabs(A.gy));
+                if (gmin > 0.0) cover = std::min(cover, 1.0 / gmin);
+            }
+            for (uint32_t k = b; k < e; ++k) {
+                const PeTri &t = T[cand[k]];
+                if (cover < INFINITY && t.plane_ok) {
+                    const double gc = t.gx * cx + t.gy * cy + t.g0, gs = half * (std::fabs(t.gx) + std::fabs(t.gy));
+                    if (gc - gs > 0.0 && 1.0 / (gc + gs) > cover * (1.0 + tune.depth_margin)) continue;      // behind the cover everywhere in the footprint
+                }
+                id = tree.lca(id, (int32_t) tree.face_leaf[cand[k]]);
+            }
+        }
+        out[p] = tree.item(id);
+    }
+}
+
 // include/mitsuba/render/fresnel.h:327-355, in float32 with the fused multiply-adds the reference's dr::fmadd / dr::horner are
 static float fresnel_diffuse_reflectance(float eta) {
     const float inv_eta = 1.f / eta;
@@ -457,7 +651,17 @@ void prepare_geometry(const lrt_scene_desc &d, const PrepOptions &opt, PreparedS
     // closed-records volpath kernels read it, and those run on the LDS image, without spheres, beside the distance field, on scenes that
     // closed_records() accepts: the build is quadratic in the faces and is not paid for a scene whose renders can never use it.  (A parameter update
     // that makes a scene qualify later renders it with 64-byte records and no table, as with LRT_NO_CONE_PROOF.)
-    if (P.use_lds && !P.ext && sc.grid.enabled && !opt.no_cone_proof && closed_records(d, d.sensor.medium)) { build_cone_table(d, P.cone_tab); sc.cone_enabled = 1; }
+    const bool closed_lds = P.use_lds && !P.ext && sc.grid.enabled && closed_records(d, d.sensor.medium);
+    if (closed_lds && !opt.no_cone_proof) { build_cone_table(d, P.cone_tab); sc.cone_enabled = 1; }
+    // ---- per-pixel primary entry: where a camera ray's traversal may start (build_primary_entry).  Read by the same kernels, built under the same
+    // condition; it depends on the geometry, the sensor, the film size and the crop window, none of which a parameter update changes.
+    if (closed_lds && !bvh.root_is_leaf && !opt.no_primary_entry) {
+        build_primary_entry(d, bvh, P.primary_tab);
+        if (!P.primary_tab.empty()) {
+            if (!primary_entry_valid(bvh, P.primary_tab)) throw std::runtime_error("primary entry table: an item names no node or leaf of the BVH");
+            sc.primary_enabled = 1;
+        }
+    }
 }
 
 void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedScene &P) {

@@ -17,9 +17,10 @@ struct PrepOptions {
     int dist_grid_res = 0;         // LRT_DIST_GRID_RES clamped to 8 .. 256; 0: by the face count
     bool no_nee_reject = false;    // LRT_NO_NEE_REJECT
     bool no_cone_proof = false;    // LRT_NO_CONE_PROOF: no per-face cone table (build_cone_table)
-    size_t lds_limit = 0;          // LDS bytes a workgroup may ask for (device.hip: the opt-in maximum minus the kernels' static words)
+    bool no_primary_entry = false; // LRT_NO_PRIMARY_ENTRY: no per-pixel primary entry (build_primary_entry)
+    size_t lds_limit = 0;         // LDS bytes a workgroup may ask for (device.hip: the opt-in maximum minus the kernels' static words)
     int n_cus = 256;               // compute units of the device: the upload side sets it and takes it back for the launch geometry; the preparation does not use it
-    static PrepOptions from_env(); // reads the six switches; lds_limit and n_cus stay at their defaults
+    static PrepOptions from_env(); // reads the seven switches; lds_limit and n_cus stay at their defaults
 };
 
 // BSDF leaf flags as DBsdf::flags stores them (dshade.h names the same values F_DELTA, F_SMOOTH, F_NULL; device.hip asserts that they agree)
@@ -44,7 +45,8 @@ struct PreparedScene {
     float grid_abs_margin = 0.f;                       // k_build_dist_grid's margin
     std::vector<DPhase> phases; std::vector<float> phase_pool;   // DScene::phases / phase_pool (prepare_phases); empty: the description has no phase table
     std::vector<uint16_t> cone_tab;                    // build_cone_table's rows, 2 * LRT_CONE_BINS binary16 per face; empty: no table (sc.cone_enabled = 0)
-    bool env_interior_positive = false;                // envmap: rows 1..h-2 of the sampling density strictly positive
+    std::vector<uint16_t> primary_tab;                 // build_primary_entry's items, one per pixel of the crop window; empty: no table (sc.primary_enabled = 0)
+    bool env_interior_positive = false;               // envmap: rows 1..h-2 of the sampling density strictly positive
     bool ext = false, has_area_emitter = false, has_het = false, has_non_bio = false, prb_null = false, use_lds = false;   // DeviceScene's flags of the same names
     bool smooth_bsdf = false;                          // a conductor / plastic / twosided sits on a shape (it sets `ext` too; prbvolpath names it in its refusal)
     int bvh_leaf = 4;
@@ -58,6 +60,9 @@ void prepare_geometry(const lrt_scene_desc &d, const PrepOptions &opt, PreparedS
 void prepare_shading(const lrt_scene_desc &d, const PrepOptions &opt, PreparedScene &P);
 PreparedScene prepare_scene(const lrt_scene_desc &d, const PrepOptions &opt);
 
+// DScene::cam and DScene::film of a description (prepare_shading's; build_primary_entry and its host test read the same constants)
+void build_camera(const lrt_scene_desc &d, DCamera &cam, DFilm &film);
+
 // Per-face cone table: out[(2 * f + s) * LRT_CONE_BINS + k] = R as binary16, rounded down, with this property: a segment whose origin lies on face f,
 // displaced to side s as spawn_ray displaces a float32 hit point (s = 0: along the geometric normal the device computes, flip_normals applied; s = 1:
 // against it), whose direction makes a cosine of at least LRT_CONE_COSk with that side's normal and whose length is at most R meets no triangle of
@@ -65,6 +70,17 @@ PreparedScene prepare_scene(const lrt_scene_desc &d, const PrepOptions &opt);
 void build_cone_table(const lrt_scene_desc &d, std::vector<uint16_t> &out);
 // a table entry as the device reads it
 float cone_table_value(uint16_t h);
+
+// Per-pixel primary entry: out[y * crop_width + x] (crop-local pixel, the index lane_to_pixel forms) = the 16-bit work item of trace_lds at which the
+// closest-hit traversal of ANY camera ray through that pixel may start without changing its result: an inner node index (0, the root: nothing is
+// claimed), 0x8000 | first slot of a leaf, or LRT_PRIMARY_NONE: no triangle can be hit.  Built from the device's own float32 camera and film constants
+// (build_camera) widened to double.  Empty: no table (a camera the construction does not cover, non-finite vertices, a root leaf).
+// `tune`: the construction's margins; only the host test changes them, to seed a mistake.  (scene_prep.cpp has the construction.)
+#define LRT_PRIMARY_NONE 0xffffu
+struct PrimaryEntryTune { double delta = 1.0 / 16.0, depth_margin = 1e-4; };
+void build_primary_entry(const lrt_scene_desc &d, const HostBVH &bvh, std::vector<uint16_t> &out, const PrimaryEntryTune &tune = PrimaryEntryTune());
+// every item names a node of the BVH, the first slot of one of its leaves, or LRT_PRIMARY_NONE (the upload refuses a table that fails this)
+bool primary_entry_valid(const HostBVH &bvh, const std::vector<uint16_t> &tab);
 
 // bytes of the LDS image of a BVH: nodes, float4 vertices, 8-byte triangle slots, 16-bit traversal stacks of 1024 threads
 size_t lds_image_bytes(const HostBVH &b, uint32_t n_vertices);
