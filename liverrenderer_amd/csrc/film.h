@@ -1,6 +1,7 @@
 // Film accumulation on the device: the reconstruction filter, a sample's footprint, and the two wave-level routes every kernel that writes
-// a film takes (box-filter runs, wide-filter group walk).  Text of kernels.h: included there, inside namespace lrt, after the lane helpers
-// (lane_to_pixel, lane_jitter, lane_local_index) it builds on; kernels_prb.h, kernels_aov.h and kernels_moment.h use it through kernels.h.
+// a film takes (box-filter runs, wide-filter group walk), and the box-filter route of the 64-byte-record kernels.  Text of kernels.h:
+// included there, inside namespace lrt, after the lane helpers (lane_to_pixel, lane_jitter, lane_local_index) it builds on;
+// kernels_prb.h, kernels_aov.h and kernels_moment.h use it through kernels.h.
 
 template <typename FP> DEV float estrin10(float x, FP c) {
     float x2 = x * x, x4 = x2 * x2, x8 = x4 * x4;
@@ -113,6 +114,57 @@ DEV void finish_paths_wave(SceneRef sc, RpRef rp, float *__restrict__ film, floa
         float *p = film + (size_t) pixel * F.channels;
         atomicAdd(p + 0, v[0]); atomicAdd(p + 1, v[1]); atomicAdd(p + 2, v[2]);
         if (F.has_alpha) { atomicAdd(p + 3, v[4]); atomicAdd(p + 4, v[3]); } else atomicAdd(p + 3, v[3]);
+    }
+}
+
+// ---- The box-filter route of the 64-byte-record volpath kernels (closed_records(): only a path's last trip adds radiance, so a lane that retires
+// anywhere else carries L = +0 exactly).  W and alpha are counts of lanes, taken from ballots (film_runs.h), and RGB costs nothing where it is zero:
+//   W      once per sample, where the sample is born (count_born_wave, the fresh tiles): a lane born in a launch retires in it, the sum of small
+//          integers in float is exact in any grouping, so the film's W is the same number whenever it is added;
+//   RGB    the runs and the scan's tree are finish_paths_wave's (runs of consecutive retiring lanes of one pixel: the non-zero members of a run are
+//          associated as there), but the scan is skipped when no retiring lane of the wave has a non-zero L and a run whose sums are all zero issues
+//          no atomic: x + (+-0) = x for every x a film holds (sums start at +0 and never become -0).  NaN compares non-zero and goes through;
+//   alpha  the valid samples.  A path's validity is only ever switched on (volpath_iteration), and generate_camera_path switches it on at birth
+//          when the environment is visible (LRT_BORN_VALID: the same for every lane of a launch): alpha is then W and is counted with it.  Otherwise it
+//          is the run's valid retiring lanes, at retirement, when the wave retires a valid lane at all.
+// Both form the film pixel as lane / spp: lane_to_pixel splits that index by the film's width and film_pixel_index puts it together again.
+DEV uint32_t lane_film_pixel(RpRef rp, uint32_t lane) { return (rp.log2_spp != 0xffffffffu) ? (lane >> rp.log2_spp) : (lane / rp.spp); }
+
+// called by EVERY lane of a fresh tile, right after generate_camera_path: `born` = the lane holds a new sample, of film pixel `pixel` (0xffffffff without one)
+DEV void count_born_wave(SceneRef sc, RpRef rp, float *__restrict__ film, const float *__restrict__ sample_out, bool born, uint32_t pixel) {
+    FilmRef F = sc.film;
+    if (sample_out || F.rfilter != LRT_RFILTER_BOX) return;                       // (finish_path counts these at retirement)
+    const uint32_t prev = wave_prev(pixel, 0xfffffffeu), next = wave_next(pixel, 0xfffffffeu);
+    const unsigned long long heads = __ballot(pixel != prev || !born), members = __ballot(born);
+    if (born && pixel != next) {
+        float *p = film + (size_t) pixel * (uint32_t) F.channels;
+        const float n = (float) film_run_count(heads, members, threadIdx.x & 63u);
+        atomicAdd(p + F.channels - 1, n);                                         // W is a film's last channel
+        if (F.has_alpha && LRT_BORN_VALID(sc, rp)) atomicAdd(p + 3, n);
+    }
+}
+
+// called by EVERY lane of a wave, as finish_paths_wave is
+DEV void finish_paths_wave_closed(SceneRef sc, RpRef rp, float *__restrict__ film, float *__restrict__ sample_out,
+                                  uint64_t sample_base, bool finishing, uint32_t lane, V3 L, bool valid) {
+    FilmRef F = sc.film;
+    if (sample_out || F.rfilter != LRT_RFILTER_BOX) {
+        if (finishing) finish_path(sc, rp, film, sample_out, sample_base, lane, L, valid);
+        return;
+    }
+    const unsigned long long lit = __ballot(finishing && (L.x != 0.f || L.y != 0.f || L.z != 0.f));
+    const unsigned long long opaque = (F.has_alpha && !LRT_BORN_VALID(sc, rp)) ? __ballot(finishing && valid) : 0ull;
+    if ((lit | opaque) == 0ull) return;
+    const uint32_t pixel = finishing ? lane_film_pixel(rp, lane) : 0xffffffffu;
+    const uint32_t prev = wave_prev(pixel, 0xfffffffeu), next = wave_next(pixel, 0xfffffffeu);
+    const bool head = pixel != prev || !finishing;
+    float v[3] = { finishing ? L.x : 0.f, finishing ? L.y : 0.f, finishing ? L.z : 0.f };
+    if (lit) wave_segmented_sums(v, head);
+    const unsigned long long heads = opaque ? __ballot(head) : 0ull;
+    if (finishing && pixel != next) {
+        float *p = film + (size_t) pixel * (uint32_t) F.channels;
+        if (v[0] != 0.f || v[1] != 0.f || v[2] != 0.f) { atomicAdd(p + 0, v[0]); atomicAdd(p + 1, v[1]); atomicAdd(p + 2, v[2]); }
+        if (opaque) atomicAdd(p + 3, (float) film_run_count(heads, opaque, threadIdx.x & 63u));       // (every lane of a tail's run retires)
     }
 }
 

@@ -13,6 +13,7 @@
 #pragma once
 #include "dshade.h"
 #include "record.h"
+#include "film_runs.h"
 
 namespace lrt {
 
@@ -115,16 +116,24 @@ DEV Ray camera_ray(SceneRef sc, float ax, float ay) {
     return ray;
 }
 
+// Is a camera path valid (PF_VALID: it counts into the film's alpha) from its first trip on?  volpath.cpp:103 / path.cpp:116: when the environment is
+// visible.  The same for every lane of a launch; generate_camera_path sets the flag by it and the closed-records film route (film.h) counts alpha by it.
+// (a macro: through a function the compiler schedules every render kernel's fresh branch differently)
+#define LRT_BORN_VALID(sc, rp) (!(rp).hide_emitters && (sc).env.type >= 0)
+
 // A fresh camera path for rank-local lane index j (integrator.cpp:321-338,449-470; volpath.cpp:93-140 /
 // path.cpp:95-170 up to the loop).
 // ENTRY (the 64-byte-record volpath kernels): *entry = the pixel's item of DScene::primary_tab when the scene has the table, asked for as soon as the
-// pixel is known, so that the sampler seeding and the camera arithmetic hide the load
+// pixel is known, so that the sampler seeding and the camera arithmetic hide the load; *film_pixel = that pixel, which count_born_wave (film.h) counts the sample into
 template <bool LD, bool ENTRY = false>
-DEV PathState generate_camera_path(SceneRef sc, RpRef rp, const uint32_t *__restrict__ pixel_list, uint64_t j, uint32_t *entry = nullptr) {
+DEV PathState generate_camera_path(SceneRef sc, RpRef rp, const uint32_t *__restrict__ pixel_list, uint64_t j, uint32_t *entry = nullptr, uint32_t *film_pixel = nullptr) {
     uint32_t lane;                               // slot_to_lane, written out: the call changes the render kernels' code
     if (pixel_list) { uint32_t pj = (rp.log2_spp != 0xffffffffu) ? (uint32_t) (j >> rp.log2_spp) : (uint32_t) (j / rp.spp); lane = pixel_list[pj] * rp.spp + (uint32_t) (j - (uint64_t) pj * rp.spp); }
     else lane = (uint32_t) j;
-    if (ENTRY && sc.primary_enabled) *entry = sc.primary_tab[(rp.log2_spp != 0xffffffffu) ? (lane >> rp.log2_spp) : (lane / rp.spp)];      // (lane_to_pixel's index)
+    if (ENTRY) {                                 // (lane_to_pixel's index: the crop-local film pixel, which count_born_wave needs again)
+        *film_pixel = (rp.log2_spp != 0xffffffffu) ? (lane >> rp.log2_spp) : (lane / rp.spp);
+        if (sc.primary_enabled) *entry = sc.primary_tab[*film_pixel];
+    }
     SamplerT<LD> rng = lane_rng_pass_start<LD>(rp, lane, j);
     int px, py; lane_to_pixel(sc, rp, lane, &px, &py);
     float jx, jy; rng.next2(jx, jy);
@@ -135,7 +144,7 @@ DEV PathState generate_camera_path(SceneRef sc, RpRef rp, const uint32_t *__rest
     s.tdepth = 0.f; s.si_t = kInf; s.ff_t = u2f(0x7fc00000u); s.bio_dist = u2f(0x7fc00000u); s.bio_hep = false; s.hit = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int a = 0; a < 2; ++a) for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) s.W[a][i][j] = 1.f;         // volpathmis.cpp:158-159
                                                      // biovolpath.cpp:125,129: si = zeros (t = inf), tissueDepth = 0
-    bool env_visible = !rp.hide_emitters && sc.env.type >= 0;
+    bool env_visible = LRT_BORN_VALID(sc, rp);
     uint32_t flags = env_visible ? PF_VALID : 0u;
     if (rp.integrator == LRT_INTEGRATOR_PATH) flags |= PF_SPECULAR;                 // prev_bsdf_delta = true
     else {
@@ -633,7 +642,8 @@ namespace lrt {
 // n_a + n_b + n_c + n_l <= P, so the regions never collide.  No cross-workgroup dependency exists besides the lane ticket and the
 // film atomics; every wave leaves its loops once the ticket is exhausted and its pool is empty.
 // READLANE: how the three regions' slot bases reach the lanes (see below)
-template <RecordLayout LAYOUT = RecordLayout::Wide, bool READLANE = true, bool COMPACT = false, bool LONGQ = false>
+// COUNTED: the film route of the 64-byte-record kernels (film.h: finish_paths_wave_closed; W was counted when the sample was born)
+template <RecordLayout LAYOUT = RecordLayout::Wide, bool READLANE = true, bool COMPACT = false, bool LONGQ = false, bool COUNTED = false>
 DEV void retire_and_compact_wave(SceneRef sc, RpRef rp, bool had_path, bool alive, const PathState &s,
                                  float *__restrict__ film, float *__restrict__ sample_out, uint64_t sample_base,
                                  const LRT_CONST DPathStreams &qout, size_t pool, uint32_t P, uint32_t *s_out /* LDS [3] */, StampClock *clk = nullptr) {
@@ -666,7 +676,8 @@ DEV void retire_and_compact_wave(SceneRef sc, RpRef rp, bool had_path, bool aliv
     }
     if (clk) clk->at(6);                                                // (stores issued)
     if (rp.pass_out && had_path && !alive) rp.pass_out[lane_local_index(rp, s.lane)] = s.rng_state;       // next pass continues this stream
-    finish_paths_wave(sc, rp, film, sample_out, sample_base, had_path && !alive, s.lane, s.res, (s.flags & PF_VALID) != 0);
+    if (COUNTED) finish_paths_wave_closed(sc, rp, film, sample_out, sample_base, had_path && !alive, s.lane, s.res, (s.flags & PF_VALID) != 0);
+    else finish_paths_wave(sc, rp, film, sample_out, sample_base, had_path && !alive, s.lane, s.res, (s.flags & PF_VALID) != 0);
 }
 
 // 4 waves per SIMD (128 VGPRs): one 1024-thread workgroup per CU, or four 256-thread ones.  BLOCK = 512 (one workgroup per CU, 2 waves per
@@ -766,8 +777,10 @@ k_render(ScenePtr scp, LaunchPtr lp) {
             } else {
                 const uint32_t i = ((t - ta - tcl - tb) << 6) + lane_in_wave;
                 had_path = i < fresh;
-                if (had_path) s = generate_camera_path<LD, CLOSED>(sc, rp, A.pixel_list, A.lane_begin + fresh_base + i, &entry);
+                uint32_t film_pixel = 0xffffffffu;                      // CLOSED: the crop-local pixel of a lane with a new sample
+                if (had_path) s = generate_camera_path<LD, CLOSED>(sc, rp, A.pixel_list, A.lane_begin + fresh_base + i, &entry, &film_pixel);
                 if (CLOSED && sc.primary_enabled) n_primary += (uint32_t) __popcll(__ballot(entry != 0u));
+                if (CLOSED) count_born_wave(sc, rp, A.film, A.sample_out, had_path, film_pixel);      // W: once per sample, here (film.h)
             }
             if (VP_LDS_COUNT) {
                 const uint32_t n_had = (uint32_t) __popcll(__ballot(had_path));       // every path of the tile runs one trip
@@ -803,11 +816,11 @@ k_render(ScenePtr scp, LaunchPtr lp) {
                 if (!VP_LDS_COUNT) n_trips += 1;
             }
 #ifdef LRT_STAMP
-            retire_and_compact_wave<LAYOUT, READLANE, COMPACT, LONGQ>(sc, rp, had_path, alive, s, A.film, A.sample_out, A.sample_base, parity ? A.q0 : A.q1, pool, P, s_out, &clk);
+            retire_and_compact_wave<LAYOUT, READLANE, COMPACT, LONGQ, CLOSED>(sc, rp, had_path, alive, s, A.film, A.sample_out, A.sample_base, parity ? A.q0 : A.q1, pool, P, s_out, &clk);
             clk.at(7);                                                  // film sums + atomics
             if (clk.on && lane_in_wave == 0) atomicAdd(&s_stamp[15], 1ull);
 #else
-            retire_and_compact_wave<LAYOUT, READLANE, COMPACT, LONGQ>(sc, rp, had_path, alive, s, A.film, A.sample_out, A.sample_base, parity ? A.q0 : A.q1, pool, P, s_out);
+            retire_and_compact_wave<LAYOUT, READLANE, COMPACT, LONGQ, CLOSED>(sc, rp, had_path, alive, s, A.film, A.sample_out, A.sample_base, parity ? A.q0 : A.q1, pool, P, s_out);
 #endif
             if ((rp.profile & 1u) && lane_in_wave == 0) {
                 const int region = t < ta ? 0 : (t < ta + tcl ? 1 : (t < ta + tcl + tb ? 2 : 3));
